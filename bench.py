@@ -13,20 +13,31 @@ the timed region and the MAX of the elapsed time.
 A "step" = one pass of the hot path (conv -> ... -> softmax -> argmax) over one batch of
 synthetic frames already resident in HBM.  Default workload = the configuration
 BASELINE.json's metric is quoted on: canonical VT-CNN2 (11 classes), batch 2^20, bf16 MFMA
-with f32 accumulation (configs[2]).  Other BASELINE configs that fit one GPU are run as
-short `extra` legs (not the headline value):  --workload selects any of them as headline.
+with f32 accumulation (configs[2]).  --workload selects any other workload as headline.
+
+A plain run sets up, warms up, times the K steps, and prints the line: metric, value, unit,
+higher_is_better, dtype, ms_per_step (one timed step) and the configuration.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last step computed --
+DIR/probs.npy (softmax probabilities) and DIR/labels.npy (argmax), both float32 -- for every
+frame, or for a fixed seeded sample of frames (DIR/sample_rows.npy, float64) when the whole
+output would exceed 64 MB.  Inputs and weights are seeded: two builds compare output for output.
+
+--full adds everything else, each with runs of its own after the headline: the roofline and
+per-kernel figures, the CPU baseline, and the other BASELINE configs that fit one GPU as short
+`extra` legs (not the headline value); --no-extras / --no-cpu-baseline / --no-live-traffic
+drop parts of it.
 
 N > 1: the headline line is the weak-scaling reading (2^20 frames PER GPU).  The metric's
 "batch=2^20 at 1/2/4/8 MI355X" also reads as a fixed 2^20-frame global batch, and configs[3]
-names 2^24 frames over 8 GPUs (2^21 per GPU): both are run by every rank as `extra` legs
-("scaling": "strong" / "weak", with global_batch and frames_per_gpu stated), same timing contract.
+names 2^24 frames over 8 GPUs (2^21 per GPU): with --full both are run by every rank as `extra`
+legs ("scaling": "strong" / "weak", with global_batch and frames_per_gpu stated), same timing contract.
 
-roofline: the dominant kernel's algorithmic FLOPs (MFMA-bound nets) or bytes (HBM-bound
+roofline (--full): the dominant kernel's algorithmic FLOPs (MFMA-bound nets) or bytes (HBM-bound
 nets) per launch / its mean launch duration, measured with HIP events recorded inside
 mdc_forward on the launch stream in a separate, untimed pass.  roofline.traffic (VT-CNN2
 workloads, N = 1, default run): HBM bytes per launch from two rocprofv3 --pmc child passes of
 this very workload, run first (live_traffic); otherwise the committed profile's figure.
-cpu_baseline: the numpy oracle ("port": a CPU restatement, NOT Keras -- Keras/TensorFlow
+cpu_baseline (--full): the numpy oracle ("port": a CPU restatement, NOT Keras -- Keras/TensorFlow
 are not installed) timed on this box's host cores on a bounded sample; rank 0, N=1 only.
 """
 import argparse
@@ -569,6 +580,33 @@ def run_host_path(device, steps=4, warmup=1):
             "unit": "frames/s", "rows": rows}
 
 
+DUMP_BUDGET_BYTES = 60_000_000      # under the 64 MB cap, with room for the .npy headers
+
+
+def dump_outputs(out_dir, probs, labels, seed=0):
+    """What the timed path's last step handed its caller: probs (n, C) f32 and labels (n,) int32, as float32 .npy files
+    (labels < 2^24: exact).  The whole batch when it fits DUMP_BUDGET_BYTES, otherwise the same fixed, seeded, sorted sample
+    of rows from both, whose indices go to sample_rows.npy (float64)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n, c = probs.shape
+    row_bytes = 4 * (c + 1)
+    files = {}
+    if n * row_bytes <= DUMP_BUDGET_BYTES:
+        files["probs"] = probs.float().cpu().numpy()
+        files["labels"] = labels.float().cpu().numpy()
+    else:
+        k = DUMP_BUDGET_BYTES // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+        idx = torch.from_numpy(rows).to(probs.device)
+        files["probs"] = probs.index_select(0, idx).float().cpu().numpy()
+        files["labels"] = labels.index_select(0, idx).float().cpu().numpy()
+        files["sample_rows"] = rows.astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(files)
+
+
 def metric_name(kind, filters, n):
     """BASELINE.json's metric string for the workloads it is quoted on (VT-CNN2 at batch 2^20); every other workload
     or batch size says what it is."""
@@ -679,13 +717,19 @@ def main(argv=None, script=None):
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=DEFAULT, choices=sorted(WORKLOADS))
-    ap.add_argument("--no-extras", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline and per-kernel figures, CPU baseline, extra legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (probs, labels) to DIR/<name>.npy as float32")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no extra legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not measure roofline.traffic with rocprofv3 child passes (use the committed profile's figure)")
+                    help="with --full: do not measure roofline.traffic with rocprofv3 child passes (use the committed profile's figure)")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     rank_environment(os.environ)      # every rank, launched by whomever, BEFORE torch is imported or the GPU touched
 
     launched = "WORLD_SIZE" in os.environ
@@ -698,7 +742,7 @@ def main(argv=None, script=None):
         print(f"[bench] --gpus {args.gpus} but the launcher set WORLD_SIZE={world}: refusing to run", file=sys.stderr)
         return 2
 
-    if world == 1 and not args.no_live_traffic and not args.no_extras:
+    if world == 1 and args.full and not args.no_live_traffic and not args.no_extras:
         # roofline.traffic of the headline's kernels, measured in this run -- child processes, BEFORE this one touches the GPU
         # (a process that has initialised the GPU must not start another program on this pool)
         live_traffic(args.workload)
@@ -730,15 +774,17 @@ def main(argv=None, script=None):
         "config": {"workload": name, "topology": kind, "classes": classes, "frames_per_gpu": n,
                    "global_batch": n * ngpu, "parallelism": f"batch-shard x{ngpu} (no collective)",
                    "outputs": "softmax probabilities f32 + argmax int32",
-                   "frames_per_forward_call": launch_chunk(kind, dtype, n) or "library default"},
+                   "frames_per_forward_call": launch_chunk(kind, dtype, n) or "library default", "full": args.full},
     }
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:      # before anything else launches: these are the last timed step's results
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, probs, labels)
+    if rank == 0 and args.full:
         rl, kernels = dominant_roofline(m, x, probs, labels, max(2, min(args.steps, 5)))
         out["roofline"] = rl
         out["kernels"] = kernels
     del m, x, probs, labels
     torch.cuda.empty_cache()
-    if dist and ngpu > 1:      # every rank runs these (barriers inside timed_region); rank 0 reports
+    if dist and ngpu > 1 and args.full:      # every rank runs these (barriers inside timed_region); rank 0 reports
         legs = []
         for label, scaling, wl, frames, global_batch in multi_gpu_legs(name, ngpu, rank):
             lsteps, lwarm = max(1, min(args.steps, 5)), min(args.warmup, 2)
@@ -753,7 +799,7 @@ def main(argv=None, script=None):
                 legs.append({"workload": wl, "reading": label, "error": str(e)})
         if rank == 0:
             out["extra"] = legs
-    if rank == 0 and ngpu == 1:
+    if rank == 0 and ngpu == 1 and args.full:
         if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(name)
         if not args.no_extras:

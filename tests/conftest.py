@@ -9,7 +9,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE = "/root/reference"          # exists only in the build container, never on the GPU box
+# the reference's own data files (Keras checkpoints, Q6.12 weight and frame tables), byte for byte, and the ROM rows
+# of its HDL source as parsed by formats.q612 (the HDL itself is not bundled): tests/golden/reference/README.md
+REFERENCE = os.path.join(GOLDEN, "reference")
 
 
 def pytest_configure(config):
@@ -45,10 +47,18 @@ def golden_dir():
 
 
 @pytest.fixture(scope="session")
-def reference_dir():
-    if not os.path.isdir(REFERENCE):
-        pytest.skip("reference tree not present (GPU box)")
-    return REFERENCE
+def reference_dir(tmp_path_factory):
+    """One directory with the reference's data files under their own names: the bundled files as they are, and the
+    Q6.12 text tables unpacked byte for byte from q612_tables.npz (one uint8 array per file)."""
+    import shutil
+    d = tmp_path_factory.mktemp("reference")
+    for name in os.listdir(REFERENCE):
+        if name != "q612_tables.npz":
+            shutil.copy(os.path.join(REFERENCE, name), d / name)
+    with np.load(os.path.join(REFERENCE, "q612_tables.npz")) as z:
+        for name in z.files:
+            (d / name).write_bytes(z[name].tobytes())
+    return str(d)
 
 
 def load_deployed_npz(name):

@@ -1,7 +1,6 @@
 """Format decoders: Keras .h5 (h5mini) and Q6.12 text tables (q612).  CPU only.
 
-The reference's data files are read from /root/reference when present (build container);
-on the GPU box these tests skip and the derived fixtures in tests/golden stand in."""
+The reference's data files are read from their bundled copies in tests/golden/reference (conftest.reference_dir)."""
 import json
 import os
 
@@ -186,10 +185,11 @@ def test_weight_writer_roundtrip(tmp_path):
 
 
 def test_sv_rom_equals_latest_weights(reference_dir):
-    """cnn_test_latest1.sv ROM rows == 12.15.latestWeights.txt bit for bit (SURVEY.md 2 #10)."""
-    sv = q612.parse_file(os.path.join(reference_dir, "cnn_test_latest1.sv"), strict=True)
+    """cnn_test_latest1.sv ROM rows == 12.15.latestWeights.txt bit for bit.  The .sv side is the
+    recorded q612.parse_file(strict=True) of that HDL file (tests/golden/reference/cnn_test_latest1_sv_rom.json)."""
+    sv = json.load(open(os.path.join(reference_dir, "cnn_test_latest1_sv_rom.json")))
     txt = q612.parse_file(os.path.join(reference_dir, "12.15.latestWeights.txt"), strict=True)
-    sv_dense = [t.rows for t in sv.tables if len(t) == 387]
+    sv_dense = [t["rows"] for t in sv["tables"] if len(t["rows"]) == 387]
     txt_dense = [t.rows for t in txt.tables if len(t) == 387]
     assert len(sv_dense) == 6 and sv_dense == txt_dense
 

@@ -9,7 +9,7 @@ Three independent readers judge a written file:
   * libhdf5 through ctypes (H5Fopen / H5Dopen2 / H5Dread), as the reference's h5py would call it;
   * libhdf5's own tools: h5diff against the bundled checkpoint (no differences; one changed bit is found), h5repack + h5diff
     round trips, h5stat's accounting.
-No reference file travels: the tests that read /root/reference skip where it is absent (the GPU box)."""
+The bundled checkpoints are read from their copies in tests/golden/reference (conftest.reference_dir)."""
 import ctypes as C
 import json
 import os

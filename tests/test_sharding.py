@@ -240,7 +240,7 @@ def _bench_worker(rank, world, port, out_dir):
     buf = io.StringIO()
     os.environ.pop("HSA_ENABLE_IPC_MODE_LEGACY", None)      # a rank started by SOMEONE ELSE's launcher, bare environment
     with contextlib.redirect_stdout(buf):
-        bench.main(["--gpus", str(world), "--steps", "4", "--warmup", "1", "--no-extras", "--no-cpu-baseline"])
+        bench.main(["--gpus", str(world), "--steps", "4", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"])
     assert os.environ["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"   # ... gets the dmabuf-IPC switch RCCL needs all the same
     with open(os.path.join(out_dir, f"out{rank}.txt"), "w") as f:
         f.write(buf.getvalue())
@@ -308,7 +308,7 @@ def test_bench_gpus_2_without_a_launcher_starts_its_own_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
                                                             "HSA_ENABLE_IPC_MODE_LEGACY")}
     env["MDC_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, str(wrapper), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-extras", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, str(wrapper), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

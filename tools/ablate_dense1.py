@@ -7,7 +7,7 @@ from modulationdetectioncnn_amd import build as _b
 _b.build(force=True, extra_flags=["-DMDC_ABLATIONS"])   # NOTE: rebuild without the flag afterwards
 for abl in (sys.argv[1:] or ["0", "1", "2", "3", "10", "11"]):
     env = dict(os.environ, MDC_ABLATE_D1=abl)
-    r = subprocess.run([sys.executable, "bench.py", "--no-extras", "--no-cpu-baseline", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--no-extras", "--no-cpu-baseline", "--steps", "3", "--warmup", "1"],
                        env=env, capture_output=True, text=True)
     try:
         j = json.loads(r.stdout.strip().splitlines()[-1])

@@ -6,7 +6,7 @@ from modulationdetectioncnn_amd import build as _b
 _b.build(force=True, extra_flags=["-DMDC_ABLATIONS"])
 for abl in (sys.argv[1:] or ["0", "1", "2", "3"]):
     env = dict(os.environ, MDC_ABLATE_DEP=abl)
-    r = subprocess.run([sys.executable, "bench.py", "--workload", "deployed3-f32-n2^20", "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, "bench.py", "--workload", "deployed3-f32-n2^20", "--full", "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True)
     try:
         j = json.loads(r.stdout.strip().splitlines()[-1])
         print("ABLATE_DEP", abl, "value %.3g frac %.3f" % (j["value"], j["roofline"]["frac"]), flush=True)

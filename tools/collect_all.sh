@@ -8,11 +8,12 @@ TAG=${1:-r05}
 if [ "$2" = "summarize" ]; then
     python3 tools/summarize_profiles.py $TAG > /dev/null
     python3 tools/summarize_dep_counters.py $TAG > /dev/null
-    cp gpurun_out/bench_${TAG}_final.json profiles/${TAG}_bench_line.json
+    cp profile_out/bench_${TAG}_final.json profiles/${TAG}_bench_line.json
     echo "profiles/${TAG}_* refreshed"
     exit 0
 fi
-bash tools/collect_profiles.sh $TAG > gpurun_out/collect_${TAG}.log 2>&1
-bash tools/collect_dep_counters.sh $TAG >> gpurun_out/collect_${TAG}.log 2>&1
-python3 bench.py > gpurun_out/bench_${TAG}_final.json 2> gpurun_out/bench_${TAG}_final.err
-tail -c 300 gpurun_out/bench_${TAG}_final.json
+mkdir -p profile_out
+bash tools/collect_profiles.sh $TAG > profile_out/collect_${TAG}.log 2>&1
+bash tools/collect_dep_counters.sh $TAG >> profile_out/collect_${TAG}.log 2>&1
+python3 bench.py --full > profile_out/bench_${TAG}_final.json 2> profile_out/bench_${TAG}_final.err
+tail -c 300 profile_out/bench_${TAG}_final.json

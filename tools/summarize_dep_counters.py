@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""gpurun_out/pmc_<round>_dep*_{A,B}/ (tools/collect_dep_counters.sh) -> profiles/<round>_dep_counters.json:
+"""profile_out/pmc_<round>_dep*_{A,B}/ (tools/collect_dep_counters.sh) -> profiles/<round>_dep_counters.json:
 per deployed-net kernel, the mean per-launch SQ / LDS counters and the derived fractions
   valu_busy   = SQ_ACTIVE_INST_VALU / SQ_BUSY_CYCLES-equivalent (quad-cycles: x4 / (SQ_WAVE_CYCLES / waves))  -- see below
   wave_parked = SQ_WAIT_ANY / SQ_WAVE_CYCLES          (waves sitting in s_waitcnt / barriers)
@@ -8,7 +8,7 @@ per deployed-net kernel, the mean per-launch SQ / LDS counters and the derived f
 SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles summed over waves (MI355X_MICROARCH.md, cycle constants)."""
 import collections, csv, glob, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.path.join(ROOT, "profile_out")
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r02"
 out = {}
 for d in sorted(glob.glob(os.path.join(G, f"pmc_{rnd}_dep*_[AB]"))):

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Turn rocprofv3 output under gpurun_out/ into the committed summaries under profiles/.
+"""Turn rocprofv3 output under profile_out/ into the committed summaries under profiles/.
 
-  kernel stats : gpurun_out/prof_<tag>/runc/*_kernel_stats.csv      -> profiles/<round>_<tag>_kernel_stats.csv
-  HBM traffic  : gpurun_out/pmc_fetch_*/, pmc_write_*/ (separate --pmc passes, as
+  kernel stats : profile_out/prof_<tag>/runc/*_kernel_stats.csv      -> profiles/<round>_<tag>_kernel_stats.csv
+  HBM traffic  : profile_out/pmc_fetch_*/, pmc_write_*/ (separate --pmc passes, as
                  MI355X_MICROARCH.md "HBM" prescribes) -> profiles/<round>_traffic.json
 Corrections applied (same guide): FETCH_SIZE/WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports
 exactly half of the bytes of a wide coalesced streaming read (16 B/lane), so the read side is
@@ -17,7 +17,7 @@ import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.path.join(ROOT, "profile_out")
 P = os.path.join(ROOT, "profiles")
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r01"
 
@@ -37,7 +37,7 @@ os.makedirs(P, exist_ok=True)
 for d in sorted(glob.glob(os.path.join(G, "prof_*"))):
     tag = os.path.basename(d)[5:]
     if tag[:1] == "r" and tag[1:3].isdigit() and not tag.startswith(rnd):
-        continue      # another round's scratch directory still lying in gpurun_out/
+        continue      # another round's scratch directory still lying in profile_out/
     for f in sorted(glob.glob(os.path.join(d, "*", "*_kernel_stats.csv")), key=os.path.getmtime)[-1:]:      # newest run only
         shutil.copy(f, os.path.join(P, (tag if tag.startswith(rnd) else f"{rnd}_{tag}") + "_kernel_stats.csv"))
 
