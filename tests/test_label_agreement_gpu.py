@@ -7,7 +7,9 @@ flipped a tenth of the labels could pass them.  Here every frame counts: on >= 2
 frames whose label equals the f32 kernels' label must stay above the floor DESIGN.md quotes for the mode.  The f32
 kernels themselves are the ones pinned to the f64 oracle (and, for T1, to Keras' recorded output); north_star's
 "argmax bit-exact" holds for f32 only, and these floors say how far the narrower modes are from it.
-Parity unpinned for T3 (no reference weights exist): synthetic seed-2016 weights, N(0, 5e-3) frames."""
+Parity unpinned for T3 (no reference weights exist): synthetic seed-2016 weights, N(0, 5e-3) frames here; the same floors
+hold on a net trained on 11-class signal frames, against the f32 kernels and the f64 oracle, with the statistical and the
+calibrated fp8 feature scale, and so does cnn.py's per-SNR accuracy (tests/test_trained_vtcnn2_gpu.py)."""
 import numpy as np
 import pytest
 import torch

@@ -7,7 +7,8 @@ import numpy as np
 
 from conftest import load_deployed_npz
 from oracle import oracle_np as O
-from signals import MODS, SNRS, modulated_frames
+from modulationdetectioncnn_amd.topology import CLASSES_11
+from signals import MODS, MODS11, SNRS, _rrc, modulated_frames, modulated_frames11
 
 
 def test_generator_is_deterministic_and_shaped_like_the_bundled_frames():
@@ -48,3 +49,70 @@ def test_bundled_nets_spread_these_frames_over_all_classes_with_decisive_margins
         assert np.median(srt[:, -1] - srt[:, -2]) > 0.05, name
     w = [a for p in load_deployed_npz("3convmodrecnets_CNN2_0.5") for a in p]
     assert len(np.unique(O.forward_deployed(noise, *w, dtype=np.float64)["labels"])) == 1      # why noise frames are not enough
+
+
+def test_eleven_class_generator_is_deterministic_complete_and_at_the_bundled_level():
+    a, la, sa = modulated_frames11(2200, seed=5)
+    b, lb, sb = modulated_frames11(2200, seed=5)
+    np.testing.assert_array_equal(a, b)
+    np.testing.assert_array_equal(la, lb)
+    np.testing.assert_array_equal(sa, sb)
+    assert a.shape == (2200, 2, 128) and a.dtype == np.float32 and la.dtype == np.int32 and sa.dtype == np.int32
+    # the DeepSig notebook's class order (`mods` sorted), which is also the package's 11-class name list
+    assert MODS11 == ("8PSK", "AM-DSB", "AM-SSB", "BPSK", "CPFSK", "GFSK", "PAM4", "QAM16", "QAM64", "QPSK", "WBFM")
+    assert list(MODS11) == sorted(MODS11) == CLASSES_11
+    assert set(np.unique(la)) == set(range(11)) and set(np.unique(sa)) == set(SNRS)
+    assert np.bincount(la, minlength=11).min() >= 140                     # uniform draw: 200 per class expected
+    c = a[:, 0].astype(np.float64) + 1j * a[:, 1]
+    rms = np.sqrt((np.abs(c) ** 2).mean(axis=1))
+    assert 0.9 * 7.8e-3 * 0.999 <= rms.min() and rms.max() <= 1.1 * 7.8e-3 * 1.001
+    assert np.isfinite(a).all() and np.abs(a).max() < 0.06
+    assert not np.array_equal(a, modulated_frames11(2200, seed=6)[0])
+    # the 3-class generator is untouched by the 11-class one (other tests pin its frames)
+    assert MODS == ("WBFM", "AM-SSB", "GFSK")
+
+
+def _symbol_rate(c):
+    """Matched (root-raised-cosine) filter, then the 12 symbol-spaced samples away from the frame's edges at each of the
+    8 timing phases: (8, n, 12).  The generator's timing offset is a whole sample, so one phase hits the symbol instants."""
+    h = _rrc()
+    mf = np.apply_along_axis(lambda r: np.convolve(r, h, mode="same"), 1, c)
+    return np.stack([mf[:, p + 16:112:8] for p in range(8)])
+
+
+def _line(sym, M):
+    """M-th-power spectral line: the largest |DFT| of (s / |s|)^M over frequency (the carrier offset moves it) and
+    timing phase, over the number of symbols: 1 for a pure tone, about 0.65 for 12 random phases."""
+    z = (sym / np.abs(sym)) ** M
+    return (np.abs(np.fft.fft(z, n=512, axis=2)).max(axis=2) / z.shape[2]).max(axis=0)
+
+
+def test_eleven_classes_have_their_signatures():
+    x, lab, _ = modulated_frames11(4400, seed=9, snrs=(18,))
+    c = x[:, 0].astype(np.float64) + 1j * x[:, 1]
+    cls = {m: lab == i for i, m in enumerate(MODS11)}
+    env = np.abs(c).std(axis=1) / np.abs(c).mean(axis=1)
+    for m in ("CPFSK", "GFSK", "WBFM"):                  # constant envelope (+ noise at 18 dB)
+        assert np.median(env[cls[m]]) < 0.15, m
+    for m in ("AM-DSB", "AM-SSB", "BPSK", "PAM4", "QAM16", "QAM64"):
+        assert np.median(env[cls[m]]) > 0.25, m
+    sym = _symbol_rate(c)
+    # M-PSK: (s/|s|)^M is a tone at M x the carrier offset; at M/2 it is not (8PSK^4 and QPSK^2 alternate in sign)
+    for m, M in (("BPSK", 2), ("QPSK", 4), ("8PSK", 8)):
+        assert np.median(_line(sym[:, cls[m]], M)) > 0.9, m
+        if M > 2:
+            assert np.median(_line(sym[:, cls[m]], M // 2)) < 0.8, m
+    # PAM4 (like BPSK and AM-DSB's real message on its carrier) is real before the rotation: a line at M = 2
+    assert np.median(_line(sym[:, cls["PAM4"]], 2)) > 0.9
+    assert np.median(_line(sym[:, cls["QAM16"]], 2)) < 0.8 and np.median(_line(sym[:, cls["QPSK"]], 2)) < 0.8
+    # QAM: several amplitude rings at the symbol instants; PSK: one (spread = coefficient of variation of |s| at the
+    # best timing phase)
+    mag = np.abs(sym)
+    spread = (mag.std(axis=2) / mag.mean(axis=2)).min(axis=0)
+    for m in ("BPSK", "QPSK", "8PSK"):
+        assert np.median(spread[cls[m]]) < 0.08, m
+    for m in ("QAM16", "QAM64"):
+        assert np.median(spread[cls[m]]) > 0.2, m
+    # AM-SSB: one-sided spectrum (as the 3-class test)
+    spec = np.abs(np.fft.fft(c[cls["AM-SSB"]], axis=1)) ** 2
+    assert np.median(spec[:, 3:64].sum(axis=1) / spec[:, 65:126].sum(axis=1)) > 5.0

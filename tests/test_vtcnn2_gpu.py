@@ -1,6 +1,8 @@
 """Parity of the canonical VT-CNN2 HIP path (conv1+conv2 MFMA kernel, dense1 GEMM, softmax head)
 against the CPU oracle, through the C ABI.  No reference outputs exist for this topology (no
-weights are bundled): parity is against this repo's f64 oracle ("parity unpinned").
+weights are bundled): parity is against this repo's f64 oracle ("parity unpinned").  The weights here are the untrained
+synthetic draws; the same bars, a per-frame bar and the label floors are held on a TRAINED net (matched conv2 filters,
+decisive and thin margins) in tests/test_trained_vtcnn2_gpu.py (profiles/r06_measured_bars.json).
 
 Tolerances (relative to the largest |logit| of the batch, since the net is positively
 homogeneous in its input scale):

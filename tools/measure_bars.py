@@ -2,7 +2,9 @@
 """ON THE GPU BOX: what the reduced-precision test bars are measured against.  Prints, per mode, the largest error
 (relative to the largest |logit|, the unit of tests/test_vtcnn2_gpu.py's TOL) over the scenarios of the GPU tests, and the
 label agreement with the f32 kernels on N(0, sigma) noise frames and on the signal-shaped frames of tests/signals.py.
-The bars in the tests are about twice these maxima; re-run after touching a kernel's arithmetic."""
+The bars in the tests are about twice these maxima; re-run after touching a kernel's arithmetic.
+--trained: only the trained-net scenario of tests/test_trained_vtcnn2_gpu.py (tests/trained_vtcnn2.py trains the net on the
+GPU first) -> profiles/r06_measured_bars.json."""
 import json, os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,8 +23,67 @@ def model(classes, dtype, seed=2016, bias_scale=0.0, absmax=None):
     m.set_weights(w); return m, w
 
 xsig, _, _ = modulated_frames(1 << 16, seed=2016)
-def progress(msg):      # (gpurun takes seven silent minutes for a hang: say where we are, on stderr)
+def progress(msg):      # (a hang is silent for minutes: say where we are, on stderr)
     print("[measure_bars]", msg, file=sys.stderr, flush=True)
+
+
+def pcts(v):
+    return [float(np.percentile(v, 50)), float(np.percentile(v, 99)), float(np.max(v))]
+
+
+def trained_scenario():
+    """The trained VT-CNN2 (tests/trained_vtcnn2.py) on its 4,096 held-out frames against the f64 oracle, and the label
+    floors / per-SNR accuracy on 2^16 further frames against the f32 kernels."""
+    import trained_vtcnn2 as T
+    from signals import modulated_frames11
+    progress("training")
+    w, st = T.trained()
+    x, lab, snr, ref = T.held_out()
+    rl = ref["logits"]; scale = float(np.abs(rl).max()); own = np.abs(rl).max(axis=1)
+    srt = np.sort(rl, axis=1); margin = (srt[:, -1] - srt[:, -2]) / own
+    res = {"training": st, "held-out frames": len(x), "oracle: per-frame top-2 margin / own max|logit| p1 / p50": [float(np.percentile(margin, 1)), float(np.percentile(margin, 50))],
+           "oracle: own max|logit| / batch max|logit| p1 / p50": [float(np.percentile(own / scale, 1)), float(np.percentile(own / scale, 50))]}
+    bound = T.fp8_feature_bound(w); kf = int(np.floor(np.log2(224.0 / bound))); clip = 448.0 * 2.0 ** -kf
+    res["fp8 occupancy"] = {"statistical bound": bound, "kf": kf, "clip level": clip, "largest feature": float(ref["flat"].max()),
+                            "largest feature / bound": float(ref["flat"].max()) / bound,
+                            "oracle features beyond the clip level": int((ref["flat"] > clip).sum())}
+    xf, labf, snrf = modulated_frames11(1 << 16, seed=T.HELD_OUT_SEED + 1)
+    xf = torch.from_numpy(xf).cuda()
+    models = {}
+    for mode in ("f32", "bf16", "fp8", "fp8+bf16feat"):
+        progress("trained " + mode)
+        m = VTCNN2(Topology.vtcnn2(11), dtype="fp8" if mode.startswith("fp8") else mode, fp8_bf16_features=mode == "fp8+bf16feat")
+        m.set_weights(w); models[mode] = m
+        lg = m.predict(x, tap="dense"); err = np.abs(lg - rl).max(axis=1)
+        r = {"per-frame logit err / own max|logit| p50 / p99 / max": pcts(err / own),
+             "logit err / batch max|logit| p50 / p99 / max": pcts(err / scale),
+             "probs err / batch max|logit| max": float(np.abs(m.predict(x) - ref["probs"]).max() / scale),
+             "small batches (1, 17, 257): logit err / their max|logit|": [float(np.abs(m.predict(x[:n], tap="dense") - rl[:n]).max() / np.abs(rl[:n]).max()) for n in (1, 17, 257)],
+             "label agreement with the oracle (4,096)": float((m.predict_classes(x) == ref["labels"]).mean())}
+        flat = m.predict(x, tap="flat")
+        r["taps: flat / max (256 frames)"] = float(np.abs(flat[:256] - ref["flat"][:256]).max() / ref["flat"][:256].max())
+        r["taps: hidden / max (256 frames)"] = float(np.abs(m.predict(x[:256], tap="hidden") - ref["dense1"][:256]).max() / np.abs(ref["dense1"][:256]).max())
+        r["flat tap: largest value / oracle's largest"] = float(flat.max()) / float(ref["flat"].max())
+        if mode == "fp8":
+            res["fp8 occupancy"]["fp8 flat values at the clip level"] = int((flat >= clip).sum())
+        res[mode] = r
+    lf = models["f32"].predict_classes(xf)
+    acc_f = models["f32"].accuracy_by_snr(xf, labf, snrf)[0]
+    res["f32"]["accuracy by SNR (2^16 frames)"] = acc_f
+    mc = VTCNN2(Topology.vtcnn2(11), dtype="fp8"); mc.set_weights(w)
+    res["fp8"]["calibrated feature absmax"] = mc.calibrate_fp8_features(modulated_frames11(256, seed=T.HELD_OUT_SEED + 2)[0])
+    models["fp8 calibrated"] = mc; res["fp8 calibrated"] = {}
+    for mode in ("bf16", "fp8", "fp8+bf16feat", "fp8 calibrated"):
+        m = models[mode]
+        res[mode]["label agreement with the f32 kernels (2^16)"] = float((m.predict_classes(xf) == lf).float().mean())
+        acc = m.accuracy_by_snr(xf, labf, snrf)[0]
+        res[mode]["accuracy by SNR: largest |difference| from the f32 kernels'"] = max(abs(acc[s] - acc_f[s]) for s in acc)
+    return res
+
+
+if "--trained" in sys.argv:
+    print(json.dumps(trained_scenario(), indent=1))
+    sys.exit(0)
 
 for dtype in ("bf16", "fp8", "fp8+bf16feat"):
     progress("vtcnn2 " + dtype)
