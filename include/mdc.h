@@ -47,7 +47,8 @@ extern "C" {
                                4: MDC_KIND_VTCNN2 at MDC_FP8 keeps E4M3 features (its workspace per frame shrinks from
                                   22,144 to 11,584 bytes: ask mdc_workspace_bytes); MDC_OPT_FP8_BF16_FEATURES restores
                                   ABI 3's numerics and workspace
-                               5: the training step (mdc_trainer_*, mdc_train_batch): additive */
+                               5: the training step (mdc_trainer_*, mdc_train_batch): additive; later, also additive:
+                                  mdc_forward_checked / mdc_predict_host_checked, MDC_NONFINITE_* (non-finite frames) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -78,8 +79,9 @@ enum {
  * MDC_KIND_DEPLOYED does the same with its conv taps and bias at MDC_F32 and MDC_BF16 (the ReLU rides in the second
  * fma's / the conversion's clamp bit; dense weights carry the 2^+32): bit-identity to Keras' operation order holds for
  * conv activations in [2^-94, 2^32) -- at 2^32 and beyond they saturate at 2^32 instead of growing on, below 2^-94 the
- * scaled value is an f32 denormal (bits lost, then zero), and an Inf activation yields finite probabilities where Keras
- * gives NaN (tests/test_deployed_gpu.py pins both ends).  The MDC_TAP_CONV / MDC_TAP_FLAT taps of the deployed nets come
+ * scaled value is an f32 denormal (bits lost, then zero).  A frame holding a NaN or +-Inf sample gets no NaN row from
+ * mdc_forward (tests/test_deployed_gpu.py pins that it stays within its frame): mdc_forward_checked flags such frames and,
+ * asked to, gives them Keras' NaN row.  The MDC_TAP_CONV / MDC_TAP_FLAT taps of the deployed nets come
  * from a kernel that reads the UNSCALED table and rectifies with fmaxf: outside that range a tap and the probabilities of
  * the same frame can disagree.
  * MDC_F16: MDC_KIND_DEPLOYED only -- as MDC_BF16 there, with IEEE f16 operands and the conv itself in packed f16
@@ -167,6 +169,44 @@ MDC_API int mdc_forward(const mdc_model* m, const void* x_dev, int64_t n,
                 float* tap_dev, int tap,
                 void* workspace_dev, size_t workspace_bytes,
                 void* hip_stream);
+
+/* ---- non-finite input frames (cnn.py:153, 198) -----------------------------------------------------------------------
+ * What Keras does with a frame holding a NaN or +-Inf sample: a NaN sample always gives an all-NaN softmax row (NaN x w is
+ * NaN, np.maximum and TF's ReLU pass it on, and Dense mixes every position into every unit); np.argmax of that row is 0 and
+ * model.evaluate's mean loss is nan.  A +-Inf sample almost always gives one too (Inf x 0 taps, Inf - Inf in the Dense sums,
+ * the softmax's x - max), but a -Inf conv output that the ReLU turns into 0 can leave Keras' row finite.  mdc_forward
+ * returns finite rows for all such frames (the 2^-32 scaling and the ReLU in the clamp bit above).
+ *
+ * mdc_forward_checked is mdc_forward for f32 frames plus a check of every sample of every frame:
+ *   nonfinite_dev (n) uint8, REQUIRED: 1 if frame i holds a NaN or +-Inf sample, else 0 (finite extremes -- +-FLT_MAX,
+ *                 denormals, -0.0 -- are finite);
+ *   nonfinite_count_dev int64, may be NULL: += the number of such frames (caller-zeroed; accumulates across calls);
+ *   policy MDC_NONFINITE_REPORT: probs and labels are bit-identical to mdc_forward for EVERY frame, bad ones included;
+ *          MDC_NONFINITE_PROPAGATE: each flagged frame gets an all-NaN probability row and label 0 (np.argmax of that row);
+ *          every other frame is bit-identical to mdc_forward.  PROPAGATE treats every non-finite sample alike, so on the
+ *          rare +-Inf frame whose Keras row stays finite (see above) it gives NaN where Keras does not.
+ * Every kind and every dtype mdc_finalize accepts, MDC_OPT_FP8_BF16_FEATURES included; no layer taps.  Validation as
+ * mdc_forward; an unknown policy or a NULL nonfinite_dev (n > 0) is MDC_EINVAL.  mdc_workspace_bytes is unchanged (the
+ * flags live in the caller's buffer).  The call only enqueues on hip_stream and can be captured in a hipGraph like
+ * mdc_forward.  MDC_KIND_DEPLOYED: the forward kernels check the samples they already hold and write flags, count and NaN
+ * rows themselves (one launch, as mdc_forward); MDC_KIND_VTCNN2 / MDC_KIND_CNNPY: the forward, then one more launch that
+ * reads the frames, writes the flags and, under PROPAGATE, the NaN rows.  In libmdc_alt.so the checked entries always run
+ * the product kernels (no alternate is selected for them).  Raw uint8 input cannot be non-finite: mdc_forward_iq_u8
+ * and mdc_predict_host_iq_u8 have no checked twin. */
+enum { MDC_NONFINITE_REPORT = 0, MDC_NONFINITE_PROPAGATE = 1 };
+
+MDC_API int mdc_forward_checked(const mdc_model* m, const void* x_dev, int64_t n,
+                float* probs_dev, int32_t* labels_dev,
+                void* workspace_dev, size_t workspace_bytes,
+                uint8_t* nonfinite_dev, int64_t* nonfinite_count_dev,
+                int policy, void* hip_stream);
+
+/* mdc_predict_host with the same check: nonfinite_host (n) uint8 is REQUIRED; *nonfinite_count (host, may be NULL) is SET
+ * to the number of flagged frames, not accumulated.  Results are bit-identical to mdc_forward_checked on the same frames,
+ * whatever the chunk. */
+MDC_API int mdc_predict_host_checked(mdc_model* m, const float* x_host, int64_t n,
+                float* probs_host, int32_t* labels_host, uint8_t* nonfinite_host,
+                int64_t* nonfinite_count, int policy, int64_t chunk_frames);
 
 /* ---- callers either side of the forward -------------------------------------------
 

@@ -29,11 +29,13 @@ EXPORTS = [
     "mdc_trainer_create", "mdc_trainer_num_layers", "mdc_trainer_layer_sizes", "mdc_trainer_set_adam", "mdc_trainer_set_dropout", "mdc_trainer_set_tensor",
     "mdc_trainer_get_tensor", "mdc_trainer_set_iterations", "mdc_train_batch", "mdc_trainer_evaluate", "mdc_trainer_read",
     "mdc_trainer_destroy",
+    "mdc_forward_checked", "mdc_predict_host_checked",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
 MDC_OPT_FP8_BF16_FEATURES = 1      # include/mdc.h: option bit in mdc_topology.reserved[0]
 HOP_FRAME = 128
+NONFINITE_REPORT, NONFINITE_PROPAGATE = 0, 1     # include/mdc.h: policies of mdc_forward_checked / mdc_predict_host_checked
 
 
 class MdcTopology(C.Structure):
@@ -98,6 +100,13 @@ def lib(variant: str = "product") -> C.CDLL:
     L.mdc_predict_host.argtypes = [vp, vp, i64, vp, vp, i64]
     L.mdc_predict_host_iq_u8.argtypes = [vp, vp, i64, i64, C.c_float, vp, vp, i64]
     L.mdc_crossentropy.argtypes = [vp, vp, i64, i32, vp, vp, vp]
+    # (getattr with a default: tools/ab_libs.py loads builds from before these entries; tests/test_nonfinite_abi.py holds
+    # both libraries of this tree to exporting them)
+    for name, args in (("mdc_forward_checked", [vp, vp, i64, vp, vp, vp, sz, vp, vp, i32, vp]),
+                       ("mdc_predict_host_checked", [vp, vp, i64, vp, vp, vp, vp, i32, i64])):
+        fn = getattr(L, name, None)
+        if fn is not None:
+            fn.argtypes, fn.restype = args, i32
     fp = C.POINTER(C.c_float)
     L.mdc_trainer_create.argtypes = [C.POINTER(MdcTopology), i32, C.POINTER(vp)]
     L.mdc_trainer_num_layers.argtypes = [vp]

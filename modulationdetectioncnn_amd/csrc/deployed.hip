@@ -196,11 +196,20 @@ __device__ __forceinline__ float rows_sum(float m) {       // sum over the four 
 // wave drains with vmcnt(0) before it ends (a copy must not land in LDS that already belongs to another work-group).
 // Round 2 tried this ring with the builtin and saw no gain: hipcc put a vmcnt(0) in front of every LDS read (HISTORY.md
 // 4.1b, "the LDS-DMA rings were not rings").
-template <int F, int TAP, int ABL = 0, bool TAIL = false, bool U8 = false, int RING = 0>   // TAP: 0 none, 2 dense (model2); ABL: timing-only ablations
+// CHECK = true (mdc_forward_checked; f32 frames, no ring, no taps; its NfArgs ride where the hop goes): each group's four frames are in registers anyway, one
+// integer max per sample (nf_absbits_max4) and a wave ballot per frame set bit j of a wave-uniform 64-bit mask of the block; after the
+// block the 64 lanes store the flag bytes (one vector store each), nf_poison != 0 gives the flagged frames the NaN row and
+// label 0 in the same epilogue, and each work-group adds its count with one 64-bit vector atomic at the end.
+template <int F, int TAP, int ABL = 0, bool TAIL = false, bool U8 = false, int RING = 0, bool CHECK = false>   // TAP: 0 none, 2 dense (model2); ABL: timing-only ablations
 __global__ __launch_bounds__(256) void deployed_fwd_kernel(const float* __restrict__ x, long n,
                                                            const float* __restrict__ wp,
                                                            float* __restrict__ probs, int* __restrict__ labels,
-                                                           float* __restrict__ tap_dense, float scale = 0.f, long hop2 = 256) {
+                                                           float* __restrict__ tap_dense, float scale = 0.f, HopOrNf<CHECK> hop_nf = 256) {
+    const long hop2 = hop_of(hop_nf);
+    const NfArgs nf = nf_of(hop_nf);      // CHECK only (in place of the hop, see NfArgs)
+    unsigned char* const nf_flags = nf.flags;
+    unsigned long long* const nf_count = nf.count;
+    const int nf_poison = nf.poison;
     const int lane = threadIdx.x & 63;
     const int lp = lane & 31;
     using f32x2 = __attribute__((ext_vector_type(2))) float;
@@ -240,6 +249,8 @@ __global__ __launch_bounds__(256) void deployed_fwd_kernel(const float* __restri
     const long nblk = TAIL ? 1 : (n >> 6);
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     static_assert(RING == 0 || (!TAIL && !U8 && RING >= 2), "the ring form serves full blocks of f32 frames");
+    static_assert(!CHECK || (RING == 0 && !U8 && TAP == 0 && ABL == 0), "the check serves the f32 product form");
+    unsigned nf_wave = 0;      // CHECK: flagged frames this wave has seen
     extern __shared__ __attribute__((aligned(16))) unsigned char ring_mem[];
     unsigned char* const ring = ring_mem + (RING ? wv * (RING * 4096) : 0);
     const long blk0 = (long)blockIdx.x * 4 + wv;
@@ -273,6 +284,7 @@ __global__ __launch_bounds__(256) void deployed_fwd_kernel(const float* __restri
     bool first_block = true;      // direct-load form: only a wave's first block loads its first group synchronously
     for (long blk = blk0; blk < nblk; blk += nwaves) {
         const long base = blk << 6;
+        unsigned long long nf_blk = 0;      // CHECK: bit j = frame base + j holds a NaN / +-Inf sample (wave-uniform)
         float r[kC] = {0.f, 0.f, 0.f};
         // x[0][0] / x[1][0] of every frame go through a 512-byte LDS table (written by lanes 0 and 32 as the
         // frames stream by, read once per block by the lane that finishes the frame): no extra HBM/L2 reads
@@ -333,6 +345,11 @@ __global__ __launch_bounds__(256) void deployed_fwd_kernel(const float* __restri
                 __builtin_amdgcn_sched_barrier(0);     // keep the prefetch at the top of the group
 #pragma unroll
                 for (int f = 0; f < 4; ++f) cur[f] = decode(cur_raw[f]);
+            }
+            if constexpr (CHECK) {
+                // (frames past the end of a ragged block were loaded as zeros: never flagged)
+#pragma unroll
+                for (int f = 0; f < 4; ++f) nf_blk |= (__ballot(nf_absbits_max4(cur[f]) >= kNfInfBits) != 0ull ? 1ull : 0ull) << (4 * G + f);
             }
             float v[4][kC];
 #pragma unroll
@@ -455,7 +472,20 @@ __global__ __launch_bounds__(256) void deployed_fwd_kernel(const float* __restri
             }
         }
         const long o = base + myframe;
-        if (!TAIL || o < n) {
+        if constexpr (CHECK) {
+            if (!TAIL || base + lane < n) nf_flags[base + lane] = (unsigned char)((nf_blk >> lane) & 1ull);
+            nf_wave += (unsigned)__builtin_popcountll(nf_blk);
+        }
+        if (CHECK && nf_poison && ((nf_blk >> myframe) & 1ull)) {
+            if (!TAIL || o < n) {      // Keras' row for a non-finite frame: all NaN, np.argmax 0
+                if (probs) {
+                    probs[o * 3 + 0] = __builtin_nanf("");
+                    probs[o * 3 + 1] = __builtin_nanf("");
+                    probs[o * 3 + 2] = __builtin_nanf("");
+                }
+                if (labels) labels[o] = 0;
+            }
+        } else if (!TAIL || o < n) {
             const float z0 = fmaxf(r[0] + bd[0], 0.f);   // Dense(3, activation='relu')
             const float z1 = fmaxf(r[1] + bd[1], 0.f);
             const float z2 = fmaxf(r[2] + bd[2], 0.f);
@@ -478,6 +508,16 @@ __global__ __launch_bounds__(256) void deployed_fwd_kernel(const float* __restri
         }
     }
     if constexpr (RING > 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // the clamped tail copies have landed
+    if constexpr (CHECK) {
+        __shared__ unsigned nf_lds[4];
+        if (lane == 0) nf_lds[wv] = nf_wave;
+        __syncthreads();
+        if (threadIdx.x == 0 && nf_count) {
+            unsigned total = 0;
+            for (int w = 0; w < (int)(blockDim.x >> 6); ++w) total += nf_lds[w];
+            if (total) atomicAdd(nf_count, (unsigned long long)total);
+        }
+    }
 }
 
 }  // namespace
@@ -624,6 +664,35 @@ int deployed_forward(const mdc_model* m, const float* x, int64_t n, float* probs
             if (F == 3) hipLaunchKernelGGL((deployed_fwd_kernel<3, 0, 0, true>), dim3(1), dim3(64), 0, s, xt, nt, wp, pt, lt, td);
             else        hipLaunchKernelGGL((deployed_fwd_kernel<10, 0, 0, true>), dim3(1), dim3(64), 0, s, xt, nt, wp, pt, lt, td);
         }
+    }
+    MDC_HIP(hipGetLastError());
+    return MDC_OK;
+}
+
+// mdc_forward_checked, f32: the product kernels' CHECK instantiations (same grid, same arithmetic: every probability and
+// label of an unflagged frame is bit-identical to deployed_forward's)
+int deployed_forward_checked(const mdc_model* m, const float* x, int64_t n, float* probs, int32_t* labels, uint8_t* flags, int64_t* count,
+                             bool poison, hipStream_t s) {
+    if (m->dtype != MDC_F32) return deployed_bf16_forward_checked(m, x, n, probs, labels, flags, count, poison, s);
+    const float* wp = static_cast<const float*>(m->d_pack[5]);
+    const int F = m->topo.filters;
+    auto* c = reinterpret_cast<unsigned long long*>(count);
+    const int pz = poison ? 1 : 0;
+    ProfScope ps(m, 0, s);
+    const long nfull = (n / 64) * 64;
+    if (nfull > 0) {
+        long grid = (nfull / 64 + 3) / 4;
+        if (grid > 2048) grid = 2048;
+        if (F == 3) hipLaunchKernelGGL((deployed_fwd_kernel<3, 0, 0, false, false, 0, true>), dim3(grid), dim3(256), 0, s, x, nfull, wp, probs, labels, nullptr, 0.f, NfArgs{flags, c, pz});
+        else        hipLaunchKernelGGL((deployed_fwd_kernel<10, 0, 0, false, false, 0, true>), dim3(grid), dim3(256), 0, s, x, nfull, wp, probs, labels, nullptr, 0.f, NfArgs{flags, c, pz});
+    }
+    if (nfull < n) {
+        const long nt = n - nfull;
+        const float* xt = x + nfull * kFrameFloats;
+        float* pt = probs ? probs + nfull * 3 : nullptr;
+        int* lt = labels ? labels + nfull : nullptr;
+        if (F == 3) hipLaunchKernelGGL((deployed_fwd_kernel<3, 0, 0, true, false, 0, true>), dim3(1), dim3(64), 0, s, xt, nt, wp, pt, lt, nullptr, 0.f, NfArgs{flags + nfull, c, pz});
+        else        hipLaunchKernelGGL((deployed_fwd_kernel<10, 0, 0, true, false, 0, true>), dim3(1), dim3(64), 0, s, xt, nt, wp, pt, lt, nullptr, 0.f, NfArgs{flags + nfull, c, pz});
     }
     MDC_HIP(hipGetLastError());
     return MDC_OK;

@@ -110,10 +110,19 @@ __device__ __forceinline__ float clamp01(float v) { return __builtin_amdgcn_fmed
 // (three in flight while one is computed), and a lane reads the 8 bytes that hold its four samples of both rows and
 // converts the row at hand with the arithmetic of mdc_iq_u8_to_frames -- the f32 samples, and so every result, are
 // bit-identical to convert-then-forward.
-template <int F, int MODE, bool U8>      // MODE: 0 bf16, 1 f16, 2 fp8 (e4m3)
+// CHECK = true (mdc_forward_checked; f32 frames; its NfArgs ride where the hop goes): lane (f, g) tests the quarter of frame f it reads out of its LDS staging
+// anyway (an integer max over the samples' sign-less words: one register, nf_absbits_max4), a ballot combines the four lanes of each frame in the
+// epilogue; lane (f, 0) stores the flag byte and, with nf_poison != 0, writes the NaN row and label 0 instead of the
+// softmax; each work-group adds its count with one 64-bit vector atomic at the end.
+template <int F, int MODE, bool U8, bool CHECK = false>      // MODE: 0 bf16, 1 f16, 2 fp8 (e4m3)
 __global__ __launch_bounds__(512, 1) void deployed_bf16_kernel(const float* __restrict__ x, long n,
                                                                 const float* __restrict__ wp, const uint4* __restrict__ atab,
-                                                                float* __restrict__ probs, int* __restrict__ labels, float scale, long hop2) {
+                                                                float* __restrict__ probs, int* __restrict__ labels, float scale, HopOrNf<CHECK> hop_nf) {
+    const long hop2 = hop_of(hop_nf);
+    const NfArgs nf = nf_of(hop_nf);      // CHECK only (in place of the hop, see NfArgs)
+    unsigned char* const nf_flags = nf.flags;
+    unsigned long long* const nf_count = nf.count;
+    const int nf_poison = nf.poison;
     using G = Bf16Geom<F>;
     constexpr bool HALF = MODE == 1, FP8 = MODE == 2;
     constexpr int kPhaseUnits = G::kUnits / 2;
@@ -178,8 +187,11 @@ __global__ __launch_bounds__(512, 1) void deployed_bf16_kernel(const float* __re
     } else {
         if (grp < ngroups) stage_row(grp, 0);
     }
+    static_assert(!CHECK || !U8, "the check serves f32 frames");
+    unsigned nf_wave = 0;      // CHECK: flagged frames this wave has seen
     for (int it = 0; grp < ngroups; grp += gstep, ++it) {
         const long frame = grp * 16 + f;
+        unsigned nf_bits = 0;      // CHECK: largest sign-less sample word of this lane's quarter of frame f (nf_absbits_max4)
         f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
         float x0[2] = {0.f, 0.f};      // first sample of each row (x[0], for the g = 0 lane's position w = 0)
         const unsigned char* raw = rawmine + (it & 3) * kRawGroup;
@@ -241,6 +253,7 @@ __global__ __launch_bounds__(512, 1) void deployed_bf16_kernel(const float* __re
                         nbv[q] = ((float)(d2 & 0xFFu) - 127.5f) * scale;
                     } else {
                         c4[q] = c4n[q]; nbv[q] = nbn[q];
+                        if constexpr (CHECK) nf_bits = max(nf_bits, nf_absbits_max4(c4[q]));
                     }
                 }
 #pragma unroll
@@ -379,8 +392,27 @@ __global__ __launch_bounds__(512, 1) void deployed_bf16_kernel(const float* __re
                 }
             }
         }
+        bool nf_mine = false;
+        if constexpr (CHECK) {
+            // lanes f, f + 16, f + 32, f + 48 hold the four quarters of frame f; frames past the end (staged as copies of
+            // the last one) are never flagged
+            const unsigned long long b = __ballot(nf_bits >= kNfInfBits && frame < n);
+            const unsigned m16 = (unsigned)((b | (b >> 16) | (b >> 32) | (b >> 48)) & 0xFFFFull);
+            nf_mine = ((m16 >> f) & 1u) != 0;
+            if (g == 0 && frame < n) nf_flags[frame] = nf_mine ? 1 : 0;
+            nf_wave += (unsigned)__builtin_popcount(m16);
+        }
         // D rows 0..2 (the classes) of column f live in lanes 0..15 (kg = 0), registers 0..2
-        if (g == 0 && frame < n) {
+        if (CHECK && nf_poison && nf_mine) {
+            if (g == 0) {      // Keras' row for a non-finite frame: all NaN, np.argmax 0
+                if (probs) {
+                    probs[frame * 3 + 0] = __builtin_nanf("");
+                    probs[frame * 3 + 1] = __builtin_nanf("");
+                    probs[frame * 3 + 2] = __builtin_nanf("");
+                }
+                if (labels) labels[frame] = 0;
+            }
+        } else if (g == 0 && frame < n) {
             // Dense(3, activation='relu'); fp8: the sums carry 2^(sa+sw), removed exactly before the bias
             const float z0 = fmaxf(FP8 ? fmaf(acc[0][0] + acc[1][0], unscale, bd[0]) : acc[0][0] + acc[1][0] + bd[0], 0.f);
             const float z1 = fmaxf(FP8 ? fmaf(acc[0][1] + acc[1][1], unscale, bd[1]) : acc[0][1] + acc[1][1] + bd[1], 0.f);
@@ -396,6 +428,16 @@ __global__ __launch_bounds__(512, 1) void deployed_bf16_kernel(const float* __re
             }
             // int(np.argmax(test_Y_hat[i,:])) (cnn.py:209): FIRST maximum of the probabilities as returned
             if (labels) labels[frame] = (p0 >= p1 && p0 >= p2) ? 0 : ((p1 >= p2) ? 1 : 2);
+        }
+    }
+    if constexpr (CHECK) {
+        __shared__ unsigned nf_lds[G::kWaves];
+        if (lane == 0) nf_lds[wv] = nf_wave;
+        __syncthreads();
+        if (threadIdx.x == 0 && nf_count) {
+            unsigned total = 0;
+            for (int w = 0; w < G::kWaves; ++w) total += nf_lds[w];
+            if (total) atomicAdd(nf_count, (unsigned long long)total);
         }
     }
 }
@@ -520,8 +562,9 @@ int deployed_bf16_pack(mdc_model* m) {
     return upload(m, 2, tab.data(), tab.size() * sizeof(unsigned short));
 }
 
-template <int F, bool U8>
-static int launch_bf16(const mdc_model* m, const void* x, int64_t n, float scale, float* probs, int32_t* labels, hipStream_t s, long hop2 = 256) {
+template <int F, bool U8, bool CHECK = false>
+static int launch_bf16(const mdc_model* m, const void* x, int64_t n, float scale, float* probs, int32_t* labels, hipStream_t s, long hop2 = 256,
+                       uint8_t* nf_flags = nullptr, int64_t* nf_count = nullptr, int nf_poison = 0) {
     using G = Bf16Geom<F>;
     const float* wp = static_cast<const float*>(m->d_pack[(m->dtype == MDC_FP8 || m->dtype == MDC_BF16) ? 4 : 0]);      // scaled heads (slot 4)
     const uint4* atab = static_cast<const uint4*>(m->d_pack[2]);
@@ -530,8 +573,12 @@ static int launch_bf16(const mdc_model* m, const void* x, int64_t n, float scale
     long grid = (ngroups + G::kWaves - 1) / G::kWaves;
     if (grid > 256) grid = 256;      // one work-group per CU (LDS: A table + 8 x 2 row buffers)
 #define MDC_LAUNCH_DEP16(MODE) do { \
-        MDC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(deployed_bf16_kernel<F, MODE, U8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::kLds)); \
-        hipLaunchKernelGGL((deployed_bf16_kernel<F, MODE, U8>), dim3((unsigned)grid), dim3(64 * G::kWaves), G::kLds, s, xf, (long)n, wp, atab, probs, labels, scale, hop2); } while (0)
+        MDC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(deployed_bf16_kernel<F, MODE, U8, CHECK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::kLds)); \
+        if constexpr (CHECK) \
+            hipLaunchKernelGGL((deployed_bf16_kernel<F, MODE, U8, true>), dim3((unsigned)grid), dim3(64 * G::kWaves), G::kLds, s, xf, (long)n, wp, atab, probs, labels, scale, \
+                               NfArgs{nf_flags, reinterpret_cast<unsigned long long*>(nf_count), nf_poison}); \
+        else \
+            hipLaunchKernelGGL((deployed_bf16_kernel<F, MODE, U8>), dim3((unsigned)grid), dim3(64 * G::kWaves), G::kLds, s, xf, (long)n, wp, atab, probs, labels, scale, hop2); } while (0)
     if (m->dtype == MDC_F16) MDC_LAUNCH_DEP16(1);
     else if (m->dtype == MDC_FP8) MDC_LAUNCH_DEP16(2);
     else MDC_LAUNCH_DEP16(0);
@@ -546,6 +593,13 @@ int deployed_bf16_forward(const mdc_model* m, const float* x, int64_t n, float* 
 }
 
 // raw uint8 I/Q (256 B per frame) straight into the 16-bit kernels
+int deployed_bf16_forward_checked(const mdc_model* m, const float* x, int64_t n, float* probs, int32_t* labels, uint8_t* flags, int64_t* count,
+                                  bool poison, hipStream_t s) {
+    ProfScope ps(m, 0, s);
+    return m->topo.filters == 3 ? launch_bf16<3, false, true>(m, x, n, 0.f, probs, labels, s, 256, flags, count, poison ? 1 : 0)
+                                : launch_bf16<10, false, true>(m, x, n, 0.f, probs, labels, s, 256, flags, count, poison ? 1 : 0);
+}
+
 int deployed_bf16_forward_iq_u8(const mdc_model* m, const uint8_t* iq, int64_t n, int64_t hop, float scale, float* probs, int32_t* labels, hipStream_t s) {
     ProfScope ps(m, 0, s);
     const long hop2 = 2 * (long)hop;

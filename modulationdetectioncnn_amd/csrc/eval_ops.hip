@@ -96,7 +96,73 @@ __global__ __launch_bounds__(256) void iq_u8_kernel(const unsigned char* __restr
     }
 }
 
+// Non-finite input frames (cnn.py:153, 198: a NaN / +-Inf sample gives Keras an all-NaN softmax row).  One wave per frame:
+// 64 lanes x one float4 = the frame's 1 KiB, one v_cmp_class_f32 per sample (NaN and both infinities), a wave ballot is the
+// frame's flag; lane 0 writes the flag byte, and the work-group adds its frame count to *count with ONE 64-bit atomic
+// (vector memory only).  Two frames per wave per step keep two loads in flight.  POISON (MDC_NONFINITE_PROPAGATE): lanes
+// 0..C-1 also overwrite a flagged frame's probability row with NaN and lane 0 its label with 0 (np.argmax of a NaN row);
+// it runs after the forward on the same stream, so it simply overwrites what the forward wrote.
+constexpr int kNonFiniteClass = 0x207;      // signalling NaN | quiet NaN | -Inf | +Inf
+constexpr int kNfWaves = 4;
+
+__device__ __forceinline__ bool nonfinite4(const float4 v) {
+    return __builtin_amdgcn_classf(v.x, kNonFiniteClass) | __builtin_amdgcn_classf(v.y, kNonFiniteClass) |
+           __builtin_amdgcn_classf(v.z, kNonFiniteClass) | __builtin_amdgcn_classf(v.w, kNonFiniteClass);
+}
+
+template <bool POISON>
+__device__ __forceinline__ unsigned nonfinite_frame(long f, bool bad, int lane, unsigned char* __restrict__ flags, float* __restrict__ probs,
+                                                    int* __restrict__ labels, int C) {
+    const bool any = __ballot(bad) != 0ull;
+    if (lane == 0) flags[f] = any ? 1 : 0;
+    if (POISON && any) {
+        if (probs && lane < C) probs[f * C + lane] = __builtin_nanf("");
+        if (labels && lane == 0) labels[f] = 0;
+    }
+    return any ? 1u : 0u;
+}
+
+template <bool POISON>
+__global__ __launch_bounds__(64 * kNfWaves) void nonfinite_kernel(const float4* __restrict__ x, long n, unsigned char* __restrict__ flags,
+                                                                 unsigned long long* __restrict__ count, float* __restrict__ probs,
+                                                                 int* __restrict__ labels, int C) {
+    __shared__ unsigned wave_bad[kNfWaves];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (scalar loop control)
+    const long step = (long)gridDim.x * kNfWaves;
+    unsigned nbad = 0;
+    // f is uniform over the wave: every ballot below sees all 64 lanes of one frame, frames past n are never read or written
+    for (long f0 = (long)blockIdx.x * kNfWaves + wave; f0 < n; f0 += 2 * step) {
+        const long f1 = f0 + step;
+        const float4 v0 = x[f0 * 64 + lane];
+        const float4 v1 = f1 < n ? x[f1 * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+        nbad += nonfinite_frame<POISON>(f0, nonfinite4(v0), lane, flags, probs, labels, C);
+        if (f1 < n) nbad += nonfinite_frame<POISON>(f1, nonfinite4(v1), lane, flags, probs, labels, C);
+    }
+    if (lane == 0) wave_bad[wave] = nbad;
+    __syncthreads();
+    if (threadIdx.x == 0 && count) {
+        unsigned total = 0;
+        for (int w = 0; w < kNfWaves; ++w) total += wave_bad[w];
+        if (total) atomicAdd(count, (unsigned long long)total);
+    }
+}
+
 }  // namespace
+
+int nonfinite_launch(const float* x, int64_t n, uint8_t* flags, int64_t* count, float* probs, int32_t* labels, int classes, bool poison,
+                     hipStream_t s) {
+    if (n == 0) return MDC_OK;
+    long grid = (n + 2 * kNfWaves - 1) / (2 * kNfWaves);
+    if (grid > 16384) grid = 16384;
+    auto* c = reinterpret_cast<unsigned long long*>(count);
+    const float4* x4 = reinterpret_cast<const float4*>(x);
+    if (poison)
+        hipLaunchKernelGGL(nonfinite_kernel<true>, dim3((unsigned)grid), dim3(64 * kNfWaves), 0, s, x4, (long)n, flags, c, probs, labels, classes);
+    else
+        hipLaunchKernelGGL(nonfinite_kernel<false>, dim3((unsigned)grid), dim3(64 * kNfWaves), 0, s, x4, (long)n, flags, c, nullptr, nullptr, classes);
+    MDC_HIP(hipGetLastError());
+    return MDC_OK;
+}
 
 int confusion_launch(const int32_t* truth, const int32_t* pred, const int32_t* bin, int64_t n, int classes, int bins, int64_t* counts,
                      int64_t* bad, hipStream_t s) {

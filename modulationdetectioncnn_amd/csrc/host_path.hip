@@ -104,7 +104,8 @@ struct Slot {
     char* d_in = nullptr;
     float* d_probs = nullptr;
     int32_t* d_labels = nullptr;
-    char* pin_out = nullptr;      // probabilities, then labels
+    uint8_t* d_flags = nullptr;   // mdc_predict_host_checked: the frames' non-finite flags
+    char* pin_out = nullptr;      // probabilities, then labels, then flags
     hipEvent_t in_done = nullptr, comp_done = nullptr, out_done = nullptr;
     int64_t start = 0, count = 0;
     bool busy = false;
@@ -130,6 +131,7 @@ void host_ctx_free(mdc_model* m) {
         if (s.d_in) (void)hipFree(s.d_in);
         if (s.d_probs) (void)hipFree(s.d_probs);
         if (s.d_labels) (void)hipFree(s.d_labels);
+        if (s.d_flags) (void)hipFree(s.d_flags);
         if (s.in_done) (void)hipEventDestroy(s.in_done);
         if (s.comp_done) (void)hipEventDestroy(s.comp_done);
         if (s.out_done) (void)hipEventDestroy(s.out_done);
@@ -185,12 +187,14 @@ int ctx_prepare(mdc_model* m, size_t in_bytes, int64_t frames) {
             if (s.pin_out) { (void)hipHostFree(s.pin_out); s.pin_out = nullptr; }
             if (s.d_probs) { (void)hipFree(s.d_probs); s.d_probs = nullptr; }
             if (s.d_labels) { (void)hipFree(s.d_labels); s.d_labels = nullptr; }
+            if (s.d_flags) { (void)hipFree(s.d_flags); s.d_flags = nullptr; }
         }
         c->out_cap = 0;
         for (Slot& s : c->slot) {
-            if (hipHostMalloc(reinterpret_cast<void**>(&s.pin_out), (size_t)frames * (C + 1) * 4, hipHostMallocDefault) != hipSuccess ||
+            if (hipHostMalloc(reinterpret_cast<void**>(&s.pin_out), (size_t)frames * ((C + 1) * 4 + 1), hipHostMallocDefault) != hipSuccess ||
                 hipMalloc(reinterpret_cast<void**>(&s.d_probs), (size_t)frames * C * 4) != hipSuccess ||
-                hipMalloc(reinterpret_cast<void**>(&s.d_labels), (size_t)frames * 4) != hipSuccess) {
+                hipMalloc(reinterpret_cast<void**>(&s.d_labels), (size_t)frames * 4) != hipSuccess ||
+                hipMalloc(reinterpret_cast<void**>(&s.d_flags), (size_t)frames) != hipSuccess) {
                 (void)hipGetLastError();
                 set_error("host path: cannot allocate result staging for %lld frames per slot", (long long)frames);
                 return MDC_ENOMEM;
@@ -224,7 +228,7 @@ bool is_pinned(const void* p) { return host_kind(p) == 1; }
 // in_range(start, count) -> (byte offset, byte count) of the input those windows read; launch(d_in, count, slot, ctx)
 template <class InRange, class Launch>
 int run_pipeline(mdc_model* m, const char* src, int64_t n, int64_t chunk, bool ramp, float* probs_host, int32_t* labels_host,
-                 InRange in_range, Launch launch) {
+                 uint8_t* flags_host, InRange in_range, Launch launch) {
     HostCtx* c = static_cast<HostCtx*>(m->host_ctx);
     const int C = m->topo.classes;
     const bool direct = is_pinned(src);
@@ -238,6 +242,7 @@ int run_pipeline(mdc_model* m, const char* src, int64_t n, int64_t chunk, bool r
         MDC_HIP(hipEventSynchronize(s.out_done));
         if (probs_host) std::memcpy(probs_host + s.start * C, s.pin_out, (size_t)s.count * C * 4);
         if (labels_host) std::memcpy(labels_host + s.start, s.pin_out + (size_t)c->out_cap * C * 4, (size_t)s.count * 4);
+        if (flags_host) std::memcpy(flags_host + s.start, s.pin_out + (size_t)c->out_cap * (C + 1) * 4, (size_t)s.count);
         s.busy = false;
         return MDC_OK;
     };
@@ -276,6 +281,7 @@ int run_pipeline(mdc_model* m, const char* src, int64_t n, int64_t chunk, bool r
         if (e == hipSuccess) e = hipStreamWaitEvent(c->out_s, s.comp_done, 0);
         if (e == hipSuccess && probs_host) e = hipMemcpyAsync(s.pin_out, s.d_probs, (size_t)count * C * 4, hipMemcpyDeviceToHost, c->out_s);
         if (e == hipSuccess && labels_host) e = hipMemcpyAsync(s.pin_out + (size_t)c->out_cap * C * 4, s.d_labels, (size_t)count * 4, hipMemcpyDeviceToHost, c->out_s);
+        if (e == hipSuccess && flags_host) e = hipMemcpyAsync(s.pin_out + (size_t)c->out_cap * (C + 1) * 4, s.d_flags, (size_t)count, hipMemcpyDeviceToHost, c->out_s);
         if (e == hipSuccess) e = hipEventRecord(s.out_done, c->out_s);
         if (e != hipSuccess) { set_error("host path: result copy failed: %s", hipGetErrorString(e)); rc = MDC_EIO; break; }
         s.start = start;
@@ -327,7 +333,7 @@ int predict_host(mdc_model* m, const float* x_host, int64_t n, float* probs_host
     const int64_t chunk = std::min<int64_t>(chunk_frames > 0 ? chunk_frames : default_chunk(n), n);
     if ((rc = ctx_prepare(m, (size_t)chunk * kFrameFloats * 4, chunk)) != MDC_OK) return rc;
     return run_pipeline(
-        m, reinterpret_cast<const char*>(x_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host,
+        m, reinterpret_cast<const char*>(x_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr,
         [](int64_t start, int64_t count, size_t* off, size_t* bytes) {
             *off = (size_t)start * kFrameFloats * 4;
             *bytes = (size_t)count * kFrameFloats * 4;
@@ -335,6 +341,38 @@ int predict_host(mdc_model* m, const float* x_host, int64_t n, float* probs_host
         [m](Slot& s, int64_t count, HostCtx* c) {
             return mdc_forward(m, s.d_in, count, s.d_probs, s.d_labels, nullptr, MDC_TAP_NONE, c->ws, c->ws_bytes, c->comp_s);
         });
+}
+
+// mdc_predict_host with mdc_forward_checked in the compute slot and one more result copy (the flags); the count is summed on
+// the host from the flags, so a chunked call returns exactly what one device call would have counted
+int predict_host_checked(mdc_model* m, const float* x_host, int64_t n, float* probs_host, int32_t* labels_host, uint8_t* nonfinite_host,
+                         int64_t* nonfinite_count, int policy, int64_t chunk_frames) {
+    if (policy != MDC_NONFINITE_REPORT && policy != MDC_NONFINITE_PROPAGATE) { set_error("mdc_predict_host_checked: unknown policy %d", policy); return MDC_EINVAL; }
+    if (n > 0 && !nonfinite_host) { set_error("mdc_predict_host_checked: null nonfinite_host (the per-frame flags are required)"); return MDC_EINVAL; }
+    int rc = check_common("mdc_predict_host_checked", m, x_host, n, chunk_frames);
+    if (rc != MDC_OK) return rc;
+    if (nonfinite_count) *nonfinite_count = 0;
+    if (n == 0) return MDC_OK;
+    std::lock_guard<std::mutex> g(m->host_mu);
+    DeviceScope dev(m->device);
+    if (!dev.ok) { set_error("mdc_predict_host_checked: cannot select device %d", m->device); return MDC_EIO; }
+    const int64_t chunk = std::min<int64_t>(chunk_frames > 0 ? chunk_frames : default_chunk(n), n);
+    if ((rc = ctx_prepare(m, (size_t)chunk * kFrameFloats * 4, chunk)) != MDC_OK) return rc;
+    rc = run_pipeline(
+        m, reinterpret_cast<const char*>(x_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nonfinite_host,
+        [](int64_t start, int64_t count, size_t* off, size_t* bytes) {
+            *off = (size_t)start * kFrameFloats * 4;
+            *bytes = (size_t)count * kFrameFloats * 4;
+        },
+        [m, policy](Slot& s, int64_t count, HostCtx* c) {
+            return mdc_forward_checked(m, s.d_in, count, s.d_probs, s.d_labels, c->ws, c->ws_bytes, s.d_flags, nullptr, policy, c->comp_s);
+        });
+    if (rc == MDC_OK && nonfinite_count) {
+        int64_t k = 0;
+        for (int64_t i = 0; i < n; ++i) k += nonfinite_host[i] != 0;
+        *nonfinite_count = k;
+    }
+    return rc;
 }
 
 int predict_host_iq_u8(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t hop, float scale, float* probs_host,
@@ -355,7 +393,7 @@ int predict_host_iq_u8(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t 
     const size_t in_bytes = (size_t)(2 * hop) * (size_t)(chunk - 1) + 256;
     if ((rc = ctx_prepare(m, in_bytes, chunk)) != MDC_OK) return rc;
     return run_pipeline(
-        m, reinterpret_cast<const char*>(iq_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host,
+        m, reinterpret_cast<const char*>(iq_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr,
         [hop](int64_t start, int64_t count, size_t* off, size_t* bytes) {
             *off = (size_t)(2 * hop) * (size_t)start;
             *bytes = (size_t)(2 * hop) * (size_t)(count - 1) + 256;

@@ -236,6 +236,38 @@ int mdc_forward(const mdc_model* m, const void* x_dev, int64_t n, float* probs_d
     });
 }
 
+int mdc_forward_checked(const mdc_model* m, const void* x_dev, int64_t n, float* probs_dev, int32_t* labels_dev, void* workspace_dev,
+                        size_t workspace_bytes, uint8_t* nonfinite_dev, int64_t* nonfinite_count_dev, int policy, void* hip_stream) {
+    return guarded("mdc_forward_checked", [&]() -> int {
+        // the arguments first, so that each mistake has its own message even without a device or a model
+        if (policy != MDC_NONFINITE_REPORT && policy != MDC_NONFINITE_PROPAGATE) { set_error("mdc_forward_checked: unknown policy %d", policy); return MDC_EINVAL; }
+        if (n < 0) { set_error("mdc_forward_checked: negative frame count"); return MDC_EINVAL; }
+        if (n > 0 && !nonfinite_dev) { set_error("mdc_forward_checked: null nonfinite_dev (the per-frame flags are required)"); return MDC_EINVAL; }
+        if (n > 0 && !x_dev) { set_error("mdc_forward_checked: null input"); return MDC_EINVAL; }
+        if ((reinterpret_cast<uintptr_t>(x_dev) & 15) != 0) { set_error("mdc_forward_checked: input must be 16-byte aligned"); return MDC_EINVAL; }
+        if (!m) { set_error("mdc_forward_checked: null model"); return MDC_EINVAL; }
+        if (!m->finalized) { set_error("mdc_forward_checked: model not finalized"); return MDC_ESTATE; }
+        if (n == 0) return MDC_OK;
+        const bool poison = policy == MDC_NONFINITE_PROPAGATE;
+        if (m->topo.kind == MDC_KIND_DEPLOYED) {
+            // the deployed nets are HBM-bound at 1 KiB per frame: their forward kernels check the samples they already hold
+            // (CHECK instantiations) and write flags, count and NaN rows themselves -- one launch, one read of the input
+            DeviceScope dev(m->device);
+            if (!dev.ok) { set_error("mdc_forward_checked: cannot select device %d", m->device); return MDC_EIO; }
+            return deployed_forward_checked(m, static_cast<const float*>(x_dev), n, probs_dev, labels_dev, nonfinite_dev, nonfinite_count_dev,
+                                            poison, static_cast<hipStream_t>(hip_stream));
+        }
+        int rc = mdc_forward(m, x_dev, n, probs_dev, labels_dev, nullptr, MDC_TAP_NONE, workspace_dev, workspace_bytes, hip_stream);
+        if (rc != MDC_OK) return rc;
+        DeviceScope dev(m->device);
+        if (!dev.ok) { set_error("mdc_forward_checked: cannot select device %d", m->device); return MDC_EIO; }
+        // VT-CNN2 and cnn.py's net: after the forward on the same stream, one pass over the frames writes the flags and, under
+        // PROPAGATE, overwrites the rows the forward just wrote
+        return nonfinite_launch(static_cast<const float*>(x_dev), n, nonfinite_dev, nonfinite_count_dev, probs_dev, labels_dev, m->topo.classes,
+                                poison, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
 int mdc_forward_iq_u8(const mdc_model* m, const uint8_t* iq_dev, int64_t n, int64_t hop, float scale,
                       float* probs_dev, int32_t* labels_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
     return guarded("mdc_forward_iq_u8", [&]() -> int {
@@ -402,6 +434,12 @@ int mdc_profile_reset(mdc_model* m) {
 
 int mdc_predict_host(mdc_model* m, const float* x_host, int64_t n, float* probs_host, int32_t* labels_host, int64_t chunk_frames) {
     return guarded("mdc_predict_host", [&]() -> int { return predict_host(m, x_host, n, probs_host, labels_host, chunk_frames); });
+}
+
+int mdc_predict_host_checked(mdc_model* m, const float* x_host, int64_t n, float* probs_host, int32_t* labels_host, uint8_t* nonfinite_host,
+                             int64_t* nonfinite_count, int policy, int64_t chunk_frames) {
+    return guarded("mdc_predict_host_checked", [&]() -> int {
+        return predict_host_checked(m, x_host, n, probs_host, labels_host, nonfinite_host, nonfinite_count, policy, chunk_frames); });
 }
 
 int mdc_predict_host_iq_u8(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t hop, float scale, float* probs_host,

@@ -8,6 +8,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "mdc.h"
@@ -84,6 +85,27 @@ __device__ __forceinline__ uint2 load8_unaligned(const unsigned char* p) {
     uint2 r;
     __builtin_memcpy(&r, p, 8);
     return r;
+}
+
+// mdc_forward_checked inside the deployed forward kernels: what their CHECK = true instantiations take in place of the raw-byte
+// hop (a parameter those f32 instantiations do not use), so that the kernels' parameter lists -- and with them the kernarg
+// layout and the machine code of every CHECK = false instantiation -- stay exactly as they were
+struct NfArgs {
+    unsigned char* flags;            // (n) 1 = the frame holds a NaN / +-Inf sample
+    unsigned long long* count;       // += number of such frames (may be NULL)
+    int poison;                      // MDC_NONFINITE_PROPAGATE: NaN row and label 0 for flagged frames
+};
+template <bool CHECK> using HopOrNf = typename std::conditional<CHECK, NfArgs, long>::type;
+__device__ __forceinline__ long hop_of(long h) { return h; }
+__device__ __forceinline__ long hop_of(const NfArgs&) { return 256; }
+__device__ __forceinline__ NfArgs nf_of(long) { return NfArgs{nullptr, nullptr, 0}; }
+__device__ __forceinline__ NfArgs nf_of(const NfArgs& a) { return a; }
+// a sample is NaN or +-Inf iff its bits without the sign are >= those of +Inf: the largest of four such words (one v_and
+// per sample, one v_max3 per two) is one register of state however many samples are folded into it
+constexpr unsigned kNfInfBits = 0x7F800000u;
+__device__ __forceinline__ unsigned nf_absbits_max4(const float4 v) {
+    return max(max(__float_as_uint(v.x) & 0x7FFFFFFFu, __float_as_uint(v.y) & 0x7FFFFFFFu),
+               max(__float_as_uint(v.z) & 0x7FFFFFFFu, __float_as_uint(v.w) & 0x7FFFFFFFu));
 }
 
 // alternates (test build only, see mdc_model::alt)
@@ -172,6 +194,8 @@ struct DeviceScope {
 
 // ---- host-buffer driver: host_path.hip ----------------------------------------------------
 int predict_host(mdc_model* m, const float* x_host, int64_t n, float* probs_host, int32_t* labels_host, int64_t chunk_frames);
+int predict_host_checked(mdc_model* m, const float* x_host, int64_t n, float* probs_host, int32_t* labels_host, uint8_t* nonfinite_host,
+                         int64_t* nonfinite_count, int policy, int64_t chunk_frames);
 int predict_host_iq_u8(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t hop, float scale, float* probs_host, int32_t* labels_host,
                        int64_t chunk_frames);
 void host_ctx_free(mdc_model* m);
@@ -197,9 +221,18 @@ int confusion_launch(const int32_t* truth, const int32_t* pred, const int32_t* b
                      int64_t* bad, hipStream_t s);
 int crossentropy_launch(const float* probs, const int32_t* truth, int64_t n, int classes, double* loss_sum, int64_t* bad, hipStream_t s);
 int iq_u8_launch(const uint8_t* iq, int64_t n, int64_t hop, float scale, float* x, hipStream_t s);
+// flags[i] = 1 iff frame i of x holds a NaN / +-Inf sample (else 0), *count += their number (count may be NULL); poison: the
+// flagged frames' probability rows become NaN and their labels 0 (probs / labels may be NULL).  mdc_forward_checked.
+int nonfinite_launch(const float* x, int64_t n, uint8_t* flags, int64_t* count, float* probs, int32_t* labels, int classes, bool poison,
+                     hipStream_t s);
 int deployed_forward(const mdc_model* m, const float* x, int64_t n, float* probs, int32_t* labels,
                      float* tap, int tap_kind, hipStream_t s);
 int deployed_forward_iq_u8(const mdc_model* m, const uint8_t* iq, int64_t n, int64_t hop, float scale, float* probs, int32_t* labels, hipStream_t s);
+// mdc_forward_checked of the deployed nets: the forward kernels' CHECK instantiations (flags, count, NaN rows in-kernel)
+int deployed_forward_checked(const mdc_model* m, const float* x, int64_t n, float* probs, int32_t* labels, uint8_t* flags, int64_t* count,
+                             bool poison, hipStream_t s);
+int deployed_bf16_forward_checked(const mdc_model* m, const float* x, int64_t n, float* probs, int32_t* labels, uint8_t* flags, int64_t* count,
+                                  bool poison, hipStream_t s);
 
 // ---- cnn.py literal model (T4): cnnpy.hip ----------------------------------------------
 int cnnpy_pack(mdc_model* m);

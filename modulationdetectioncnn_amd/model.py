@@ -41,6 +41,30 @@ _TAP = {None: _cabi.TAP_NONE, "conv": _cabi.TAP_CONV, "flat": _cabi.TAP_FLAT, "d
 
 Weights = List[Tuple[np.ndarray, np.ndarray]]
 
+# nonfinite= of the inference calls: None = mdc_forward / mdc_predict_host as they are; otherwise the checked entry points
+# (include/mdc.h, "non-finite input frames") with this policy
+_NONFINITE = {"propagate": _cabi.NONFINITE_PROPAGATE, "raise": _cabi.NONFINITE_REPORT}
+
+
+class NonFiniteInputError(ValueError):
+    """nonfinite="raise": some input frames hold a NaN or +-Inf sample.  .frames: their indices (sorted), .count: how many."""
+
+    def __init__(self, frames: Sequence[int]):
+        self.frames = [int(i) for i in frames]
+        self.count = len(self.frames)
+        shown = ", ".join(str(i) for i in self.frames[:8]) + (", ..." if self.count > 8 else "")
+        super().__init__(f"{self.count} input frame(s) hold a NaN or +-Inf sample: {shown}")
+
+
+def _nonfinite_policy(nonfinite: Optional[str], tap: Optional[str] = None) -> Optional[int]:
+    if nonfinite is None:
+        return None
+    if nonfinite not in _NONFINITE:
+        raise ValueError(f"nonfinite must be None, 'propagate' or 'raise'; got {nonfinite!r}")
+    if tap is not None:
+        raise ValueError("nonfinite= and tap= cannot be combined: the checked forward has no layer taps")
+    return _NONFINITE[nonfinite]
+
 
 def _torch():
     import torch
@@ -420,9 +444,17 @@ class VTCNN2:
         return {"conv": (1, 3, t.filters), "flat": (3 * t.filters,), "dense": (t.classes,), "hidden": (t.hidden,)}[tap]
 
     def forward_device(self, x, probs=None, labels=None, tap: Optional[str] = None, tap_out=None,
-                       batch_size: Optional[int] = None):
+                       batch_size: Optional[int] = None, nonfinite: Optional[str] = None, nonfinite_out=None):
         """Enqueue the forward on torch's current stream.  x: contiguous float32 CUDA tensor (n,2,128).
-        Pre-allocated outputs may be passed; returns (probs, labels, tap_out)."""
+        Pre-allocated outputs may be passed; returns (probs, labels, tap_out).
+        nonfinite="propagate" | "raise" (mdc_forward_checked, no taps; tap_out stays None): the (n,) uint8 per-frame flags
+        (1 = the frame holds a NaN or +-Inf sample) go to nonfinite_out, a caller's tensor, if given.  "propagate": flagged frames
+        get an all-NaN row and label 0, as Keras' predict + np.argmax give them.  "raise": the results are mdc_forward's,
+        and if any frame is flagged the call synchronises and raises NonFiniteInputError (the count is read back always,
+        the flags only then)."""
+        policy = _nonfinite_policy(nonfinite, tap)
+        if nonfinite_out is not None and policy is None:
+            raise ValueError("nonfinite_out needs nonfinite='propagate' or 'raise'")
         torch = _torch()
         if not (isinstance(x, torch.Tensor) and x.is_cuda):
             raise TypeError("forward_device needs a torch tensor on the ROCm device")
@@ -443,6 +475,12 @@ class VTCNN2:
             labels = torch.empty((n,), dtype=torch.int32, device=dev)
         if tap is not None and tap_out is None:
             tap_out = torch.empty((n,) + self.tap_shape(tap), dtype=torch.float32, device=dev)
+        if policy is not None:
+            if nonfinite_out is None:
+                nonfinite_out = torch.empty((n,), dtype=torch.uint8, device=dev)
+            elif not (isinstance(nonfinite_out, torch.Tensor) and nonfinite_out.dtype == torch.uint8 and tuple(nonfinite_out.shape) == (n,)
+                      and nonfinite_out.is_contiguous() and nonfinite_out.device == dev):
+                raise ValueError(f"nonfinite_out must be a contiguous uint8 tensor of shape ({n},) on {dev}")
         if n == 0:
             return probs, labels, tap_out
         chunk = int(batch_size) if batch_size else self.default_chunk
@@ -450,6 +488,17 @@ class VTCNN2:
         stream = torch.cuda.current_stream(dev).cuda_stream      # (2 us: looked up once per call)
         ws, ws_bytes = self._workspace(chunk, stream)
         tap_row = int(np.prod(self.tap_shape(tap))) if tap is not None else 0
+        if policy is not None:
+            count = torch.zeros((1,), dtype=torch.int64, device=dev) if nonfinite == "raise" else None
+            for s in range(0, n, chunk):
+                m = min(chunk, n - s)
+                self._check(L.mdc_forward_checked(
+                    h, x.data_ptr() + s * 1024, m, probs.data_ptr() + s * Cn * 4, labels.data_ptr() + s * 4,
+                    ws.data_ptr() if ws is not None else None, ws_bytes, nonfinite_out.data_ptr() + s,
+                    count.data_ptr() if count is not None else None, policy, stream))
+            if count is not None and int(count.item()):
+                raise NonFiniteInputError(torch.nonzero(nonfinite_out).flatten().tolist())
+            return probs, labels, None
         for s in range(0, n, chunk):
             m = min(chunk, n - s)
             self._check(L.mdc_forward(
@@ -465,10 +514,12 @@ class VTCNN2:
         return max(int(batch_size), HOST_MIN_CHUNK) if batch_size else 0
 
     def predict_host(self, X: np.ndarray, batch_size: Optional[int] = None, want_probs: bool = True,
-                     want_labels: bool = True, out=None) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+                     want_labels: bool = True, out=None, nonfinite: Optional[str] = None) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
         """numpy frames in, numpy (probs, labels) out through the library's own host-buffer driver (mdc_predict_host:
         pinned ring, copy / compute / result streams overlapped).  Bit-identical to the device path.  out = (probs,
-        labels): write into the caller's C-contiguous float32 (n,C) / int32 (n,) arrays (slices of a larger batch's)."""
+        labels): write into the caller's C-contiguous float32 (n,C) / int32 (n,) arrays (slices of a larger batch's).
+        nonfinite="propagate" | "raise": mdc_predict_host_checked, as forward_device describes."""
+        policy = _nonfinite_policy(nonfinite)
         a = np.ascontiguousarray(np.asarray(X), dtype=np.float32)
         if a.ndim != 3 or a.shape[1:] != (2, 128):
             raise ValueError(f"expected input of shape (n,2,128); got {a.shape}")
@@ -482,12 +533,22 @@ class VTCNN2:
         else:
             probs = np.empty((n, Cn), np.float32) if want_probs else None
             labels = np.empty((n,), np.int32) if want_labels else None
+        if policy is not None:
+            flags = np.empty((n,), np.uint8)
+            count = C.c_int64(0)
+            self._check(self._lib().mdc_predict_host_checked(self._engine(), a.ctypes.data, n,
+                                                             probs.ctypes.data if probs is not None else None,
+                                                             labels.ctypes.data if labels is not None else None, flags.ctypes.data,
+                                                             C.byref(count), policy, self._host_chunk(batch_size)))
+            if nonfinite == "raise" and count.value:
+                raise NonFiniteInputError(np.flatnonzero(flags).tolist())
+            return probs, labels
         self._check(self._lib().mdc_predict_host(self._engine(), a.ctypes.data, n,
                                                  probs.ctypes.data if probs is not None else None,
                                                  labels.ctypes.data if labels is not None else None, self._host_chunk(batch_size)))
         return probs, labels
 
-    def _run(self, X, batch_size, tap):
+    def _run(self, X, batch_size, tap, nonfinite=None):
         torch = _torch()
         as_numpy = not isinstance(X, torch.Tensor)
         if as_numpy:
@@ -500,24 +561,29 @@ class VTCNN2:
             if not x.is_cuda:
                 x = x.to(f"cuda:{self.device_index}")
             x = x.to(torch.float32).contiguous()
-        probs, labels, tap_out = self.forward_device(x, tap=tap, batch_size=batch_size)
+        probs, labels, tap_out = self.forward_device(x, tap=tap, batch_size=batch_size, nonfinite=nonfinite)
         return as_numpy, probs, labels, tap_out
 
-    def predict(self, X, batch_size: Optional[int] = None, tap: Optional[str] = None, verbose: int = 0):
+    def predict(self, X, batch_size: Optional[int] = None, tap: Optional[str] = None, verbose: int = 0, nonfinite: Optional[str] = None):
         """``model.predict(X, batch_size)``: (n,C) float32 softmax rows (``verbose`` is accepted and says nothing); with ``tap`` the named
         intermediate layer of CNN.ipynb cell 17 instead.  Results do not depend on batch_size.  numpy in -> numpy out
-        (through the streaming host-buffer driver); torch-ROCm tensor in -> tensor out on torch's current stream."""
+        (through the streaming host-buffer driver); torch-ROCm tensor in -> tensor out on torch's current stream.
+        nonfinite="propagate": frames holding a NaN / +-Inf sample get Keras' all-NaN row; "raise": NonFiniteInputError
+        names them (see forward_device)."""
+        _nonfinite_policy(nonfinite, tap)
         if tap is None and not isinstance(X, _torch().Tensor):
-            return self.predict_host(X, batch_size, want_labels=False)[0]
-        as_numpy, probs, _labels, tap_out = self._run(X, batch_size, tap)
+            return self.predict_host(X, batch_size, want_labels=False, nonfinite=nonfinite)[0]
+        as_numpy, probs, _labels, tap_out = self._run(X, batch_size, tap, nonfinite)
         out = tap_out if tap is not None else probs
         return out.cpu().numpy() if as_numpy else out
 
-    def predict_classes(self, X, batch_size: Optional[int] = None):
-        """Row-wise ``np.argmax`` of predict(X) (cnn.py:209: first maximum wins), int32 (n,)."""
+    def predict_classes(self, X, batch_size: Optional[int] = None, nonfinite: Optional[str] = None):
+        """Row-wise ``np.argmax`` of predict(X) (cnn.py:209: first maximum wins), int32 (n,).  nonfinite: as predict (a NaN
+        row's argmax is 0)."""
+        _nonfinite_policy(nonfinite)
         if not isinstance(X, _torch().Tensor):
-            return self.predict_host(X, batch_size, want_probs=False)[1]
-        as_numpy, _probs, labels, _ = self._run(X, batch_size, None)
+            return self.predict_host(X, batch_size, want_probs=False, nonfinite=nonfinite)[1]
+        as_numpy, _probs, labels, _ = self._run(X, batch_size, None, nonfinite)
         return labels.cpu().numpy() if as_numpy else labels
 
     # ------------------------------------------------------------------ evaluation (cnn.py:198-216)
@@ -543,14 +609,17 @@ class VTCNN2:
             raise ValueError(f"{nbad} labels lie outside [0, {Cn})")
         return counts
 
-    def evaluate(self, X, Y, batch_size: Optional[int] = None, verbose: int = 0) -> float:
+    def evaluate(self, X, Y, batch_size: Optional[int] = None, verbose: int = 0, nonfinite: Optional[str] = None) -> float:
         """``score = model.evaluate(X_test, Y_test, verbose=0, batch_size=...)`` (cnn.py:153): the reference compiles its model with
         loss='categorical_crossentropy' and no metric, so the score is the MEAN LOSS -- Keras' categorical cross-entropy
         on the softmax rows (row scaled to sum 1, clipped to [1e-7, 1 - 1e-7]).  Y: one-hot rows (n, C) as cnn.py:80-82
-        builds them, or class indices (n,).  One forward, one reduction launch (mdc_crossentropy), one scalar read-back."""
+        builds them, or class indices (n,).  One forward, one reduction launch (mdc_crossentropy), one scalar read-back.
+        nonfinite="propagate": a frame holding a NaN / +-Inf sample makes the score nan, as cnn.py:153 prints it; "raise":
+        NonFiniteInputError names such frames."""
         torch = _torch()
+        _nonfinite_policy(nonfinite)
         Xt = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(X), dtype=np.float32)).to(f"cuda:{self.device_index}")
-        probs = self.predict(Xt, batch_size)
+        probs = self.predict(Xt, batch_size, nonfinite=nonfinite)
         dev = probs.device
         y = Y if isinstance(Y, torch.Tensor) else torch.as_tensor(np.asarray(Y))
         if y.ndim == 2:
