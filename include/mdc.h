@@ -48,7 +48,8 @@ extern "C" {
                                   22,144 to 11,584 bytes: ask mdc_workspace_bytes); MDC_OPT_FP8_BF16_FEATURES restores
                                   ABI 3's numerics and workspace
                                5: the training step (mdc_trainer_*, mdc_train_batch): additive; later, also additive:
-                                  mdc_forward_checked / mdc_predict_host_checked, MDC_NONFINITE_* (non-finite frames) */
+                                  mdc_forward_checked / mdc_predict_host_checked, MDC_NONFINITE_* (non-finite frames);
+                                  mdc_iq_u8_windows_norm / mdc_predict_host_iq_u8_norm (level-normalised raw I/Q) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -266,6 +267,43 @@ MDC_API int mdc_forward_iq_u8(const mdc_model* m, const uint8_t* iq_dev, int64_t
                       float* probs_dev, int32_t* labels_dev,
                       void* workspace_dev, size_t workspace_bytes, void* hip_stream);
 
+/* ---- level-normalised windows: DC removal, fixed rms, power (additive in ABI 5) ------------------------------------------
+ * mdc_iq_u8_windows / mdc_forward_iq_u8 turn every byte into (byte - 127.5) * scale with ONE scale for the whole capture,
+ * but the nets were trained on level-normalised frames (RadioML2016.10a normalises each 128-sample vector's energy; the
+ * bundled frames sit at a complex rms of about 7.8e-3), and an RTL-SDR capture has whatever level the tuner gain gave it
+ * plus a DC offset.  mdc_iq_u8_windows_norm is mdc_iq_u8_windows with a scale PER WINDOW, chosen so that the window's
+ * complex rms sqrt(mean(I^2 + Q^2)) equals `level`, after removing each channel's mean if MDC_IQ_REMOVE_DC is set; it
+ * also returns the window's statistics as exact integers, for a power estimate / squelch.
+ *
+ * Windows are addressed exactly as in mdc_iq_u8_windows: window i covers bytes [2*hop*i, 2*hop*i + 256) of iq_dev, hop in
+ * 1..2^24, iq_dev 2-byte aligned (odd hops are supported).  With s = 2*byte - 255 (an odd integer in [-255, 255]):
+ *     sum_i, sum_q   sum of s over the window's 128 I bytes / 128 Q bytes
+ *     sum_sq         sum of s_I^2 + s_Q^2 over the 128 pairs (<= 16,646,400)
+ *     energy  E      with MDC_IQ_REMOVE_DC:  E = 128*sum_sq - sum_i^2 - sum_q^2  ( = 128 * sum |a|^2,  a = s - mean )
+ *                    without it:             E = 128*sum_sq                      ( a = s )
+ *                    0 <= E <= 128*256*255^2 = 2,130,739,200 < 2^31; computed in integers: all four fields are exact.
+ *     x              = a * (128*level / sqrt(E)), I in row 0 and Q in row 1 of the (2,128) frame.  a is exact in f32 (s is
+ *                    an integer, the mean a multiple of 1/128); the remaining roundings are the conversion of E, the
+ *                    square root, one division and one multiplication, each correctly rounded: |x - exact| <= 2^-21 |exact|.
+ *                    A constant window (E == 0) gives an all-zero frame, never NaN or Inf.
+ * The window's power relative to a full-scale constant-envelope one is E / (128*255)^2 (10*log10 of it: dBFS).
+ * x_dev (n,2,128) f32, 8-byte aligned, or NULL (statistics only); stats_dev (n), 16-byte aligned, or NULL; not both NULL.
+ * level must be finite and > 0; flags may hold MDC_IQ_REMOVE_DC only; a NULL iq_dev with n > 0: MDC_EINVAL.  The call only
+ * enqueues on hip_stream (no synchronisation, no allocation: capturable in a hipGraph) and runs on the current device, like
+ * mdc_iq_u8_windows.  Followed by mdc_forward it serves every kind, MDC_KIND_CNNPY included.
+ * MDC_FP8: set mdc_set_fp8_input_absmax to level x the crest factor (peak / rms) the caller expects of its signals; the hard
+ * bound on a normalised sample is level * sqrt(128) (one pair carrying the whole window's energy). */
+typedef struct mdc_iq_window_stats {   /* 16 B */
+    int32_t  sum_i, sum_q;
+    uint32_t sum_sq;
+    uint32_t energy;
+} mdc_iq_window_stats;
+
+#define MDC_IQ_REMOVE_DC 1             /* flags of mdc_iq_u8_windows_norm / mdc_predict_host_iq_u8_norm */
+
+MDC_API int mdc_iq_u8_windows_norm(const uint8_t* iq_dev, int64_t n, int64_t hop, float level, int flags,
+                           float* x_dev, mdc_iq_window_stats* stats_dev, void* hip_stream);
+
 /* test_Y_hat = model.predict(X_test, batch_size=batch_size)  (cnn.py:198, 237) when X_test lies in HOST memory -- a
  * numpy array, or whatever buffer a cgo / JNI / N-API caller holds: the library's own driver in front of mdc_forward.
  * Frames are copied into a pinned ring by a few host threads, DMA'd, computed and the results DMA'd back in three
@@ -282,6 +320,15 @@ MDC_API int mdc_predict_host(mdc_model* m, const float* x_host, int64_t n, float
  * iq_host (2*hop*(n-1) + 256 bytes) through mdc_forward_iq_u8 -- 2*hop bytes per window over PCIe instead of 1,024. */
 MDC_API int mdc_predict_host_iq_u8(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t hop, float scale,
                            float* probs_host, int32_t* labels_host, int64_t chunk_frames);
+
+/* The same through mdc_iq_u8_windows_norm + mdc_forward: each slot's bytes are normalised into a frame buffer of the
+ * model's host context (freed by mdc_destroy; a default chunk keeps it within 64 MiB per slot) and forwarded from there, so
+ * every kind is served, MDC_KIND_CNNPY included.  level / flags as mdc_iq_u8_windows_norm; stats_host (n) receives the
+ * windows' statistics, or is NULL.  Results are bit-identical to the two device calls on the same bytes, whatever the
+ * chunk. */
+MDC_API int mdc_predict_host_iq_u8_norm(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t hop, float level, int flags,
+                           float* probs_host, int32_t* labels_host, mdc_iq_window_stats* stats_host,
+                           int64_t chunk_frames);
 
 /* Measurement support (bench.py roofline leg): when on, mdc_forward brackets each kernel
  * launch with HIP events on the launch stream; mdc_profile_read synchronises on them and

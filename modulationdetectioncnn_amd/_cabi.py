@@ -9,6 +9,8 @@ import ctypes as C
 import os
 from typing import Optional
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmdc.so")
 # "alternates" = the -DMDC_ALTERNATES test build (build.py): the product kernels plus the measured-slower alternates the
@@ -30,12 +32,16 @@ EXPORTS = [
     "mdc_trainer_get_tensor", "mdc_trainer_set_iterations", "mdc_train_batch", "mdc_trainer_evaluate", "mdc_trainer_read",
     "mdc_trainer_destroy",
     "mdc_forward_checked", "mdc_predict_host_checked",
+    "mdc_iq_u8_windows_norm", "mdc_predict_host_iq_u8_norm",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
 MDC_OPT_FP8_BF16_FEATURES = 1      # include/mdc.h: option bit in mdc_topology.reserved[0]
 HOP_FRAME = 128
 NONFINITE_REPORT, NONFINITE_PROPAGATE = 0, 1     # include/mdc.h: policies of mdc_forward_checked / mdc_predict_host_checked
+IQ_REMOVE_DC = 1                                 # include/mdc.h: flag of mdc_iq_u8_windows_norm / mdc_predict_host_iq_u8_norm
+# mdc_iq_window_stats (16 B): one record per window, exact integers (s = 2*byte - 255)
+IQ_WINDOW_STATS = np.dtype([("sum_i", np.int32), ("sum_q", np.int32), ("sum_sq", np.uint32), ("energy", np.uint32)])
 
 
 class MdcTopology(C.Structure):
@@ -103,7 +109,9 @@ def lib(variant: str = "product") -> C.CDLL:
     # (getattr with a default: tools/ab_libs.py loads builds from before these entries; tests/test_nonfinite_abi.py holds
     # both libraries of this tree to exporting them)
     for name, args in (("mdc_forward_checked", [vp, vp, i64, vp, vp, vp, sz, vp, vp, i32, vp]),
-                       ("mdc_predict_host_checked", [vp, vp, i64, vp, vp, vp, vp, i32, i64])):
+                       ("mdc_predict_host_checked", [vp, vp, i64, vp, vp, vp, vp, i32, i64]),
+                       ("mdc_iq_u8_windows_norm", [vp, i64, i64, C.c_float, i32, vp, vp, vp]),
+                       ("mdc_predict_host_iq_u8_norm", [vp, vp, i64, i64, C.c_float, i32, vp, vp, vp, i64])):
         fn = getattr(L, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, i32

@@ -106,6 +106,9 @@ struct Slot {
     int32_t* d_labels = nullptr;
     uint8_t* d_flags = nullptr;   // mdc_predict_host_checked: the frames' non-finite flags
     char* pin_out = nullptr;      // probabilities, then labels, then flags
+    float* d_x = nullptr;         // mdc_predict_host_iq_u8_norm: the slot's normalised frames, between the two device calls
+    mdc_iq_window_stats* d_stats = nullptr;      // ... and its windows' statistics, with their own pinned landing buffer
+    char* pin_stats = nullptr;
     hipEvent_t in_done = nullptr, comp_done = nullptr, out_done = nullptr;
     int64_t start = 0, count = 0;
     bool busy = false;
@@ -118,6 +121,7 @@ struct HostCtx {
     Slot slot[kSlots];
     size_t in_cap = 0;            // bytes of input per slot
     int64_t out_cap = 0;          // frames of output per slot
+    int64_t norm_cap = 0;         // frames of d_x / d_stats / pin_stats per slot (0 until the first normalised call)
     void* ws = nullptr;
     size_t ws_bytes = 0;
 };
@@ -132,6 +136,9 @@ void host_ctx_free(mdc_model* m) {
         if (s.d_probs) (void)hipFree(s.d_probs);
         if (s.d_labels) (void)hipFree(s.d_labels);
         if (s.d_flags) (void)hipFree(s.d_flags);
+        if (s.d_x) (void)hipFree(s.d_x);
+        if (s.d_stats) (void)hipFree(s.d_stats);
+        if (s.pin_stats) (void)hipHostFree(s.pin_stats);
         if (s.in_done) (void)hipEventDestroy(s.in_done);
         if (s.comp_done) (void)hipEventDestroy(s.comp_done);
         if (s.out_done) (void)hipEventDestroy(s.out_done);
@@ -215,6 +222,29 @@ int ctx_prepare(mdc_model* m, size_t in_bytes, int64_t frames) {
     return MDC_OK;
 }
 
+// the normalised path's extra buffers: a slot's frames (1 KiB each) and statistics; grown on demand like the others
+int ctx_prepare_norm(mdc_model* m, int64_t frames) {
+    HostCtx* c = static_cast<HostCtx*>(m->host_ctx);
+    if (frames <= c->norm_cap) return MDC_OK;
+    for (Slot& s : c->slot) {
+        if (s.d_x) { (void)hipFree(s.d_x); s.d_x = nullptr; }
+        if (s.d_stats) { (void)hipFree(s.d_stats); s.d_stats = nullptr; }
+        if (s.pin_stats) { (void)hipHostFree(s.pin_stats); s.pin_stats = nullptr; }
+    }
+    c->norm_cap = 0;
+    for (Slot& s : c->slot) {
+        if (hipMalloc(reinterpret_cast<void**>(&s.d_x), (size_t)frames * kFrameFloats * 4) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&s.d_stats), (size_t)frames * sizeof(mdc_iq_window_stats)) != hipSuccess ||
+            hipHostMalloc(reinterpret_cast<void**>(&s.pin_stats), (size_t)frames * sizeof(mdc_iq_window_stats), hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("host path: cannot allocate normalised-frame staging for %lld frames per slot", (long long)frames);
+            return MDC_ENOMEM;
+        }
+    }
+    c->norm_cap = frames;
+    return MDC_OK;
+}
+
 // (the first byte decides: a caller that pins its buffer pins all of it)
 // 0 = pageable host memory (or unknown to HIP), 1 = pinned host memory, -1 = DEVICE memory: not a host buffer at all
 int host_kind(const void* p) {
@@ -228,7 +258,7 @@ bool is_pinned(const void* p) { return host_kind(p) == 1; }
 // in_range(start, count) -> (byte offset, byte count) of the input those windows read; launch(d_in, count, slot, ctx)
 template <class InRange, class Launch>
 int run_pipeline(mdc_model* m, const char* src, int64_t n, int64_t chunk, bool ramp, float* probs_host, int32_t* labels_host,
-                 uint8_t* flags_host, InRange in_range, Launch launch) {
+                 uint8_t* flags_host, mdc_iq_window_stats* stats_host, InRange in_range, Launch launch) {
     HostCtx* c = static_cast<HostCtx*>(m->host_ctx);
     const int C = m->topo.classes;
     const bool direct = is_pinned(src);
@@ -243,6 +273,7 @@ int run_pipeline(mdc_model* m, const char* src, int64_t n, int64_t chunk, bool r
         if (probs_host) std::memcpy(probs_host + s.start * C, s.pin_out, (size_t)s.count * C * 4);
         if (labels_host) std::memcpy(labels_host + s.start, s.pin_out + (size_t)c->out_cap * C * 4, (size_t)s.count * 4);
         if (flags_host) std::memcpy(flags_host + s.start, s.pin_out + (size_t)c->out_cap * (C + 1) * 4, (size_t)s.count);
+        if (stats_host) std::memcpy(stats_host + s.start, s.pin_stats, (size_t)s.count * sizeof(mdc_iq_window_stats));
         s.busy = false;
         return MDC_OK;
     };
@@ -282,6 +313,7 @@ int run_pipeline(mdc_model* m, const char* src, int64_t n, int64_t chunk, bool r
         if (e == hipSuccess && probs_host) e = hipMemcpyAsync(s.pin_out, s.d_probs, (size_t)count * C * 4, hipMemcpyDeviceToHost, c->out_s);
         if (e == hipSuccess && labels_host) e = hipMemcpyAsync(s.pin_out + (size_t)c->out_cap * C * 4, s.d_labels, (size_t)count * 4, hipMemcpyDeviceToHost, c->out_s);
         if (e == hipSuccess && flags_host) e = hipMemcpyAsync(s.pin_out + (size_t)c->out_cap * (C + 1) * 4, s.d_flags, (size_t)count, hipMemcpyDeviceToHost, c->out_s);
+        if (e == hipSuccess && stats_host) e = hipMemcpyAsync(s.pin_stats, s.d_stats, (size_t)count * sizeof(mdc_iq_window_stats), hipMemcpyDeviceToHost, c->out_s);
         if (e == hipSuccess) e = hipEventRecord(s.out_done, c->out_s);
         if (e != hipSuccess) { set_error("host path: result copy failed: %s", hipGetErrorString(e)); rc = MDC_EIO; break; }
         s.start = start;
@@ -333,7 +365,7 @@ int predict_host(mdc_model* m, const float* x_host, int64_t n, float* probs_host
     const int64_t chunk = std::min<int64_t>(chunk_frames > 0 ? chunk_frames : default_chunk(n), n);
     if ((rc = ctx_prepare(m, (size_t)chunk * kFrameFloats * 4, chunk)) != MDC_OK) return rc;
     return run_pipeline(
-        m, reinterpret_cast<const char*>(x_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr,
+        m, reinterpret_cast<const char*>(x_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr, nullptr,
         [](int64_t start, int64_t count, size_t* off, size_t* bytes) {
             *off = (size_t)start * kFrameFloats * 4;
             *bytes = (size_t)count * kFrameFloats * 4;
@@ -359,7 +391,7 @@ int predict_host_checked(mdc_model* m, const float* x_host, int64_t n, float* pr
     const int64_t chunk = std::min<int64_t>(chunk_frames > 0 ? chunk_frames : default_chunk(n), n);
     if ((rc = ctx_prepare(m, (size_t)chunk * kFrameFloats * 4, chunk)) != MDC_OK) return rc;
     rc = run_pipeline(
-        m, reinterpret_cast<const char*>(x_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nonfinite_host,
+        m, reinterpret_cast<const char*>(x_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nonfinite_host, nullptr,
         [](int64_t start, int64_t count, size_t* off, size_t* bytes) {
             *off = (size_t)start * kFrameFloats * 4;
             *bytes = (size_t)count * kFrameFloats * 4;
@@ -393,7 +425,7 @@ int predict_host_iq_u8(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t 
     const size_t in_bytes = (size_t)(2 * hop) * (size_t)(chunk - 1) + 256;
     if ((rc = ctx_prepare(m, in_bytes, chunk)) != MDC_OK) return rc;
     return run_pipeline(
-        m, reinterpret_cast<const char*>(iq_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr,
+        m, reinterpret_cast<const char*>(iq_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr, nullptr,
         [hop](int64_t start, int64_t count, size_t* off, size_t* bytes) {
             *off = (size_t)(2 * hop) * (size_t)start;
             *bytes = (size_t)(2 * hop) * (size_t)(count - 1) + 256;
@@ -401,6 +433,39 @@ int predict_host_iq_u8(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t 
         [m, hop, scale](Slot& s, int64_t count, HostCtx* c) {
             return mdc_forward_iq_u8(m, reinterpret_cast<const uint8_t*>(s.d_in), count, hop, scale, s.d_probs, s.d_labels, c->ws, c->ws_bytes,
                                      c->comp_s);
+        });
+}
+
+// mdc_predict_host_iq_u8 with mdc_iq_u8_windows_norm into the slot's frame buffer + mdc_forward in the compute step, and one
+// more result copy (the statistics).  Through frames, so cnn.py's literal model is served too.
+int predict_host_iq_u8_norm(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t hop, float level, int flags, float* probs_host,
+                            int32_t* labels_host, mdc_iq_window_stats* stats_host, int64_t chunk_frames) {
+    int rc = iq_norm_check("mdc_predict_host_iq_u8_norm", hop, level, flags);
+    if (rc != MDC_OK) return rc;
+    if ((rc = check_common("mdc_predict_host_iq_u8_norm", m, iq_host, n, chunk_frames)) != MDC_OK) return rc;
+    if (n == 0) return MDC_OK;
+    std::lock_guard<std::mutex> g(m->host_mu);
+    DeviceScope dev(m->device);
+    if (!dev.ok) { set_error("mdc_predict_host_iq_u8_norm: cannot select device %d", m->device); return MDC_EIO; }
+    int64_t chunk = std::min<int64_t>(chunk_frames > 0 ? chunk_frames : default_chunk(n), n);
+    if (chunk_frames <= 0) {      // default: a slot's frames are within 64 MiB already (default_chunk); so are its bytes, however large the hop
+        const int64_t fit = ((kDefaultChunkFrames * kFrameFloats * 4) - 256) / (2 * hop) + 1;
+        chunk = std::max<int64_t>(1, std::min(chunk, fit));
+    }
+    const size_t in_bytes = (size_t)(2 * hop) * (size_t)(chunk - 1) + 256;
+    if ((rc = ctx_prepare(m, in_bytes, chunk)) != MDC_OK) return rc;
+    if ((rc = ctx_prepare_norm(m, chunk)) != MDC_OK) return rc;
+    return run_pipeline(
+        m, reinterpret_cast<const char*>(iq_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr, stats_host,
+        [hop](int64_t start, int64_t count, size_t* off, size_t* bytes) {
+            *off = (size_t)(2 * hop) * (size_t)start;
+            *bytes = (size_t)(2 * hop) * (size_t)(count - 1) + 256;
+        },
+        [m, hop, level, flags, stats_host](Slot& s, int64_t count, HostCtx* c) {
+            int r = mdc_iq_u8_windows_norm(reinterpret_cast<const uint8_t*>(s.d_in), count, hop, level, flags, s.d_x, stats_host ? s.d_stats : nullptr,
+                                           c->comp_s);
+            if (r != MDC_OK) return r;
+            return mdc_forward(m, s.d_x, count, s.d_probs, s.d_labels, nullptr, MDC_TAP_NONE, c->ws, c->ws_bytes, c->comp_s);
         });
 }
 

@@ -52,6 +52,14 @@ ProfScope::~ProfScope() {
     }
 }
 
+// what mdc_iq_u8_windows_norm and mdc_predict_host_iq_u8_norm ask of hop, level and flags (before any device call)
+int iq_norm_check(const char* who, int64_t hop, float level, int flags) {
+    if (hop < 1 || hop > (int64_t)1 << 24) { set_error("%s: hop must be in 1..2^24 sample pairs (got %lld)", who, (long long)hop); return MDC_EINVAL; }
+    if (!(level > 0.f) || !(level <= 3.402823466e38f)) { set_error("%s: level must be finite and > 0", who); return MDC_EINVAL; }
+    if ((flags & ~MDC_IQ_REMOVE_DC) != 0) { set_error("%s: unknown flag bits 0x%x", who, flags & ~MDC_IQ_REMOVE_DC); return MDC_EINVAL; }
+    return MDC_OK;
+}
+
 }  // namespace mdc
 
 using namespace mdc;
@@ -375,6 +383,20 @@ int mdc_iq_u8_windows(const uint8_t* iq_dev, int64_t n, int64_t hop, float scale
     return guarded("mdc_iq_u8_windows", [&]() -> int { return iq_u8_launch(iq_dev, n, hop, scale, x_dev, static_cast<hipStream_t>(hip_stream)); });
 }
 
+int mdc_iq_u8_windows_norm(const uint8_t* iq_dev, int64_t n, int64_t hop, float level, int flags, float* x_dev,
+                           mdc_iq_window_stats* stats_dev, void* hip_stream) {
+    if (n < 0) { set_error("mdc_iq_u8_windows_norm: negative window count"); return MDC_EINVAL; }
+    int rc = iq_norm_check("mdc_iq_u8_windows_norm", hop, level, flags);
+    if (rc != MDC_OK) return rc;
+    if (!x_dev && !stats_dev) { set_error("mdc_iq_u8_windows_norm: x_dev and stats_dev are both null (nothing to compute)"); return MDC_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(x_dev) & 7) != 0) { set_error("mdc_iq_u8_windows_norm: frames must be 8-byte aligned"); return MDC_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(stats_dev) & 15) != 0) { set_error("mdc_iq_u8_windows_norm: statistics must be 16-byte aligned"); return MDC_EINVAL; }
+    if (n > 0 && !iq_dev) { set_error("mdc_iq_u8_windows_norm: null input"); return MDC_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(iq_dev) & 1) != 0) { set_error("mdc_iq_u8_windows_norm: input must start on a whole (I,Q) pair (2-byte aligned)"); return MDC_EINVAL; }
+    return guarded("mdc_iq_u8_windows_norm", [&]() -> int {
+        return iq_norm_launch(iq_dev, n, hop, level, flags, x_dev, stats_dev, static_cast<hipStream_t>(hip_stream)); });
+}
+
 int mdc_set_profiling(mdc_model* m, int on) {
     if (!m) { set_error("null model"); return MDC_EINVAL; }
     m->profiling = on != 0;
@@ -445,6 +467,12 @@ int mdc_predict_host_checked(mdc_model* m, const float* x_host, int64_t n, float
 int mdc_predict_host_iq_u8(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t hop, float scale, float* probs_host,
                            int32_t* labels_host, int64_t chunk_frames) {
     return guarded("mdc_predict_host_iq_u8", [&]() -> int { return predict_host_iq_u8(m, iq_host, n, hop, scale, probs_host, labels_host, chunk_frames); });
+}
+
+int mdc_predict_host_iq_u8_norm(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t hop, float level, int flags, float* probs_host,
+                                int32_t* labels_host, mdc_iq_window_stats* stats_host, int64_t chunk_frames) {
+    return guarded("mdc_predict_host_iq_u8_norm", [&]() -> int {
+        return predict_host_iq_u8_norm(m, iq_host, n, hop, level, flags, probs_host, labels_host, stats_host, chunk_frames); });
 }
 
 void mdc_destroy(mdc_model* m) {

@@ -747,7 +747,8 @@ class VTCNN2:
         return (out.cpu().numpy(), labels.cpu().numpy()) if as_numpy else (out, labels)
 
     # ------------------------------------------------------------------ raw SDR bytes
-    def predict_iq_u8(self, iq, scale: Optional[float] = None, batch_size: int = 0, hop: int = 128):
+    def predict_iq_u8(self, iq, scale: Optional[float] = None, batch_size: int = 0, hop: int = 128, normalize: Optional[str] = None,
+                      level: float = 7.8e-3, remove_dc: bool = True, squelch_dbfs: Optional[float] = None, return_power: bool = False):
         """`predict` on raw RTL-SDR samples: iq holds unsigned bytes (I0,Q0,I1,Q1,...), each sample becomes
         (byte - 127.5) * scale (default 1/127.5).  Window i is the 128 (I,Q) pairs starting at pair i*hop of the
         capture: hop = 128 cuts it into disjoint 256-byte frames (then the byte count must be a multiple of 256),
@@ -755,9 +756,25 @@ class VTCNN2:
         nets and the VT-CNN2 family read the bytes in the forward kernels themselves (mdc_forward_iq_u8: 2*hop B of
         HBM input per window, no frame buffer); cnn.py's literal model converts on the device first
         (frames_from_iq_u8) -- the results are bit-identical either way.  Returns (probs, labels) as device tensors
-        for a device tensor input, numpy arrays otherwise."""
+        for a device tensor input, numpy arrays otherwise.
+
+        normalize="rms": one scale PER WINDOW instead of `scale` (giving both is a ValueError) -- each window is brought to
+        complex rms `level` (the level the nets were trained at), after removing each channel's mean if remove_dc
+        (mdc_iq_u8_windows_norm, include/mdc.h), whatever the tuner gain and DC offset of the capture.  A device tensor runs
+        chunk by chunk through mdc_iq_u8_windows_norm + mdc_forward on torch's current stream, numpy bytes through
+        mdc_predict_host_iq_u8_norm; every kind of net.  squelch_dbfs (needs normalize="rms"): windows whose power
+        (frontend.window_power_dbfs: 0 dBFS = a full-scale constant envelope) lies below it get label -1, their
+        probabilities stay as computed.  return_power=True appends the per-window dBFS vector (float64) to the result."""
         torch = _torch()
         from .frontend import DEFAULT_SCALE, frames_from_iq_u8, window_count
+        if normalize is not None:
+            if normalize != "rms":
+                raise ValueError(f"normalize must be None or 'rms'; got {normalize!r}")
+            if scale is not None:
+                raise ValueError("scale= and normalize='rms' cannot be combined: the normalised path scales each window itself")
+            return self._predict_iq_u8_norm(iq, batch_size, hop, float(level), bool(remove_dc), squelch_dbfs, bool(return_power))
+        if squelch_dbfs is not None or return_power:
+            raise ValueError("squelch_dbfs and return_power need normalize='rms' (the plain path computes no window power)")
         scale = DEFAULT_SCALE if scale is None else float(scale)
         as_numpy = not isinstance(iq, torch.Tensor)
         if as_numpy and self.topology.kind != "cnnpy":      # host bytes: the library's streaming driver (mdc_predict_host_iq_u8)
@@ -793,6 +810,55 @@ class VTCNN2:
                                                     probs.data_ptr() + s0 * Cn * 4, labels.data_ptr() + s0 * 4,
                                                     ws.data_ptr() if ws is not None else None, ws_bytes, stream))
         return (probs.cpu().numpy(), labels.cpu().numpy()) if as_numpy else (probs, labels)
+
+    def _predict_iq_u8_norm(self, iq, batch_size, hop, level, remove_dc, squelch_dbfs, return_power):
+        torch = _torch()
+        from .frontend import FULL_SCALE_ENERGY, squelch_energy_threshold, window_count, window_power_dbfs
+        if not (level > 0.0 and np.isfinite(level)):
+            raise ValueError("level must be finite and > 0")
+        flags = _cabi.IQ_REMOVE_DC if remove_dc else 0
+        want_stats = squelch_dbfs is not None or return_power
+        floor = squelch_energy_threshold(squelch_dbfs) if squelch_dbfs is not None else 0
+        Cn = self.topology.classes
+        if not isinstance(iq, torch.Tensor):      # host bytes: the library's streaming driver
+            b = np.ascontiguousarray(np.asarray(iq, dtype=np.uint8)).reshape(-1)
+            n = window_count(b.size, hop)
+            probs, labels = np.empty((n, Cn), np.float32), np.empty((n,), np.int32)
+            stats = np.empty((n,), _cabi.IQ_WINDOW_STATS) if want_stats else None
+            self._check(self._lib().mdc_predict_host_iq_u8_norm(self._engine(), b.ctypes.data, n, int(hop), level, flags, probs.ctypes.data,
+                                                                labels.ctypes.data, stats.ctypes.data if want_stats else None,
+                                                                self._host_chunk(batch_size)))
+            if squelch_dbfs is not None:
+                labels[stats["energy"] < floor] = -1
+            return (probs, labels, window_power_dbfs(stats)) if return_power else (probs, labels)
+        if iq.dtype != torch.uint8:
+            raise TypeError(f"iq must be uint8, got {iq.dtype}")
+        t = iq.to(f"cuda:{self.device_index}").contiguous().view(-1)
+        n = window_count(t.numel(), hop)
+        if t.data_ptr() % 2:
+            t = t.clone()       # a view into a larger buffer starting at an odd byte: the ABI wants whole (I,Q) pairs
+        probs = torch.empty((n, Cn), dtype=torch.float32, device=t.device)
+        labels = torch.empty((n,), dtype=torch.int32, device=t.device)
+        stats = torch.empty((n, 4), dtype=torch.int32, device=t.device) if want_stats else None
+        if n:
+            L, h = self._lib(), self._engine()
+            chunk = max(1, min(int(batch_size) if batch_size else self.default_chunk, n))
+            with torch.cuda.device(t.device):
+                stream = torch.cuda.current_stream(t.device).cuda_stream
+                ws, ws_bytes = self._workspace(chunk, stream)
+                x = torch.empty((chunk, 2, 128), dtype=torch.float32, device=t.device)      # one chunk of frames, reused in stream order
+                for s0 in range(0, n, chunk):
+                    m = min(chunk, n - s0)
+                    self._check(L.mdc_iq_u8_windows_norm(t.data_ptr() + 2 * hop * s0, m, hop, level, flags, x.data_ptr(),
+                                                         (stats.data_ptr() + 16 * s0) if want_stats else None, stream))
+                    self._check(L.mdc_forward(h, x.data_ptr(), m, probs.data_ptr() + s0 * Cn * 4, labels.data_ptr() + s0 * 4, None,
+                                              _cabi.TAP_NONE, ws.data_ptr() if ws is not None else None, ws_bytes, stream))
+        if squelch_dbfs is not None:
+            # (every energy is below 2^31 - 1: the int32 column holds it as it is, and a larger floor means the same as that one)
+            labels.masked_fill_(stats[:, 3] < min(floor, 0x7FFFFFFF), -1)
+        if return_power:
+            return probs, labels, 10.0 * torch.log10(stats[:, 3].to(torch.float64) / FULL_SCALE_ENERGY)
+        return probs, labels
 
     # ------------------------------------------------------------------ measurement hooks
     def set_profiling(self, on: bool) -> None:
