@@ -49,7 +49,9 @@ extern "C" {
                                   ABI 3's numerics and workspace
                                5: the training step (mdc_trainer_*, mdc_train_batch): additive; later, also additive:
                                   mdc_forward_checked / mdc_predict_host_checked, MDC_NONFINITE_* (non-finite frames);
-                                  mdc_iq_u8_windows_norm / mdc_predict_host_iq_u8_norm (level-normalised raw I/Q) */
+                                  mdc_iq_u8_windows_norm / mdc_predict_host_iq_u8_norm (level-normalised raw I/Q);
+                                  mdc_iq_windows / mdc_iq_windows_norm / mdc_predict_host_iq / mdc_predict_host_iq_norm
+                                  (signed 8- and 16-bit sample formats, MDC_IQ_*, mdc_iq_window_stats64) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -304,6 +306,49 @@ typedef struct mdc_iq_window_stats {   /* 16 B */
 MDC_API int mdc_iq_u8_windows_norm(const uint8_t* iq_dev, int64_t n, int64_t hop, float level, int flags,
                            float* x_dev, mdc_iq_window_stats* stats_dev, void* hip_stream);
 
+/* ---- other sample formats: signed 8- and 16-bit captures (additive in ABI 5) ----------------------------------------------
+ * mdc_iq_windows / mdc_iq_windows_norm are mdc_iq_u8_windows / mdc_iq_u8_windows_norm for a capture in one of three integer
+ * sample formats, interleaved I0 Q0 I1 Q1 ...; one (I,Q) PAIR is 2 / 2 / 4 bytes:
+ *     format         integer sample s            plain conversion x (mdc_iq_windows)              full-scale amplitude A
+ *     MDC_IQ_CU8     2*byte - 255                (byte - 127.5) * scale  (exactly mdc_iq_u8_windows)   255   RTL-SDR, SigMF cu8
+ *     MDC_IQ_CI8     the int8 value              (float)s * scale                                      128   HackRF, SigMF ci8
+ *     MDC_IQ_CI16    the int16 value, little-    (float)s * scale                                    32768   USRP sc16, SDRplay,
+ *                    endian                                                                                  bladeRF, Airspy, ci16_le
+ * Windows are addressed as in mdc_iq_u8_windows: window i is the 128 pairs from pair i*hop on, hop in 1..2^24 (odd hops are
+ * supported); iq_dev holds (hop*(n-1) + 128) pairs and is aligned to ONE PAIR (2 / 2 / 4 bytes), otherwise MDC_EINVAL; an
+ * unknown format: MDC_EINVAL.
+ *
+ * mdc_iq_windows_norm: sum_i, sum_q, sum_sq and the energy E are defined on s exactly as in the block above
+ * (E = 128*sum_sq - sum_i^2 - sum_q^2 with MDC_IQ_REMOVE_DC, 128*sum_sq without) and returned as exact integers in the
+ * 32-byte record below.  Bounds:   |sum_i|, |sum_q|      sum_sq            E
+ *     MDC_IQ_CU8                   <= 32,640             <= 16,646,400     <= 2,130,739,200 (the four values of mdc_iq_window_stats)
+ *     MDC_IQ_CI8                   <= 2^14               <= 2^22           <= 2^29
+ *     MDC_IQ_CI16                  <= 2^22               <= 2^38           <= 2^45
+ * Frames, normatively, are the chain of operations of mdc_iq_u8_windows_norm:
+ *     x = (float)(128*s - c) * (level / sqrtf((float)E)),   c = the channel's sum under MDC_IQ_REMOVE_DC, else 0;
+ * |128*s - c| < 2^24 in every format, so its conversion is exact; (float)E is ONE correctly rounded conversion of the 64-bit
+ * integer; square root, division and multiplication are correctly rounded: |x - exact| <= 2^-21 |exact| as above.  E == 0
+ * gives an all-zero frame.  (MDC_IQ_CI16 with a level so small that level / sqrt(E) nears the f32 denormals -- 1e-30 -- is
+ * outside this bound.)  With MDC_IQ_CU8 the frames are bit-identical to mdc_iq_u8_windows / mdc_iq_u8_windows_norm.
+ * The window's power relative to a full-scale constant-envelope one is E / (128*A)^2 (10*log10 of it: dBFS); the largest
+ * possible window is +3 dB in every format.
+ * x_dev (n,2,128) f32, 8-byte aligned; stats64_dev (n), 16-byte aligned; in mdc_iq_windows_norm each may be NULL, not both.
+ * level, flags as mdc_iq_u8_windows_norm.  n == 0 is MDC_OK.  Both calls only enqueue on hip_stream (no synchronisation, no
+ * allocation: capturable in a hipGraph) and run on the current device.
+ * Float captures (cf32) are not served: they need their own decision on non-finite samples and on what "exact statistics"
+ * means.  Big-endian 16-bit samples must be swapped by the caller. */
+enum { MDC_IQ_CU8 = 0, MDC_IQ_CI8 = 1, MDC_IQ_CI16 = 2 };
+
+typedef struct mdc_iq_window_stats64 {   /* 32 B */
+    int64_t  sum_i, sum_q;
+    uint64_t sum_sq;
+    uint64_t energy;
+} mdc_iq_window_stats64;
+
+MDC_API int mdc_iq_windows(const void* iq_dev, int format, int64_t n, int64_t hop, float scale, float* x_dev, void* hip_stream);
+MDC_API int mdc_iq_windows_norm(const void* iq_dev, int format, int64_t n, int64_t hop, float level, int flags,
+                           float* x_dev, mdc_iq_window_stats64* stats64_dev, void* hip_stream);
+
 /* test_Y_hat = model.predict(X_test, batch_size=batch_size)  (cnn.py:198, 237) when X_test lies in HOST memory -- a
  * numpy array, or whatever buffer a cgo / JNI / N-API caller holds: the library's own driver in front of mdc_forward.
  * Frames are copied into a pinned ring by a few host threads, DMA'd, computed and the results DMA'd back in three
@@ -328,6 +373,18 @@ MDC_API int mdc_predict_host_iq_u8(mdc_model* m, const uint8_t* iq_host, int64_t
  * chunk. */
 MDC_API int mdc_predict_host_iq_u8_norm(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t hop, float level, int flags,
                            float* probs_host, int32_t* labels_host, mdc_iq_window_stats* stats_host,
+                           int64_t chunk_frames);
+
+/* The two drivers above for a capture in any MDC_IQ_* format (iq_host: (hop*(n-1) + 128) pairs of 2 / 2 / 4 bytes; a
+ * misaligned pointer is copied as it is: only the device side wants whole pairs).  Both go through frames -- mdc_iq_windows /
+ * mdc_iq_windows_norm into the slot's frame buffer, then mdc_forward -- so every kind is served, MDC_KIND_CNNPY included,
+ * and the results are bit-identical to those two device calls on the same samples, whatever the chunk.  stats64_host (n)
+ * receives the windows' 64-bit statistics, or is NULL.  (MDC_IQ_CU8 through mdc_predict_host_iq is
+ * mdc_predict_host_iq_u8 where that serves the model's kind.) */
+MDC_API int mdc_predict_host_iq(mdc_model* m, const void* iq_host, int format, int64_t n, int64_t hop, float scale,
+                           float* probs_host, int32_t* labels_host, int64_t chunk_frames);
+MDC_API int mdc_predict_host_iq_norm(mdc_model* m, const void* iq_host, int format, int64_t n, int64_t hop, float level, int flags,
+                           float* probs_host, int32_t* labels_host, mdc_iq_window_stats64* stats64_host,
                            int64_t chunk_frames);
 
 /* Measurement support (bench.py roofline leg): when on, mdc_forward brackets each kernel

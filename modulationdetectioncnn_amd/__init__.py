@@ -4,6 +4,7 @@ libmdc.so (HIP).  The CPU oracle lives in /oracle and is never imported from her
 from .topology import Topology, synthetic_weights, synthetic_frames  # noqa: F401
 from .model import VTCNN2, Model, NonFiniteInputError  # noqa: F401
 from .frontend import frames_from_iq_u8, normalized_frames_from_iq_u8, window_stats_iq_u8, window_power_dbfs  # noqa: F401
+from .frontend import frames_from_iq, normalized_frames_from_iq, window_stats_iq  # noqa: F401
 from . import callbacks  # noqa: F401
 
 __all__ = ["Topology", "VTCNN2", "Model", "callbacks", "synthetic_weights", "synthetic_frames", "frames_from_iq_u8", "NonFiniteInputError"]

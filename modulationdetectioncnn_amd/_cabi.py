@@ -33,6 +33,7 @@ EXPORTS = [
     "mdc_trainer_destroy",
     "mdc_forward_checked", "mdc_predict_host_checked",
     "mdc_iq_u8_windows_norm", "mdc_predict_host_iq_u8_norm",
+    "mdc_iq_windows", "mdc_iq_windows_norm", "mdc_predict_host_iq", "mdc_predict_host_iq_norm",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
@@ -42,6 +43,12 @@ NONFINITE_REPORT, NONFINITE_PROPAGATE = 0, 1     # include/mdc.h: policies of md
 IQ_REMOVE_DC = 1                                 # include/mdc.h: flag of mdc_iq_u8_windows_norm / mdc_predict_host_iq_u8_norm
 # mdc_iq_window_stats (16 B): one record per window, exact integers (s = 2*byte - 255)
 IQ_WINDOW_STATS = np.dtype([("sum_i", np.int32), ("sum_q", np.int32), ("sum_sq", np.uint32), ("energy", np.uint32)])
+# sample formats of mdc_iq_windows / mdc_iq_windows_norm / mdc_predict_host_iq(_norm): MDC_IQ_*, bytes per (I,Q) pair, numpy dtype
+IQ_CU8, IQ_CI8, IQ_CI16 = 0, 1, 2
+IQ_PAIR_BYTES = {IQ_CU8: 2, IQ_CI8: 2, IQ_CI16: 4}
+IQ_SAMPLE_DTYPE = {IQ_CU8: np.dtype(np.uint8), IQ_CI8: np.dtype(np.int8), IQ_CI16: np.dtype("<i2")}
+# mdc_iq_window_stats64 (32 B): the same four exact integers for any format (s: include/mdc.h)
+IQ_WINDOW_STATS64 = np.dtype([("sum_i", np.int64), ("sum_q", np.int64), ("sum_sq", np.uint64), ("energy", np.uint64)])
 
 
 class MdcTopology(C.Structure):
@@ -111,7 +118,11 @@ def lib(variant: str = "product") -> C.CDLL:
     for name, args in (("mdc_forward_checked", [vp, vp, i64, vp, vp, vp, sz, vp, vp, i32, vp]),
                        ("mdc_predict_host_checked", [vp, vp, i64, vp, vp, vp, vp, i32, i64]),
                        ("mdc_iq_u8_windows_norm", [vp, i64, i64, C.c_float, i32, vp, vp, vp]),
-                       ("mdc_predict_host_iq_u8_norm", [vp, vp, i64, i64, C.c_float, i32, vp, vp, vp, i64])):
+                       ("mdc_predict_host_iq_u8_norm", [vp, vp, i64, i64, C.c_float, i32, vp, vp, vp, i64]),
+                       ("mdc_iq_windows", [vp, i32, i64, i64, C.c_float, vp, vp]),
+                       ("mdc_iq_windows_norm", [vp, i32, i64, i64, C.c_float, i32, vp, vp, vp]),
+                       ("mdc_predict_host_iq", [vp, vp, i32, i64, i64, C.c_float, vp, vp, i64]),
+                       ("mdc_predict_host_iq_norm", [vp, vp, i32, i64, i64, C.c_float, i32, vp, vp, vp, i64])):
         fn = getattr(L, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, i32

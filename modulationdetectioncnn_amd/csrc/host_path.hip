@@ -107,7 +107,7 @@ struct Slot {
     uint8_t* d_flags = nullptr;   // mdc_predict_host_checked: the frames' non-finite flags
     char* pin_out = nullptr;      // probabilities, then labels, then flags
     float* d_x = nullptr;         // mdc_predict_host_iq_u8_norm: the slot's normalised frames, between the two device calls
-    mdc_iq_window_stats* d_stats = nullptr;      // ... and its windows' statistics, with their own pinned landing buffer
+    char* d_stats = nullptr;      // ... and its windows' statistics (16- or 32-byte records), with their own pinned landing buffer
     char* pin_stats = nullptr;
     hipEvent_t in_done = nullptr, comp_done = nullptr, out_done = nullptr;
     int64_t start = 0, count = 0;
@@ -223,6 +223,7 @@ int ctx_prepare(mdc_model* m, size_t in_bytes, int64_t frames) {
 }
 
 // the normalised path's extra buffers: a slot's frames (1 KiB each) and statistics; grown on demand like the others
+constexpr size_t kStatBytesMax = sizeof(mdc_iq_window_stats64);      // room for either record
 int ctx_prepare_norm(mdc_model* m, int64_t frames) {
     HostCtx* c = static_cast<HostCtx*>(m->host_ctx);
     if (frames <= c->norm_cap) return MDC_OK;
@@ -234,8 +235,8 @@ int ctx_prepare_norm(mdc_model* m, int64_t frames) {
     c->norm_cap = 0;
     for (Slot& s : c->slot) {
         if (hipMalloc(reinterpret_cast<void**>(&s.d_x), (size_t)frames * kFrameFloats * 4) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&s.d_stats), (size_t)frames * sizeof(mdc_iq_window_stats)) != hipSuccess ||
-            hipHostMalloc(reinterpret_cast<void**>(&s.pin_stats), (size_t)frames * sizeof(mdc_iq_window_stats), hipHostMallocDefault) != hipSuccess) {
+            hipMalloc(reinterpret_cast<void**>(&s.d_stats), (size_t)frames * kStatBytesMax) != hipSuccess ||
+            hipHostMalloc(reinterpret_cast<void**>(&s.pin_stats), (size_t)frames * kStatBytesMax, hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
             set_error("host path: cannot allocate normalised-frame staging for %lld frames per slot", (long long)frames);
             return MDC_ENOMEM;
@@ -258,7 +259,7 @@ bool is_pinned(const void* p) { return host_kind(p) == 1; }
 // in_range(start, count) -> (byte offset, byte count) of the input those windows read; launch(d_in, count, slot, ctx)
 template <class InRange, class Launch>
 int run_pipeline(mdc_model* m, const char* src, int64_t n, int64_t chunk, bool ramp, float* probs_host, int32_t* labels_host,
-                 uint8_t* flags_host, mdc_iq_window_stats* stats_host, InRange in_range, Launch launch) {
+                 uint8_t* flags_host, void* stats_host, size_t stat_bytes, InRange in_range, Launch launch) {
     HostCtx* c = static_cast<HostCtx*>(m->host_ctx);
     const int C = m->topo.classes;
     const bool direct = is_pinned(src);
@@ -273,7 +274,7 @@ int run_pipeline(mdc_model* m, const char* src, int64_t n, int64_t chunk, bool r
         if (probs_host) std::memcpy(probs_host + s.start * C, s.pin_out, (size_t)s.count * C * 4);
         if (labels_host) std::memcpy(labels_host + s.start, s.pin_out + (size_t)c->out_cap * C * 4, (size_t)s.count * 4);
         if (flags_host) std::memcpy(flags_host + s.start, s.pin_out + (size_t)c->out_cap * (C + 1) * 4, (size_t)s.count);
-        if (stats_host) std::memcpy(stats_host + s.start, s.pin_stats, (size_t)s.count * sizeof(mdc_iq_window_stats));
+        if (stats_host) std::memcpy(static_cast<char*>(stats_host) + (size_t)s.start * stat_bytes, s.pin_stats, (size_t)s.count * stat_bytes);
         s.busy = false;
         return MDC_OK;
     };
@@ -313,7 +314,7 @@ int run_pipeline(mdc_model* m, const char* src, int64_t n, int64_t chunk, bool r
         if (e == hipSuccess && probs_host) e = hipMemcpyAsync(s.pin_out, s.d_probs, (size_t)count * C * 4, hipMemcpyDeviceToHost, c->out_s);
         if (e == hipSuccess && labels_host) e = hipMemcpyAsync(s.pin_out + (size_t)c->out_cap * C * 4, s.d_labels, (size_t)count * 4, hipMemcpyDeviceToHost, c->out_s);
         if (e == hipSuccess && flags_host) e = hipMemcpyAsync(s.pin_out + (size_t)c->out_cap * (C + 1) * 4, s.d_flags, (size_t)count, hipMemcpyDeviceToHost, c->out_s);
-        if (e == hipSuccess && stats_host) e = hipMemcpyAsync(s.pin_stats, s.d_stats, (size_t)count * sizeof(mdc_iq_window_stats), hipMemcpyDeviceToHost, c->out_s);
+        if (e == hipSuccess && stats_host) e = hipMemcpyAsync(s.pin_stats, s.d_stats, (size_t)count * stat_bytes, hipMemcpyDeviceToHost, c->out_s);
         if (e == hipSuccess) e = hipEventRecord(s.out_done, c->out_s);
         if (e != hipSuccess) { set_error("host path: result copy failed: %s", hipGetErrorString(e)); rc = MDC_EIO; break; }
         s.start = start;
@@ -365,7 +366,7 @@ int predict_host(mdc_model* m, const float* x_host, int64_t n, float* probs_host
     const int64_t chunk = std::min<int64_t>(chunk_frames > 0 ? chunk_frames : default_chunk(n), n);
     if ((rc = ctx_prepare(m, (size_t)chunk * kFrameFloats * 4, chunk)) != MDC_OK) return rc;
     return run_pipeline(
-        m, reinterpret_cast<const char*>(x_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr, nullptr,
+        m, reinterpret_cast<const char*>(x_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr, nullptr, 0,
         [](int64_t start, int64_t count, size_t* off, size_t* bytes) {
             *off = (size_t)start * kFrameFloats * 4;
             *bytes = (size_t)count * kFrameFloats * 4;
@@ -391,7 +392,7 @@ int predict_host_checked(mdc_model* m, const float* x_host, int64_t n, float* pr
     const int64_t chunk = std::min<int64_t>(chunk_frames > 0 ? chunk_frames : default_chunk(n), n);
     if ((rc = ctx_prepare(m, (size_t)chunk * kFrameFloats * 4, chunk)) != MDC_OK) return rc;
     rc = run_pipeline(
-        m, reinterpret_cast<const char*>(x_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nonfinite_host, nullptr,
+        m, reinterpret_cast<const char*>(x_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nonfinite_host, nullptr, 0,
         [](int64_t start, int64_t count, size_t* off, size_t* bytes) {
             *off = (size_t)start * kFrameFloats * 4;
             *bytes = (size_t)count * kFrameFloats * 4;
@@ -425,7 +426,7 @@ int predict_host_iq_u8(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t 
     const size_t in_bytes = (size_t)(2 * hop) * (size_t)(chunk - 1) + 256;
     if ((rc = ctx_prepare(m, in_bytes, chunk)) != MDC_OK) return rc;
     return run_pipeline(
-        m, reinterpret_cast<const char*>(iq_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr, nullptr,
+        m, reinterpret_cast<const char*>(iq_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr, nullptr, 0,
         [hop](int64_t start, int64_t count, size_t* off, size_t* bytes) {
             *off = (size_t)(2 * hop) * (size_t)start;
             *bytes = (size_t)(2 * hop) * (size_t)(count - 1) + 256;
@@ -456,17 +457,75 @@ int predict_host_iq_u8_norm(mdc_model* m, const uint8_t* iq_host, int64_t n, int
     if ((rc = ctx_prepare(m, in_bytes, chunk)) != MDC_OK) return rc;
     if ((rc = ctx_prepare_norm(m, chunk)) != MDC_OK) return rc;
     return run_pipeline(
-        m, reinterpret_cast<const char*>(iq_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr, stats_host,
+        m, reinterpret_cast<const char*>(iq_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr, stats_host, sizeof(mdc_iq_window_stats),
         [hop](int64_t start, int64_t count, size_t* off, size_t* bytes) {
             *off = (size_t)(2 * hop) * (size_t)start;
             *bytes = (size_t)(2 * hop) * (size_t)(count - 1) + 256;
         },
         [m, hop, level, flags, stats_host](Slot& s, int64_t count, HostCtx* c) {
-            int r = mdc_iq_u8_windows_norm(reinterpret_cast<const uint8_t*>(s.d_in), count, hop, level, flags, s.d_x, stats_host ? s.d_stats : nullptr,
+            int r = mdc_iq_u8_windows_norm(reinterpret_cast<const uint8_t*>(s.d_in), count, hop, level, flags, s.d_x,
+                                           stats_host ? reinterpret_cast<mdc_iq_window_stats*>(s.d_stats) : nullptr,
                                            c->comp_s);
             if (r != MDC_OK) return r;
             return mdc_forward(m, s.d_x, count, s.d_probs, s.d_labels, nullptr, MDC_TAP_NONE, c->ws, c->ws_bytes, c->comp_s);
         });
+}
+
+// mdc_predict_host_iq / mdc_predict_host_iq_norm: the two drivers above for any MDC_IQ_* format, the slots sized in bytes per
+// pair.  Both go through frames (mdc_iq_windows / mdc_iq_windows_norm into the slot's frame buffer, then mdc_forward): every
+// kind is served.  norm = false: `gain` is the scale, flags and stats_host are unused.
+namespace {
+
+int predict_host_iq_frames(const char* who, bool norm, mdc_model* m, const void* iq_host, int format, int64_t n, int64_t hop, float gain, int flags,
+                           float* probs_host, int32_t* labels_host, mdc_iq_window_stats64* stats_host, int64_t chunk_frames) {
+    int rc = iq_format_check(who, format, hop);
+    if (rc != MDC_OK) return rc;
+    if (norm && (rc = iq_norm_check(who, hop, gain, flags)) != MDC_OK) return rc;
+    if ((rc = check_common(who, m, iq_host, n, chunk_frames)) != MDC_OK) return rc;
+    if (n == 0) return MDC_OK;
+    const size_t pair = (size_t)iq_pair_bytes(format);
+    std::lock_guard<std::mutex> g(m->host_mu);
+    DeviceScope dev(m->device);
+    if (!dev.ok) { set_error("%s: cannot select device %d", who, m->device); return MDC_EIO; }
+    int64_t chunk = std::min<int64_t>(chunk_frames > 0 ? chunk_frames : default_chunk(n), n);
+    if (chunk_frames <= 0) {      // default: a slot's frames are within 64 MiB already (default_chunk); so are its samples, however large the hop
+        const int64_t fit = ((kDefaultChunkFrames * kFrameFloats * 4) - 128 * (int64_t)pair) / ((int64_t)pair * hop) + 1;
+        chunk = std::max<int64_t>(1, std::min(chunk, fit));
+    }
+    const size_t in_bytes = pair * (size_t)hop * (size_t)(chunk - 1) + 128 * pair;
+    if ((rc = ctx_prepare(m, in_bytes, chunk)) != MDC_OK) return rc;
+    if ((rc = ctx_prepare_norm(m, chunk)) != MDC_OK) return rc;
+    return run_pipeline(
+        m, static_cast<const char*>(iq_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr, stats_host,
+        sizeof(mdc_iq_window_stats64),
+        [hop, pair](int64_t start, int64_t count, size_t* off, size_t* bytes) {
+            *off = pair * (size_t)hop * (size_t)start;
+            *bytes = pair * (size_t)hop * (size_t)(count - 1) + 128 * pair;
+        },
+        [m, norm, format, hop, gain, flags, stats_host](Slot& s, int64_t count, HostCtx* c) {
+            int r = norm ? mdc_iq_windows_norm(s.d_in, format, count, hop, gain, flags, s.d_x,
+                                               stats_host ? reinterpret_cast<mdc_iq_window_stats64*>(s.d_stats) : nullptr, c->comp_s)
+                         : mdc_iq_windows(s.d_in, format, count, hop, gain, s.d_x, c->comp_s);
+            if (r != MDC_OK) return r;
+            return mdc_forward(m, s.d_x, count, s.d_probs, s.d_labels, nullptr, MDC_TAP_NONE, c->ws, c->ws_bytes, c->comp_s);
+        });
+}
+
+}  // namespace
+
+int predict_host_iq(mdc_model* m, const void* iq_host, int format, int64_t n, int64_t hop, float scale, float* probs_host, int32_t* labels_host,
+                    int64_t chunk_frames) {
+    // unsigned bytes where the forward kernels read them themselves: the same results (mdc_forward_iq_u8 is bit-identical to
+    // mdc_iq_u8_windows + mdc_forward) without the frame buffer
+    if (format == MDC_IQ_CU8 && m && m->topo.kind != MDC_KIND_CNNPY)
+        return predict_host_iq_u8(m, static_cast<const uint8_t*>(iq_host), n, hop, scale, probs_host, labels_host, chunk_frames);
+    return predict_host_iq_frames("mdc_predict_host_iq", false, m, iq_host, format, n, hop, scale, 0, probs_host, labels_host, nullptr, chunk_frames);
+}
+
+int predict_host_iq_norm(mdc_model* m, const void* iq_host, int format, int64_t n, int64_t hop, float level, int flags, float* probs_host,
+                         int32_t* labels_host, mdc_iq_window_stats64* stats_host, int64_t chunk_frames) {
+    return predict_host_iq_frames("mdc_predict_host_iq_norm", true, m, iq_host, format, n, hop, level, flags, probs_host, labels_host, stats_host,
+                                  chunk_frames);
 }
 
 }  // namespace mdc

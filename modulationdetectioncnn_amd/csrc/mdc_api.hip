@@ -469,6 +469,17 @@ int mdc_predict_host_iq_u8(mdc_model* m, const uint8_t* iq_host, int64_t n, int6
     return guarded("mdc_predict_host_iq_u8", [&]() -> int { return predict_host_iq_u8(m, iq_host, n, hop, scale, probs_host, labels_host, chunk_frames); });
 }
 
+int mdc_predict_host_iq(mdc_model* m, const void* iq_host, int format, int64_t n, int64_t hop, float scale, float* probs_host,
+                        int32_t* labels_host, int64_t chunk_frames) {
+    return guarded("mdc_predict_host_iq", [&]() -> int { return predict_host_iq(m, iq_host, format, n, hop, scale, probs_host, labels_host, chunk_frames); });
+}
+
+int mdc_predict_host_iq_norm(mdc_model* m, const void* iq_host, int format, int64_t n, int64_t hop, float level, int flags, float* probs_host,
+                             int32_t* labels_host, mdc_iq_window_stats64* stats64_host, int64_t chunk_frames) {
+    return guarded("mdc_predict_host_iq_norm", [&]() -> int {
+        return predict_host_iq_norm(m, iq_host, format, n, hop, level, flags, probs_host, labels_host, stats64_host, chunk_frames); });
+}
+
 int mdc_predict_host_iq_u8_norm(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t hop, float level, int flags, float* probs_host,
                                 int32_t* labels_host, mdc_iq_window_stats* stats_host, int64_t chunk_frames) {
     return guarded("mdc_predict_host_iq_u8_norm", [&]() -> int {

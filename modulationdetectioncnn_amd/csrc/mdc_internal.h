@@ -200,6 +200,10 @@ int predict_host_iq_u8(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t 
                        int64_t chunk_frames);
 int predict_host_iq_u8_norm(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t hop, float level, int flags, float* probs_host,
                             int32_t* labels_host, mdc_iq_window_stats* stats_host, int64_t chunk_frames);
+int predict_host_iq(mdc_model* m, const void* iq_host, int format, int64_t n, int64_t hop, float scale, float* probs_host, int32_t* labels_host,
+                    int64_t chunk_frames);
+int predict_host_iq_norm(mdc_model* m, const void* iq_host, int format, int64_t n, int64_t hop, float level, int flags, float* probs_host,
+                         int32_t* labels_host, mdc_iq_window_stats64* stats_host, int64_t chunk_frames);
 void host_ctx_free(mdc_model* m);
 
 // ---- deployed (T1/T2): deployed.hip -------------------------------------------------
@@ -226,6 +230,12 @@ int iq_u8_launch(const uint8_t* iq, int64_t n, int64_t hop, float scale, float* 
 int iq_norm_check(const char* who, int64_t hop, float level, int flags);      // mdc_api.hip
 // iq_norm.hip: mdc_iq_u8_windows_norm behind its argument checks (x or stats may be NULL, not both)
 int iq_norm_launch(const uint8_t* iq, int64_t n, int64_t hop, float level, int flags, float* x, mdc_iq_window_stats* stats, hipStream_t s);
+// iq_formats.hip: mdc_iq_windows / mdc_iq_windows_norm behind their argument checks (MDC_IQ_CU8 frames: the two launchers above)
+int iq_pair_bytes(int format);      // 2 / 2 / 4; 0 for an unknown format
+int iq_format_check(const char* who, int format, int64_t hop);
+int iq_fmt_windows_launch(const void* iq, int format, int64_t n, int64_t hop, float scale, float* x, hipStream_t s);
+int iq_fmt_norm_launch(const void* iq, int format, int64_t n, int64_t hop, float level, int flags, float* x, mdc_iq_window_stats64* stats,
+                       hipStream_t s);
 // flags[i] = 1 iff frame i of x holds a NaN / +-Inf sample (else 0), *count += their number (count may be NULL); poison: the
 // flagged frames' probability rows become NaN and their labels 0 (probs / labels may be NULL).  mdc_forward_checked.
 int nonfinite_launch(const float* x, int64_t n, uint8_t* flags, int64_t* count, float* probs, int32_t* labels, int classes, bool poison,

@@ -14,18 +14,20 @@ DEFAULT_SCALE = 1.0 / 127.5
 HOP_FRAME = 128
 
 
-def window_count(nbytes: int, hop: int = HOP_FRAME) -> int:
-    """Windows of 128 (I,Q) pairs, `hop` pairs apart, that fit a capture of nbytes bytes.  hop = 128 (disjoint frames)
-    keeps the strict rule of the frame format: a trailing partial frame is an error."""
+def window_count(nbytes: int, hop: int = HOP_FRAME, pair_bytes: int = 2) -> int:
+    """Windows of 128 (I,Q) pairs, `hop` pairs apart, that fit a capture of nbytes bytes (pair_bytes per pair: 2 for the 8-bit
+    formats, 4 for 16-bit samples).  hop = 128 (disjoint frames) keeps the strict rule of the frame format: a trailing
+    partial frame is an error."""
     if hop < 1:
         raise ValueError("hop must be >= 1 sample pair")
+    frame = 128 * pair_bytes
     if hop == HOP_FRAME:
-        if nbytes % 256:
-            raise ValueError(f"{nbytes} bytes is not a whole number of 256-byte frames")
-        return nbytes // 256
-    if nbytes % 2:
+        if nbytes % frame:
+            raise ValueError(f"{nbytes} bytes is not a whole number of {frame}-byte frames")
+        return nbytes // frame
+    if nbytes % pair_bytes:
         raise ValueError(f"{nbytes} bytes is not a whole number of (I,Q) pairs")
-    pairs = nbytes // 2
+    pairs = nbytes // pair_bytes
     return 0 if pairs < 128 else (pairs - 128) // hop + 1
 
 
@@ -105,29 +107,139 @@ def window_stats_iq_u8(iq, hop: int = HOP_FRAME, remove_dc: bool = True, device=
     return stats_tensor_to_numpy(stats)
 
 
-def window_power_dbfs(stats) -> np.ndarray:
-    """10*log10(E / (128*255)^2) per window: 0 dBFS is a full-scale constant-envelope window, -inf stands for E == 0.
-    stats: IQ_WINDOW_STATS records, or an (n,4) integer array / tensor whose last column is the energy."""
+def window_power_dbfs(stats, sample_format="cu8") -> np.ndarray:
+    """10*log10(E / (128*A)^2) per window (A: the format's full-scale amplitude, 255 for "cu8"): 0 dBFS is a full-scale
+    constant-envelope window, -inf stands for E == 0.  stats: IQ_WINDOW_STATS / IQ_WINDOW_STATS64 records, or an (n,4) integer
+    array / tensor whose last column is the energy (int32 columns hold the 32-bit record's unsigned values)."""
     if hasattr(stats, "cpu"):
         stats = stats.cpu().numpy()
     a = np.asarray(stats)
-    e = (a["energy"] if a.dtype.names else a[..., 3].astype(np.int64) & 0xFFFFFFFF).astype(np.float64)
+    if a.dtype.names:
+        e = a["energy"].astype(np.float64)
+    elif a.dtype.itemsize <= 4:
+        e = (a[..., 3].astype(np.int64) & 0xFFFFFFFF).astype(np.float64)
+    else:
+        e = a[..., 3].astype(np.float64)
     with np.errstate(divide="ignore"):
-        return 10.0 * np.log10(e / FULL_SCALE_ENERGY)
+        return 10.0 * np.log10(e / full_scale_energy(sample_format))
 
 
-def squelch_energy_threshold(squelch_dbfs: float) -> int:
+def squelch_energy_threshold(squelch_dbfs: float, sample_format="cu8") -> int:
     """The smallest energy E whose window_power_dbfs is >= squelch_dbfs: `E < threshold` is the squelch test, in integers, and
-    agrees with comparing the dBFS values themselves (the power is monotone in E; found by bisection on that very formula)."""
+    agrees with comparing the dBFS values themselves (the power is monotone in E; found by bisection on that very formula,
+    over the format's energy range)."""
     sq = float(squelch_dbfs)
     if np.isnan(sq):
         raise ValueError("squelch_dbfs is NaN")
-    lo, hi = 0, 1 << 31      # power(hi) is above every window's; the answer lies in [lo, hi]
-    if not (10.0 * np.log10(hi / FULL_SCALE_ENERGY) >= sq):
+    fmt = sample_format_id(sample_format)
+    full = full_scale_energy(fmt)
+    lo, hi = 0, _ENERGY_CEILING[fmt]      # power(hi) is above every window's; the answer lies in [lo, hi]
+    if not (10.0 * np.log10(hi / full) >= sq):
         return hi
     while lo < hi:
         mid = (lo + hi) // 2
         with np.errstate(divide="ignore"):
-            ok = 10.0 * np.log10(np.float64(mid) / FULL_SCALE_ENERGY) >= sq
+            ok = 10.0 * np.log10(np.float64(mid) / full) >= sq
         lo, hi = (lo, mid) if ok else (mid + 1, hi)
     return lo
+
+
+# ---- any integer sample format (mdc_iq_windows / mdc_iq_windows_norm): unsigned 8-bit, signed 8-bit, signed 16-bit LE ------
+SAMPLE_FORMATS = {"cu8": _cabi.IQ_CU8, "ci8": _cabi.IQ_CI8, "ci16": _cabi.IQ_CI16, "ci16_le": _cabi.IQ_CI16,
+                  "u8": _cabi.IQ_CU8, "i8": _cabi.IQ_CI8, "sc8": _cabi.IQ_CI8, "sc16": _cabi.IQ_CI16, "i16": _cabi.IQ_CI16}
+FULL_SCALE_AMPLITUDE = {_cabi.IQ_CU8: 255, _cabi.IQ_CI8: 128, _cabi.IQ_CI16: 32768}
+DEFAULT_SCALES = {_cabi.IQ_CU8: DEFAULT_SCALE, _cabi.IQ_CI8: 1.0 / 128.0, _cabi.IQ_CI16: 1.0 / 32768.0}
+_ENERGY_CEILING = {_cabi.IQ_CU8: 1 << 31, _cabi.IQ_CI8: 1 << 30, _cabi.IQ_CI16: 1 << 46}      # above 128 * max(sum_sq) of the format
+
+
+def sample_format_id(sample_format) -> int:
+    """"cu8" / "ci8" / "ci16" (SigMF's "ci16_le", UHD's "sc16", ... are aliases), or an MDC_IQ_* value -> the MDC_IQ_* value."""
+    if isinstance(sample_format, str):
+        key = sample_format.lower()
+        if key not in SAMPLE_FORMATS:
+            raise ValueError(f"sample_format must be one of 'cu8', 'ci8', 'ci16' (got {sample_format!r})")
+        return SAMPLE_FORMATS[key]
+    if sample_format in FULL_SCALE_AMPLITUDE:
+        return int(sample_format)
+    raise ValueError(f"unknown sample format {sample_format!r}")
+
+
+def full_scale_energy(sample_format) -> float:
+    """E of a full-scale constant-envelope window: (128*A)^2, the 0 dBFS reference of the format."""
+    return float((128 * FULL_SCALE_AMPLITUDE[sample_format_id(sample_format)]) ** 2)
+
+
+def host_samples(iq, fmt: int) -> np.ndarray:
+    """A numpy capture, flat interleaved or (..., 2), as a flat contiguous array of the format's dtype.  Only the byte order
+    is ever converted (big-endian int16 -> '<i2'); any other dtype is a TypeError."""
+    a = np.asarray(iq)
+    want = _cabi.IQ_SAMPLE_DTYPE[fmt]
+    if a.dtype.kind != want.kind or a.dtype.itemsize != want.itemsize:
+        raise TypeError(f"iq must be {want.name} for this sample format, got {a.dtype}")
+    return np.ascontiguousarray(a.astype(want, copy=False)).reshape(-1)
+
+
+def _device_samples(iq, fmt: int, device=None):
+    import torch
+    want = {_cabi.IQ_CU8: torch.uint8, _cabi.IQ_CI8: torch.int8, _cabi.IQ_CI16: torch.int16}[fmt]
+    t = iq if isinstance(iq, torch.Tensor) else torch.from_numpy(host_samples(iq, fmt))
+    if t.dtype != want:
+        raise TypeError(f"iq must be {want} for this sample format, got {t.dtype}")
+    if not t.is_cuda:
+        t = t.to(device if device is not None else "cuda:0")
+    t = t.contiguous().view(-1)
+    if t.data_ptr() % _cabi.IQ_PAIR_BYTES[fmt]:
+        t = t.clone()       # a view starting inside a pair of a larger buffer: the ABI wants whole (I,Q) pairs
+    return t
+
+
+def stats64_tensor_to_numpy(stats):
+    """The (n,4) int64 device tensor the calls below fill -> a numpy array of _cabi.IQ_WINDOW_STATS64 records."""
+    return stats.cpu().numpy().view(_cabi.IQ_WINDOW_STATS64).reshape(-1)
+
+
+def frames_from_iq(iq, sample_format, scale=None, device=None, hop: int = HOP_FRAME):
+    """frames_from_iq_u8 for any sample format: iq holds interleaved samples of the format's dtype (uint8 / int8 / int16).
+    Returns float32 (n,2,128) on the device, sample * scale ("cu8": (byte - 127.5) * scale); default scale 1/127.5, 1/128,
+    1/32768 (mdc_iq_windows)."""
+    import torch
+    fmt = sample_format_id(sample_format)
+    t = _device_samples(iq, fmt, device)
+    n = window_count(t.numel() * t.element_size(), hop, _cabi.IQ_PAIR_BYTES[fmt])
+    x = torch.empty((n, 2, 128), dtype=torch.float32, device=t.device)
+    with torch.cuda.device(t.device):
+        _cabi.check(_cabi.lib().mdc_iq_windows(t.data_ptr() if n else None, fmt, n, int(hop), float(DEFAULT_SCALES[fmt] if scale is None else scale),
+                                               x.data_ptr() if n else None, torch.cuda.current_stream(t.device).cuda_stream))
+    return x
+
+
+def normalized_frames_from_iq(iq, sample_format, level: float = DEFAULT_LEVEL, remove_dc: bool = True, hop: int = HOP_FRAME, device=None,
+                              return_stats: bool = False):
+    """normalized_frames_from_iq_u8 for any sample format (mdc_iq_windows_norm).  With return_stats also the windows' statistics
+    as an (n,4) int64 device tensor (columns sum_i, sum_q, sum_sq, energy; stats64_tensor_to_numpy names them)."""
+    import torch
+    fmt = sample_format_id(sample_format)
+    t = _device_samples(iq, fmt, device)
+    n = window_count(t.numel() * t.element_size(), hop, _cabi.IQ_PAIR_BYTES[fmt])
+    x = torch.empty((n, 2, 128), dtype=torch.float32, device=t.device)
+    stats = torch.empty((n, 4), dtype=torch.int64, device=t.device) if return_stats else None
+    with torch.cuda.device(t.device):
+        _cabi.check(_cabi.lib().mdc_iq_windows_norm(t.data_ptr() if n else None, fmt, n, int(hop), float(level),
+                                                    _cabi.IQ_REMOVE_DC if remove_dc else 0, x.data_ptr() if n else None,
+                                                    stats.data_ptr() if return_stats and n else None,
+                                                    torch.cuda.current_stream(t.device).cuda_stream))
+    return (x, stats) if return_stats else x
+
+
+def window_stats_iq(iq, sample_format, hop: int = HOP_FRAME, remove_dc: bool = True, device=None):
+    """The statistics alone (no frames are written): a numpy array of _cabi.IQ_WINDOW_STATS64 records, one per window."""
+    import torch
+    fmt = sample_format_id(sample_format)
+    t = _device_samples(iq, fmt, device)
+    n = window_count(t.numel() * t.element_size(), hop, _cabi.IQ_PAIR_BYTES[fmt])
+    stats = torch.empty((n, 4), dtype=torch.int64, device=t.device)
+    if n:
+        with torch.cuda.device(t.device):
+            _cabi.check(_cabi.lib().mdc_iq_windows_norm(t.data_ptr(), fmt, n, int(hop), 1.0, _cabi.IQ_REMOVE_DC if remove_dc else 0, None,
+                                                        stats.data_ptr(), torch.cuda.current_stream(t.device).cuda_stream))
+    return stats64_tensor_to_numpy(stats)

@@ -860,6 +860,91 @@ class VTCNN2:
             return probs, labels, 10.0 * torch.log10(stats[:, 3].to(torch.float64) / FULL_SCALE_ENERGY)
         return probs, labels
 
+    def predict_iq(self, iq, sample_format, scale: Optional[float] = None, batch_size: int = 0, hop: int = 128,
+                   normalize: Optional[str] = None, level: float = 7.8e-3, remove_dc: bool = True, squelch_dbfs: Optional[float] = None,
+                   return_power: bool = False):
+        """predict_iq_u8 for a capture in any integer sample format: sample_format "cu8" (unsigned bytes, RTL-SDR), "ci8"
+        (signed bytes: HackRF) or "ci16" (signed 16-bit little-endian: USRP sc16, SDRplay, bladeRF, Airspy); SigMF's
+        "ci16_le" etc. are aliases.  iq: a numpy array or torch tensor of the format's dtype (uint8 / int8 / int16; a
+        big-endian numpy int16 array is converted, any other dtype is a TypeError), flat interleaved I0,Q0,I1,Q1,... or
+        shaped (..., 2).  Every sample becomes sample * scale (default 1/127.5, 1/128, 1/32768; "cu8": (byte - 127.5) * scale),
+        or, with normalize="rms", each window is brought to complex rms `level` (mdc_iq_windows_norm, include/mdc.h).
+        Windows, hop, batch_size, squelch_dbfs (0 dBFS = a full-scale constant envelope OF THE FORMAT) and return_power are
+        predict_iq_u8's; "cu8" returns bit for bit what predict_iq_u8 returns.  A device tensor runs chunk by chunk through
+        mdc_iq_windows(_norm) + mdc_forward on torch's current stream, a numpy array through mdc_predict_host_iq(_norm);
+        every kind of net."""
+        torch = _torch()
+        from . import frontend as F
+        fmt = F.sample_format_id(sample_format)
+        as_numpy = not isinstance(iq, torch.Tensor)
+        if as_numpy:
+            iq = F.host_samples(iq, fmt)
+        elif iq.dtype != {_cabi.IQ_CU8: torch.uint8, _cabi.IQ_CI8: torch.int8, _cabi.IQ_CI16: torch.int16}[fmt]:
+            raise TypeError(f"iq must be {_cabi.IQ_SAMPLE_DTYPE[fmt].name} for sample_format {sample_format!r}, got {iq.dtype}")
+        if fmt == _cabi.IQ_CU8:
+            return self.predict_iq_u8(iq, scale, batch_size=batch_size, hop=hop, normalize=normalize, level=level, remove_dc=remove_dc,
+                                      squelch_dbfs=squelch_dbfs, return_power=return_power)
+        norm = normalize is not None
+        if norm:
+            if normalize != "rms":
+                raise ValueError(f"normalize must be None or 'rms'; got {normalize!r}")
+            if scale is not None:
+                raise ValueError("scale= and normalize='rms' cannot be combined: the normalised path scales each window itself")
+            gain = float(level)
+            if not (gain > 0.0 and np.isfinite(gain)):
+                raise ValueError("level must be finite and > 0")
+        else:
+            if squelch_dbfs is not None or return_power:
+                raise ValueError("squelch_dbfs and return_power need normalize='rms' (the plain path computes no window power)")
+            gain = F.DEFAULT_SCALES[fmt] if scale is None else float(scale)
+        flags = _cabi.IQ_REMOVE_DC if remove_dc else 0
+        want_stats = squelch_dbfs is not None or return_power
+        floor = F.squelch_energy_threshold(squelch_dbfs, fmt) if squelch_dbfs is not None else 0
+        pair, Cn = _cabi.IQ_PAIR_BYTES[fmt], self.topology.classes
+        L = self._lib()
+        if as_numpy:      # host samples: the library's streaming driver
+            n = F.window_count(iq.nbytes, hop, pair)
+            probs, labels = np.empty((n, Cn), np.float32), np.empty((n,), np.int32)
+            if not norm:
+                self._check(L.mdc_predict_host_iq(self._engine(), iq.ctypes.data, fmt, n, int(hop), gain, probs.ctypes.data, labels.ctypes.data,
+                                                  self._host_chunk(batch_size)))
+                return probs, labels
+            stats = np.empty((n,), _cabi.IQ_WINDOW_STATS64) if want_stats else None
+            self._check(L.mdc_predict_host_iq_norm(self._engine(), iq.ctypes.data, fmt, n, int(hop), gain, flags, probs.ctypes.data,
+                                                   labels.ctypes.data, stats.ctypes.data if want_stats else None, self._host_chunk(batch_size)))
+            if squelch_dbfs is not None:
+                labels[stats["energy"] < np.uint64(floor)] = -1
+            return (probs, labels, F.window_power_dbfs(stats, fmt)) if return_power else (probs, labels)
+        t = iq.to(f"cuda:{self.device_index}").contiguous().view(-1)
+        n = F.window_count(t.numel() * t.element_size(), hop, pair)
+        if t.data_ptr() % pair:
+            t = t.clone()       # a view into a larger buffer starting inside a pair: the ABI wants whole (I,Q) pairs
+        probs = torch.empty((n, Cn), dtype=torch.float32, device=t.device)
+        labels = torch.empty((n,), dtype=torch.int32, device=t.device)
+        stats = torch.empty((n, 4), dtype=torch.int64, device=t.device) if want_stats else None
+        if n:
+            h = self._engine()
+            chunk = max(1, min(int(batch_size) if batch_size else self.default_chunk, n))
+            with torch.cuda.device(t.device):
+                stream = torch.cuda.current_stream(t.device).cuda_stream
+                ws, ws_bytes = self._workspace(chunk, stream)
+                x = torch.empty((chunk, 2, 128), dtype=torch.float32, device=t.device)      # one chunk of frames, reused in stream order
+                for s0 in range(0, n, chunk):
+                    m = min(chunk, n - s0)
+                    src = t.data_ptr() + pair * hop * s0
+                    if norm:
+                        self._check(L.mdc_iq_windows_norm(src, fmt, m, hop, gain, flags, x.data_ptr(),
+                                                          (stats.data_ptr() + 32 * s0) if want_stats else None, stream))
+                    else:
+                        self._check(L.mdc_iq_windows(src, fmt, m, hop, gain, x.data_ptr(), stream))
+                    self._check(L.mdc_forward(h, x.data_ptr(), m, probs.data_ptr() + s0 * Cn * 4, labels.data_ptr() + s0 * 4, None,
+                                              _cabi.TAP_NONE, ws.data_ptr() if ws is not None else None, ws_bytes, stream))
+        if squelch_dbfs is not None:
+            labels.masked_fill_(stats[:, 3] < floor, -1)      # (64-bit energies: every E and every floor is below 2^47)
+        if return_power:
+            return probs, labels, 10.0 * torch.log10(stats[:, 3].to(torch.float64) / F.full_scale_energy(fmt))
+        return probs, labels
+
     # ------------------------------------------------------------------ measurement hooks
     def set_profiling(self, on: bool) -> None:
         self._check(self._lib().mdc_set_profiling(self._engine(), int(on)))
