@@ -5,6 +5,12 @@ window, whatever the gain and DC offset of the capture: each window is brought t
 (predict_iq(normalize="rms")), and windows whose power lies below the squelch get label -1.
 
     python examples/classify_capture.py capture.bin --weights tests/golden/weights/convmodrecnets_CNN2_0.5.npz --hop 64 --squelch -35
+A wideband capture -- the signal away from the tuner's centre, the sample rate above the nets' 8 samples per symbol -- is tuned,
+low-pass filtered and decimated on the device first (frontend.ddc, exact integer arithmetic); hop, level and squelch then apply
+to the decimated stream:
+
+    python examples/classify_capture.py capture.bin --format cu8 --rate 2.4e6 --shift-hz -480e3 --decimate 12
+
 Without a capture file it classifies a synthetic one: bursts of tones at three gains with silence between them."""
 import argparse
 import os
@@ -38,6 +44,26 @@ def synthetic_capture(fmt="cu8", seed=1):
     return np.clip(np.rint(iq), lo, hi).astype(DTYPES[fmt]).reshape(-1)
 
 
+def classify(model, iq, fmt, hop=128, level=7.8e-3, squelch=-35.0, shift=0.0, decimate=1):
+    """(probs, labels, dBFS) per window.  shift (cycles per sample, ADDED to the capture) / decimate: the capture is tuned,
+    low-pass filtered (frontend.design_lowpass) and decimated on the device first, and the windows are cut from that stream."""
+    ddc = {}
+    if shift != 0.0 or decimate != 1:
+        from modulationdetectioncnn_amd import frontend
+        ddc = dict(shift=shift, decimate=decimate)
+        ntaps = 8 * decimate        # frontend.design_lowpass's default
+        if decimate == 1:           # a pure frequency shift: one tap of (all but) unit gain
+            ddc["taps"], ntaps = np.array([32767], np.int16), 1
+        if hop == 128:              # disjoint frames want whole frames of the DECIMATED stream: trim the input to what gives them
+            keep = frontend.ddc_out_count(iq.size // 2, ntaps, decimate) // 128 * 128
+            iq = iq[:2 * ((keep - 1) * decimate + ntaps)] if keep else iq[:0]
+        else:
+            iq = iq[:iq.size // 2 * 2]
+    else:
+        iq = iq[:iq.size // 256 * 256] if hop == 128 else iq[:iq.size // 2 * 2]
+    return model.predict_iq(iq, fmt, hop=hop, normalize="rms", level=level, squelch_dbfs=squelch, return_power=True, **ddc)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("capture", nargs="?", help="file of interleaved samples I0 Q0 I1 Q1 ... in --format")
@@ -47,14 +73,17 @@ def main():
     ap.add_argument("--hop", type=int, default=128, help="sample pairs between windows (128: disjoint frames)")
     ap.add_argument("--level", type=float, default=7.8e-3, help="complex rms every window is normalised to")
     ap.add_argument("--squelch", type=float, default=-35.0, help="dBFS below which a window gets label -1")
+    ap.add_argument("--rate", type=float, default=1.0, help="sample rate of the capture in Hz (only scales --shift-hz)")
+    ap.add_argument("--shift-hz", type=float, default=0.0,
+                    help="frequency ADDED to the capture before filtering, in Hz at --rate: a signal at +f0 from the tuner's centre wants -f0")
+    ap.add_argument("--decimate", type=int, default=1, help="keep one sample in this many after the anti-alias low-pass (1..256)")
     a = ap.parse_args()
     iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_capture(a.format)
-    iq = iq[:iq.size // 256 * 256] if a.hop == 128 else iq[:iq.size // 2 * 2]
     if a.weights is None:
         model = VTCNN2.synthetic("deployed3")
     else:
         model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
-    probs, labels, dbfs = model.predict_iq(iq, a.format, hop=a.hop, normalize="rms", level=a.level, squelch_dbfs=a.squelch, return_power=True)
+    probs, labels, dbfs = classify(model, iq, a.format, hop=a.hop, level=a.level, squelch=a.squelch, shift=a.shift_hz / a.rate, decimate=a.decimate)
     print(f"{labels.size} windows, {int((labels < 0).sum())} below {a.squelch} dBFS")
     for k in np.unique(labels):
         sel = labels == k

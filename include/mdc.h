@@ -51,7 +51,9 @@ extern "C" {
                                   mdc_forward_checked / mdc_predict_host_checked, MDC_NONFINITE_* (non-finite frames);
                                   mdc_iq_u8_windows_norm / mdc_predict_host_iq_u8_norm (level-normalised raw I/Q);
                                   mdc_iq_windows / mdc_iq_windows_norm / mdc_predict_host_iq / mdc_predict_host_iq_norm
-                                  (signed 8- and 16-bit sample formats, MDC_IQ_*, mdc_iq_window_stats64) */
+                                  (signed 8- and 16-bit sample formats, MDC_IQ_*, mdc_iq_window_stats64);
+                                  mdc_iq_ddc / mdc_iq_ddc_out_count / mdc_iq_ddc_nco_table (frequency shift, low-pass and
+                                  decimation of a raw capture, exact integers) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -348,6 +350,39 @@ typedef struct mdc_iq_window_stats64 {   /* 32 B */
 MDC_API int mdc_iq_windows(const void* iq_dev, int format, int64_t n, int64_t hop, float scale, float* x_dev, void* hip_stream);
 MDC_API int mdc_iq_windows_norm(const void* iq_dev, int format, int64_t n, int64_t hop, float level, int flags,
                            float* x_dev, mdc_iq_window_stats64* stats64_dev, void* hip_stream);
+
+/* ---- digital down-converter: frequency shift, low-pass, decimate (additive in ABI 5) ---------------------------------------
+ * A capture comes off the radio at its own rate and with the signal at some offset from the tuner's centre; the nets want
+ * 8 samples per symbol at 0 Hz.  mdc_iq_ddc does what lies between, on the device, in EXACT integer arithmetic: the output is
+ * the same bits on every machine (the numpy int64 restatement is tests/iq_ddc_ref.py) and is an ordinary MDC_IQ_CI16 stream
+ * for mdc_iq_windows / mdc_iq_windows_norm.  Normatively, for the pairs_in input pairs (I_n, Q_n), n counted from iq_dev:
+ *   widening   to 16-bit full scale: MDC_IQ_CU8 (2*byte - 255)*128, MDC_IQ_CI8 s*256, MDC_IQ_CI16 s  (|.| <= 32768; 0 dBFS
+ *              stays 0 dBFS)
+ *   oscillator phi_n = (phase0 + n*phase_step) mod 2^32; k = phi_n >> 20 indexes a table of 4096 int16 pairs
+ *              c_k = rint(32767 cos(2 pi k / 4096)), s_k = rint(32767 sin(2 pi k / 4096))  (the table itself:
+ *              mdc_iq_ddc_nco_table).  The mixer multiplies by e^{+j 2 pi phi / 2^32}: phase_step / 2^32 cycles per sample are
+ *              ADDED to every component; a signal at +f0 comes to 0 with a step of -f0.  The 12-bit table's spurs lie near
+ *              -72 dBc.
+ *   mixer      m_re = (I c - Q s + 32768) >> 16,  m_im = (I s + Q c + 32768) >> 16  (arithmetic shifts: round half up).
+ *              |I c - Q s| <= 2 * 32768 * 32767, + 32768 < 2^31; |m| <= 32767: an int16 holding HALF the product.
+ *   filter     taps h_0 .. h_{T-1}: int16, Q15 (DC gain 1 is a sum of 32768), applied as written (no reversal), with the hard
+ *              precondition sum |h_k| <= 65535.  Output j: acc = sum_k h_k m_{jD+k}, re and im separately;
+ *              |acc| <= 32767 * 65535, + 8192 < 2^31: 32-bit accumulation is exact.
+ *              out = clamp((acc + 8192) >> 14, -32768, 32767): the shift restores the mixer's halving.
+ *   output     n_out = pairs_in >= T ? (pairs_in - T) / D + 1 : 0 int16 pairs: a "valid" convolution, no invented edge
+ *              samples.  The filter's group delay, (T-1)/2 input pairs for symmetric taps, is not compensated.
+ * 1 <= decimate D <= 256, 1 <= ntaps T <= 1024.  A capture processed in pieces gives the same bits as in one call when piece
+ * two starts at input pair a = (a multiple of D) with phase0 + a*phase_step and the pieces overlap by T - D pairs.
+ * taps_host is read (and validated) during the call and travels with the launch: it may be freed on return, and nothing is
+ * copied that would need a synchronisation.  iq_dev is aligned to one pair (2 / 2 / 4 bytes), out_dev to 4 bytes; n_out must
+ * equal mdc_iq_ddc_out_count.  Every argument error is MDC_EINVAL before any device call.  n_out == 0 is MDC_OK.  The call only
+ * enqueues on hip_stream (no synchronisation, no allocation: capturable in a hipGraph) and runs on the current device.
+ * mdc_iq_ddc_out_count returns n_out, or a negative MDC_EINVAL; mdc_iq_ddc_nco_table writes the 4096 (cos, sin) pairs and
+ * needs no device. */
+MDC_API int64_t mdc_iq_ddc_out_count(int64_t pairs_in, int ntaps, int decimate);
+MDC_API int mdc_iq_ddc_nco_table(int16_t* cos_sin_host /* 4096 x 2 */);
+MDC_API int mdc_iq_ddc(const void* iq_dev, int format, int64_t pairs_in, uint32_t phase0, uint32_t phase_step, int decimate,
+                       const int16_t* taps_host, int ntaps, int16_t* out_dev, int64_t n_out, void* hip_stream);
 
 /* test_Y_hat = model.predict(X_test, batch_size=batch_size)  (cnn.py:198, 237) when X_test lies in HOST memory -- a
  * numpy array, or whatever buffer a cgo / JNI / N-API caller holds: the library's own driver in front of mdc_forward.

@@ -1,0 +1,251 @@
+// mdc_iq_ddc -- tune, low-pass and decimate a wideband integer I/Q capture on the device, in exact integer arithmetic
+// (include/mdc.h, "digital down-converter"; the numpy int64 restatement is tests/iq_ddc_ref.py).  One pass over the capture:
+//
+//   tile      the capture's outputs are cut into tiles of `tile_out` = (kDdcTilePairs - T) / D + 1 outputs: such a tile reads
+//             (tile_out - 1) D + T <= kDdcTilePairs input pairs, its own D tile_out and the T - D pairs of halo.  Work-groups
+//             stride over the tiles (grid cap kDdcGridCap).
+//   mix       each thread takes four adjacent pairs at a time (one unaligned 8- or 16-byte vector load; the capture's last,
+//             partial quads pair by pair with bounds), widens them to 16-bit full scale, reads the oscillator word of
+//             phi_n = phase0 + n step (mod 2^32: the low word of the 64-bit n suffices) from the table's copy in LDS, and
+//             writes m = x e^{j phi} / 2 as int16 into two PLANAR LDS images (re, im): adjacent samples share a dword.
+//   filter    one lane per output j: acc += dot2(m[jD + 2i], m[jD + 2i + 1]; h[2i], h[2i + 1]) with the packed 16-bit dot
+//             product (v_dot2c_i32_i16), the tap pairs uniform over the wave -- they are kernel ARGUMENTS (2 KiB by value: no
+//             copy to wait for, nothing to allocate, and the compiler reads them with scalar loads), zero-padded to whole
+//             groups of 8 dwords.  T odd: the last pair's second tap is that padding.  jD odd (only possible for odd D: the
+//             ODD instantiations): the output's first sample is the HIGH half of its dword; the lane then forms each operand
+//             from two neighbouring dwords with v_alignbit (shift 16; lanes with even jD shift by 0), the taps stay as they are.
+//   LDS       lane j starts at dword j D / 2: for D = 64 every lane of a wave would sit on ONE bank.  The images therefore skip
+//             one dword after every 32 (slot(i) = i + i / 32): a stride of 32 dwords becomes 33.
+// Everything the filter reads beyond the tile's last needed sample (the taps' zero padding times it) is still written by the
+// mix step -- zeros beyond the capture -- so the result never depends on stale LDS.  All sums are the exact integers of the
+// definition: |I c - Q s| + 32768 < 2^31, |acc| <= 32767 sum|h| <= 32767 * 65535, |acc| + 8192 < 2^31 (int32 wraps nowhere,
+// and a dot2 without clamp is plain modular arithmetic in any case).
+// The call only enqueues; vector memory for every store.
+#include "mdc_internal.h"
+
+namespace mdc {
+
+namespace {
+
+constexpr int kDdcThreads = 256;
+constexpr int kDdcTilePairs = 8192;      // input pairs a tile spans at most: (tile_out - 1) D + T
+constexpr int kDdcPadPairs = 32;         // beyond them: what the zero-padded tap groups (and the ODD look-ahead) still read
+constexpr long kDdcGridCap = 1024;       // work-groups; beyond it the kernel strides (_cabi.DDC_GRID_CAP)
+constexpr int kNcoEntries = 4096;
+constexpr int kMaxTaps = 1024, kMaxDecimate = 256;
+constexpr int kTapGroup = 8;             // tap dwords per step of the filter loop
+
+__host__ __device__ constexpr int lds_slot(int i) { return i + (i >> 5); }
+constexpr int kPlaneDwords = lds_slot((kDdcTilePairs + kDdcPadPairs) / 2) + 1;
+
+__device__ const unsigned d_nco[kNcoEntries] = {
+#include "iq_ddc_nco_table.h"
+};
+const unsigned h_nco[kNcoEntries] = {
+#include "iq_ddc_nco_table.h"
+};
+
+struct DdcTaps { unsigned pk[kMaxTaps / 2]; };      // pk[i] = h[2i] | h[2i+1] << 16, zeros beyond the taps
+
+typedef short short2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ int dot2(unsigned a, unsigned b, int c) {
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b), c, false);
+}
+
+template <int FMT> struct Quad { using type = uint2; static constexpr int kPairBytes = 2; };
+template <> struct Quad<MDC_IQ_CI16> { using type = uint4; static constexpr int kPairBytes = 4; };
+
+template <int FMT> __device__ __forceinline__ int widen(int raw) {      // raw: the byte (CU8) or the signed sample
+    return FMT == MDC_IQ_CU8 ? (2 * raw - 255) * 128 : FMT == MDC_IQ_CI8 ? raw * 256 : raw;
+}
+
+// the widened samples of pairs n .. n+3 (I[e], Q[e]); pairs at or beyond `pairs` read nothing and are zero
+template <int FMT>
+__device__ __forceinline__ void load_quad(const unsigned char* __restrict__ iq, long n, long pairs, int (&I)[4], int (&Q)[4]) {
+    constexpr int kPB = Quad<FMT>::kPairBytes;
+    if (n + 4 <= pairs) {
+        typename Quad<FMT>::type w;
+        __builtin_memcpy(&w, iq + n * kPB, sizeof(w));
+        if constexpr (FMT == MDC_IQ_CI16) {
+            const unsigned v[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { I[e] = (int)(short)(v[e] & 0xFFFFu); Q[e] = (int)(short)(v[e] >> 16); }
+        } else {
+            const unsigned v[2] = {w.x, w.y};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned bi = (v[e >> 1] >> (16 * (e & 1))) & 0xFFu, bq = (v[e >> 1] >> (16 * (e & 1) + 8)) & 0xFFu;
+                I[e] = widen<FMT>(FMT == MDC_IQ_CU8 ? (int)bi : (int)(signed char)bi);
+                Q[e] = widen<FMT>(FMT == MDC_IQ_CU8 ? (int)bq : (int)(signed char)bq);
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        I[e] = Q[e] = 0;
+        if (n + e < pairs) {
+            const unsigned char* p = iq + (n + e) * kPB;
+            if constexpr (FMT == MDC_IQ_CI16) {
+                unsigned v;
+                __builtin_memcpy(&v, p, 4);
+                I[e] = (int)(short)(v & 0xFFFFu);
+                Q[e] = (int)(short)(v >> 16);
+            } else {
+                I[e] = widen<FMT>(FMT == MDC_IQ_CU8 ? (int)p[0] : (int)(signed char)p[0]);
+                Q[e] = widen<FMT>(FMT == MDC_IQ_CU8 ? (int)p[1] : (int)(signed char)p[1]);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ int sat16(int v) { return v < -32768 ? -32768 : v > 32767 ? 32767 : v; }
+
+template <int FMT, bool ODD>
+__global__ __launch_bounds__(kDdcThreads) void iq_ddc_kernel(const unsigned char* __restrict__ iq, long pairs, unsigned phase0, unsigned step,
+                                                             int D, int ngroups, int tile_out, long n_out, long ntiles,
+                                                             unsigned* __restrict__ out, const DdcTaps taps) {
+    __shared__ unsigned lds[kNcoEntries + 2 * kPlaneDwords];
+    unsigned* nco = lds;
+    unsigned* re = lds + kNcoEntries;
+    unsigned* im = re + kPlaneDwords;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < kNcoEntries; i += kDdcThreads) nco[i] = d_nco[i];
+
+    for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const long out0 = t * tile_out, in0 = out0 * D;
+        const long left = n_out - out0;
+        const int nout = left < tile_out ? (int)left : tile_out;
+        // local pairs the filter reads: the last output's start, its tap groups, one more dword for the ODD look-ahead
+        const int span = (nout - 1) * D + 2 * kTapGroup * ngroups + 2;      // <= kDdcTilePairs + 17
+        const int quads = (span + 3) >> 2;
+        __syncthreads();      // the table is in place; the previous tile's filter has read its samples
+        for (int q = tid; q < quads; q += kDdcThreads) {
+            const long n = in0 + 4 * (long)q;
+            int I[4], Q[4], mr[4], mi[4];
+            load_quad<FMT>(iq, n, pairs, I, Q);
+            const unsigned phi = phase0 + (unsigned)(unsigned long)n * step;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned cs = nco[(phi + (unsigned)e * step) >> 20];
+                const int c = (int)(short)(cs & 0xFFFFu), s = (int)(short)(cs >> 16);
+                mr[e] = (I[e] * c - Q[e] * s + 32768) >> 16;
+                mi[e] = (I[e] * s + Q[e] * c + 32768) >> 16;
+            }
+            const int a = lds_slot(2 * q), b = lds_slot(2 * q + 1);
+            re[a] = ((unsigned)mr[0] & 0xFFFFu) | ((unsigned)mr[1] << 16);
+            re[b] = ((unsigned)mr[2] & 0xFFFFu) | ((unsigned)mr[3] << 16);
+            im[a] = ((unsigned)mi[0] & 0xFFFFu) | ((unsigned)mi[1] << 16);
+            im[b] = ((unsigned)mi[2] & 0xFFFFu) | ((unsigned)mi[3] << 16);
+        }
+        __syncthreads();
+        for (int j = tid; j < nout; j += kDdcThreads) {
+            const int start = j * D, base = start >> 1;
+            const unsigned sh = (unsigned)(start & 1) << 4;
+            int ar = 0, ai = 0;
+            unsigned cr = 0, ci = 0;
+            if (ODD) { cr = re[lds_slot(base)]; ci = im[lds_slot(base)]; }
+            for (int g = 0; g < ngroups; ++g) {
+#pragma unroll
+                for (int u = 0; u < kTapGroup; ++u) {
+                    const unsigned tp = taps.pk[kTapGroup * g + u];
+                    unsigned wr, wi;
+                    if (ODD) {
+                        const int idx = lds_slot(base + kTapGroup * g + u + 1);
+                        const unsigned nr = re[idx], ni = im[idx];
+                        wr = __builtin_amdgcn_alignbit(nr, cr, sh);
+                        wi = __builtin_amdgcn_alignbit(ni, ci, sh);
+                        cr = nr;
+                        ci = ni;
+                    } else {
+                        const int idx = lds_slot(base + kTapGroup * g + u);
+                        wr = re[idx];
+                        wi = im[idx];
+                    }
+                    ar = dot2(wr, tp, ar);
+                    ai = dot2(wi, tp, ai);
+                }
+            }
+            const int r = sat16((ar + 8192) >> 14), i = sat16((ai + 8192) >> 14);
+            out[out0 + j] = ((unsigned)r & 0xFFFFu) | ((unsigned)i << 16);
+        }
+    }
+}
+
+template <int FMT>
+int ddc_launch(const unsigned char* iq, int64_t pairs, uint32_t phase0, uint32_t step, int D, int ngroups, int tile_out, int64_t n_out,
+               int16_t* out, const DdcTaps& taps, hipStream_t s) {
+    const long ntiles = (n_out + tile_out - 1) / tile_out;
+    const dim3 g((unsigned)(ntiles < kDdcGridCap ? ntiles : kDdcGridCap)), b(kDdcThreads);
+    unsigned* o = reinterpret_cast<unsigned*>(out);
+    if (D & 1) hipLaunchKernelGGL((iq_ddc_kernel<FMT, true>), g, b, 0, s, iq, (long)pairs, phase0, step, D, ngroups, tile_out, (long)n_out, ntiles, o, taps);
+    else       hipLaunchKernelGGL((iq_ddc_kernel<FMT, false>), g, b, 0, s, iq, (long)pairs, phase0, step, D, ngroups, tile_out, (long)n_out, ntiles, o, taps);
+    MDC_HIP(hipGetLastError());
+    return MDC_OK;
+}
+
+int64_t ddc_out_count(int64_t pairs, int ntaps, int decimate) { return pairs >= ntaps ? (pairs - ntaps) / decimate + 1 : 0; }
+
+int ddc_shape_check(const char* who, int64_t pairs, int ntaps, int decimate) {
+    if (decimate < 1 || decimate > kMaxDecimate) { set_error("%s: decimate must be in 1..%d (got %d)", who, kMaxDecimate, decimate); return MDC_EINVAL; }
+    if (ntaps < 1 || ntaps > kMaxTaps) { set_error("%s: ntaps must be in 1..%d (got %d)", who, kMaxTaps, ntaps); return MDC_EINVAL; }
+    if (pairs < 0) { set_error("%s: negative pair count", who); return MDC_EINVAL; }
+    return MDC_OK;
+}
+
+}  // namespace
+
+}  // namespace mdc
+
+using namespace mdc;
+
+int64_t mdc_iq_ddc_out_count(int64_t pairs_in, int ntaps, int decimate) {
+    const int rc = ddc_shape_check("mdc_iq_ddc_out_count", pairs_in, ntaps, decimate);
+    return rc != MDC_OK ? (int64_t)rc : ddc_out_count(pairs_in, ntaps, decimate);
+}
+
+int mdc_iq_ddc_nco_table(int16_t* cos_sin_host) {
+    if (!cos_sin_host) { set_error("mdc_iq_ddc_nco_table: null buffer"); return MDC_EINVAL; }
+    for (int k = 0; k < kNcoEntries; ++k) {
+        cos_sin_host[2 * k] = (int16_t)(h_nco[k] & 0xFFFFu);
+        cos_sin_host[2 * k + 1] = (int16_t)(h_nco[k] >> 16);
+    }
+    return MDC_OK;
+}
+
+int mdc_iq_ddc(const void* iq_dev, int format, int64_t pairs_in, uint32_t phase0, uint32_t phase_step, int decimate, const int16_t* taps_host,
+               int ntaps, int16_t* out_dev, int64_t n_out, void* hip_stream) {
+    const int pair_bytes = iq_pair_bytes(format);
+    if (pair_bytes == 0) { set_error("mdc_iq_ddc: unknown sample format %d (MDC_IQ_CU8, MDC_IQ_CI8, MDC_IQ_CI16)", format); return MDC_EINVAL; }
+    const int rc = ddc_shape_check("mdc_iq_ddc", pairs_in, ntaps, decimate);
+    if (rc != MDC_OK) return rc;
+    if (!taps_host) { set_error("mdc_iq_ddc: null taps"); return MDC_EINVAL; }
+    long abs_sum = 0;
+    for (int k = 0; k < ntaps; ++k) abs_sum += taps_host[k] < 0 ? -(long)taps_host[k] : (long)taps_host[k];
+    if (abs_sum > 65535) {
+        set_error("mdc_iq_ddc: the taps' absolute values sum to %ld; at most 65535 keeps the 32-bit accumulation exact", abs_sum);
+        return MDC_EINVAL;
+    }
+    if (n_out != ddc_out_count(pairs_in, ntaps, decimate)) {
+        set_error("mdc_iq_ddc: n_out is %lld, mdc_iq_ddc_out_count gives %lld", (long long)n_out, (long long)ddc_out_count(pairs_in, ntaps, decimate));
+        return MDC_EINVAL;
+    }
+    if ((reinterpret_cast<uintptr_t>(iq_dev) & (uintptr_t)(pair_bytes - 1)) != 0) {
+        set_error("mdc_iq_ddc: input must start on a whole (I,Q) pair (%d-byte aligned)", pair_bytes);
+        return MDC_EINVAL;
+    }
+    if ((reinterpret_cast<uintptr_t>(out_dev) & 3) != 0) { set_error("mdc_iq_ddc: output must be 4-byte aligned"); return MDC_EINVAL; }
+    if (n_out == 0) return MDC_OK;
+    if (!iq_dev || !out_dev) { set_error("mdc_iq_ddc: null buffer"); return MDC_EINVAL; }
+    DdcTaps taps{};
+    for (int k = 0; k < ntaps; ++k) taps.pk[k >> 1] |= (unsigned)(uint16_t)taps_host[k] << (16 * (k & 1));
+    const int ngroups = ((ntaps + 1) / 2 + kTapGroup - 1) / kTapGroup;
+    const int tile_out = (kDdcTilePairs - ntaps) / decimate + 1;
+    const unsigned char* p = static_cast<const unsigned char*>(iq_dev);
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    return guarded("mdc_iq_ddc", [&]() -> int {
+        if (format == MDC_IQ_CU8) return ddc_launch<MDC_IQ_CU8>(p, pairs_in, phase0, phase_step, decimate, ngroups, tile_out, n_out, out_dev, taps, s);
+        if (format == MDC_IQ_CI8) return ddc_launch<MDC_IQ_CI8>(p, pairs_in, phase0, phase_step, decimate, ngroups, tile_out, n_out, out_dev, taps, s);
+        return ddc_launch<MDC_IQ_CI16>(p, pairs_in, phase0, phase_step, decimate, ngroups, tile_out, n_out, out_dev, taps, s);
+    });
+}

@@ -243,3 +243,89 @@ def window_stats_iq(iq, sample_format, hop: int = HOP_FRAME, remove_dc: bool = T
             _cabi.check(_cabi.lib().mdc_iq_windows_norm(t.data_ptr(), fmt, n, int(hop), 1.0, _cabi.IQ_REMOVE_DC if remove_dc else 0, None,
                                                         stats.data_ptr(), torch.cuda.current_stream(t.device).cuda_stream))
     return stats64_tensor_to_numpy(stats)
+
+
+# ---- digital down-converter (mdc_iq_ddc): frequency shift, low-pass, decimate -- exact integers, on the device -------------
+def phase_step(shift: float) -> int:
+    """shift: the frequency ADDED to every component of the capture, in cycles per input sample, in [-0.5, 0.5] (a signal at
+    +f0 comes to 0 with shift = -f0).  Returns the oscillator's 32-bit step, round(shift * 2^32) mod 2^32."""
+    shift = float(shift)
+    if not -0.5 <= shift <= 0.5:
+        raise ValueError(f"shift must lie in [-0.5, 0.5] cycles per sample (got {shift!r})")
+    return int(round(shift * 2.0 ** 32)) % (1 << 32)
+
+
+def design_lowpass(decimate: int, ntaps=None, cutoff=None, beta: float = 8.0) -> np.ndarray:
+    """The anti-alias filter in front of a decimation by `decimate` >= 2, as int16 Q15 taps for mdc_iq_ddc: a Kaiser-windowed
+    sinc of ntaps taps (default 8 * decimate) whose -6 dB point lies at `cutoff` cycles per input sample (default 0.4 / decimate),
+    normalised to unit sum, rounded to Q15, the centre tap(s) then adjusted so that the taps sum to exactly 32768 (DC gain 1;
+    the taps stay symmetric).  With the defaults, for decimate in {2, 3, 4, 8, 12, 16, 32, 64}: sum |h| <= 40,712 (mdc_iq_ddc
+    wants <= 65,535), droop <= 0.95 dB over |f| <= 0.25 / decimate, and >= 63 dB attenuation for |f| >= 0.75 / decimate --
+    everything that aliases onto |f| <= 0.25 / decimate.  (A signal of 8 samples per symbol AFTER decimation with a root
+    raised cosine pulse occupies |f| <= 0.085 / decimate.)  Group delay: (ntaps - 1) / 2 input samples."""
+    D = int(decimate)
+    if D < 2:
+        raise ValueError("design_lowpass needs decimate >= 2 (a decimation by 1 has nothing to reject: pass explicit taps)")
+    T = 8 * D if ntaps is None else int(ntaps)
+    if not 1 <= T <= _cabi.DDC_MAX_TAPS:
+        raise ValueError(f"ntaps must be in 1..{_cabi.DDC_MAX_TAPS} (got {T})")
+    fc = 0.4 / D if cutoff is None else float(cutoff)
+    if not 0.0 < fc <= 0.5:
+        raise ValueError(f"cutoff must lie in (0, 0.5] cycles per sample (got {fc!r})")
+    k = np.arange(T, dtype=np.float64) - (T - 1) / 2.0
+    h = 2.0 * fc * np.sinc(2.0 * fc * k) * np.kaiser(T, float(beta))
+    q = np.rint(h / h.sum() * 32768.0).astype(np.int64)
+    rest = 32768 - int(q.sum())
+    if T % 2:
+        q[T // 2] += rest
+    else:      # symmetric taps of even length sum to an even number: both centre taps take half of what is missing
+        q[T // 2 - 1] += rest // 2
+        q[T // 2] += rest - rest // 2
+    if np.abs(q).max() > 32767 or int(np.abs(q).sum()) > _cabi.DDC_MAX_TAPS_ABS_SUM:
+        raise ValueError("these parameters give taps outside int16 Q15 / the sum |h| <= 65535 of mdc_iq_ddc")
+    return q.astype(np.int16)
+
+
+def ddc_out_count(pairs_in: int, ntaps: int, decimate: int) -> int:
+    """mdc_iq_ddc_out_count: output pairs of a capture of pairs_in pairs (a "valid" convolution)."""
+    return _cabi.check(_cabi.lib().mdc_iq_ddc_out_count(int(pairs_in), int(ntaps), int(decimate)))
+
+
+def nco_table() -> np.ndarray:
+    """The (4096, 2) int16 (cos, sin) table the device oscillator uses (mdc_iq_ddc_nco_table; needs no GPU)."""
+    t = np.empty((_cabi.DDC_NCO_ENTRIES, 2), np.int16)
+    _cabi.check(_cabi.lib().mdc_iq_ddc_nco_table(t.ctypes.data))
+    return t
+
+
+def ddc(iq, sample_format, shift: float = 0.0, decimate: int = 1, taps=None, phase0: int = 0, device=None):
+    """Tune, low-pass and decimate a capture on the device (mdc_iq_ddc, include/mdc.h: exact integer arithmetic).  iq: as
+    frames_from_iq; shift: the frequency added to the capture, cycles per input sample (phase_step); taps: int16 Q15, applied as
+    written, None = design_lowpass(decimate) -- decimate == 1 needs explicit taps; phase0: the oscillator's 32-bit phase at the
+    capture's first pair.  Returns the (n_out, 2) int16 device tensor of (I, Q) pairs, n_out = (pairs - ntaps) // decimate + 1: an
+    ordinary "ci16" capture for frames_from_iq / normalized_frames_from_iq / VTCNN2.predict_iq.  Enqueues on torch's current
+    stream without synchronising."""
+    import torch
+    fmt = sample_format_id(sample_format)
+    D, step = int(decimate), phase_step(shift)
+    if taps is None:
+        if D == 1:
+            raise ValueError("decimate == 1 needs explicit taps (design_lowpass designs anti-alias filters for decimate >= 2)")
+        taps = design_lowpass(D)
+    h = np.asarray(taps)
+    if h.dtype.kind != "i" or h.ndim != 1:
+        raise TypeError("taps must be a one-dimensional integer array (int16 Q15)")
+    if h.size and (h.min() < -32768 or h.max() > 32767):
+        raise ValueError("taps must fit int16")
+    h = np.ascontiguousarray(h.astype(np.int16))
+    t = _device_samples(iq, fmt, device)
+    pairs = t.numel() * t.element_size() // _cabi.IQ_PAIR_BYTES[fmt]
+    if pairs * _cabi.IQ_PAIR_BYTES[fmt] != t.numel() * t.element_size():
+        raise ValueError("the capture is not a whole number of (I,Q) pairs")
+    L = _cabi.lib()
+    n_out = _cabi.check(L.mdc_iq_ddc_out_count(pairs, h.size, D))
+    out = torch.empty((n_out, 2), dtype=torch.int16, device=t.device)
+    with torch.cuda.device(t.device):
+        _cabi.check(L.mdc_iq_ddc(t.data_ptr() if pairs else None, fmt, pairs, int(phase0) % (1 << 32), step, D, h.ctypes.data, h.size,
+                                 out.data_ptr() if n_out else None, n_out, torch.cuda.current_stream(t.device).cuda_stream))
+    return out
