@@ -11,6 +11,12 @@ to the decimated stream:
 
     python examples/classify_capture.py capture.bin --format cu8 --rate 2.4e6 --shift-hz -480e3 --decimate 12
 
+A rate that no integer brings to 8 samples per symbol is resampled by a rational factor instead (frontend.resample, the same
+exact arithmetic): give the factor as --interpolate L --decimate D, or let --symbol-rate choose it from --rate -- 2.4 MS/s on a
+250 ksym/s signal is 9.6 samples per symbol, and 5/6 makes that 8:
+
+    python examples/classify_capture.py capture.bin --rate 2.4e6 --symbol-rate 250e3 --shift-hz -480e3
+
 Without a capture file it classifies a synthetic one: bursts of tones at three gains with silence between them."""
 import argparse
 import os
@@ -44,10 +50,25 @@ def synthetic_capture(fmt="cu8", seed=1):
     return np.clip(np.rint(iq), lo, hi).astype(DTYPES[fmt]).reshape(-1)
 
 
-def classify(model, iq, fmt, hop=128, level=7.8e-3, squelch=-35.0, shift=0.0, decimate=1):
+def classify(model, iq, fmt, hop=128, level=7.8e-3, squelch=-35.0, shift=0.0, decimate=1, interpolate=1):
     """(probs, labels, dBFS) per window.  shift (cycles per sample, ADDED to the capture) / decimate: the capture is tuned,
-    low-pass filtered (frontend.design_lowpass) and decimated on the device first, and the windows are cut from that stream."""
+    low-pass filtered (frontend.design_lowpass) and decimated on the device first, and the windows are cut from that stream.
+    interpolate != 1: resampled by interpolate / decimate instead (frontend.resample with frontend.design_resampler's taps)."""
     ddc = {}
+    if interpolate != 1:
+        import math
+        from modulationdetectioncnn_amd import frontend
+        g = math.gcd(interpolate, decimate)
+        L, D = interpolate // g, decimate // g
+        if L == 1:                  # an integer decimation after all
+            return classify(model, iq, fmt, hop, level, squelch, shift, D)
+        taps = frontend.design_resampler(L, D)
+        iq = iq[:iq.size // 2 * 2]
+        down = frontend.resample(iq, fmt, shift=shift, interpolate=L, decimate=D, taps=taps, device=f"cuda:{model.device_index}")
+        if hop == 128:              # disjoint frames want whole frames of the RESAMPLED stream
+            down = down[:frontend.resample_out_count(iq.size // 2, taps.size, L, D) // 128 * 128]
+        res = model.predict_iq(down.reshape(-1), "ci16", hop=hop, normalize="rms", level=level, squelch_dbfs=squelch, return_power=True)
+        return tuple(r.cpu().numpy() for r in res)
     if shift != 0.0 or decimate != 1:
         from modulationdetectioncnn_amd import frontend
         ddc = dict(shift=shift, decimate=decimate)
@@ -77,13 +98,22 @@ def main():
     ap.add_argument("--shift-hz", type=float, default=0.0,
                     help="frequency ADDED to the capture before filtering, in Hz at --rate: a signal at +f0 from the tuner's centre wants -f0")
     ap.add_argument("--decimate", type=int, default=1, help="keep one sample in this many after the anti-alias low-pass (1..256)")
+    ap.add_argument("--interpolate", type=int, default=1, help="with --decimate D: resample by this L over D (1..32)")
+    ap.add_argument("--symbol-rate", type=float, default=None,
+                    help="symbols per second of the signal: picks --interpolate / --decimate so that --rate becomes 8 samples per symbol")
     a = ap.parse_args()
+    if a.symbol_rate is not None:
+        from modulationdetectioncnn_amd import frontend
+        a.interpolate, a.decimate, sps = frontend.resample_ratio(a.rate, a.symbol_rate)
+        print(f"{a.rate:g} S/s at {a.symbol_rate:g} sym/s is {a.rate / a.symbol_rate:g} samples per symbol: "
+              f"resampling by {a.interpolate}/{a.decimate} gives {sps:g}")
     iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_capture(a.format)
     if a.weights is None:
         model = VTCNN2.synthetic("deployed3")
     else:
         model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
-    probs, labels, dbfs = classify(model, iq, a.format, hop=a.hop, level=a.level, squelch=a.squelch, shift=a.shift_hz / a.rate, decimate=a.decimate)
+    probs, labels, dbfs = classify(model, iq, a.format, hop=a.hop, level=a.level, squelch=a.squelch, shift=a.shift_hz / a.rate, decimate=a.decimate,
+                                   interpolate=a.interpolate)
     print(f"{labels.size} windows, {int((labels < 0).sum())} below {a.squelch} dBFS")
     for k in np.unique(labels):
         sel = labels == k

@@ -53,7 +53,8 @@ extern "C" {
                                   mdc_iq_windows / mdc_iq_windows_norm / mdc_predict_host_iq / mdc_predict_host_iq_norm
                                   (signed 8- and 16-bit sample formats, MDC_IQ_*, mdc_iq_window_stats64);
                                   mdc_iq_ddc / mdc_iq_ddc_out_count / mdc_iq_ddc_nco_table (frequency shift, low-pass and
-                                  decimation of a raw capture, exact integers) */
+                                  decimation of a raw capture, exact integers);
+                                  mdc_iq_resample / mdc_iq_resample_out_count (the same with a rational factor L/D) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -383,6 +384,36 @@ MDC_API int64_t mdc_iq_ddc_out_count(int64_t pairs_in, int ntaps, int decimate);
 MDC_API int mdc_iq_ddc_nco_table(int16_t* cos_sin_host /* 4096 x 2 */);
 MDC_API int mdc_iq_ddc(const void* iq_dev, int format, int64_t pairs_in, uint32_t phase0, uint32_t phase_step, int decimate,
                        const int16_t* taps_host, int ntaps, int16_t* out_dev, int64_t n_out, void* hip_stream);
+
+/* ---- rational resampler: frequency shift, low-pass, resample by L/D (additive in ABI 5) ------------------------------------
+ * Integer decimation reaches the nets' 8 samples per symbol only when the radio's rate is an integer multiple of 8 x the symbol
+ * rate (2.4 MS/s on 250 ksym/s is 9.6 samples per symbol: 5/6 gives 8).  mdc_iq_resample is mdc_iq_ddc with an interpolation
+ * factor L = interpolate in front of the filter, in the same EXACT integer arithmetic (the numpy int64 restatement is
+ * tests/iq_resample_ref.py).  Normatively, for the pairs_in = P input pairs:
+ *   widening, oscillator, mixer   word for word those of mdc_iq_ddc: m_n (int16, half the product), n = 0 .. P-1; the
+ *              oscillator advances once per INPUT pair.
+ *   zero stuffing   v has length Lv = (P-1) L + 1; v_{nL} = m_n, every other v is 0.  No zeros are invented after the last
+ *              sample.
+ *   filter     prototype taps h_0 .. h_{T-1}: int16, at the INTERPOLATED rate, applied as written.  Output j:
+ *              acc_j = sum_k h_k v_{jD+k}, re and im separately.  Only k = r_j (mod L) contribute, r_j = (-jD) mod L, so
+ *              acc_j = sum_i h_{r_j + iL} m_{ceil(jD/L) + i}: output j uses branch r_j of the polyphase decomposition.  A branch
+ *              without taps (possible when T < L) gives 0.
+ *              Hard precondition: for EVERY branch r, sum_i |h_{r+iL}| <= 65535 (the prototype's sum may be up to L times
+ *              that).  Then |acc| <= 32767 * 65535, + 8192 < 2^31: 32-bit accumulation is exact.  DC gain 1 means every branch
+ *              sums to 32768 (the prototype to 32768 L).
+ *              out = clamp((acc + 8192) >> 14, -32768, 32767), as in mdc_iq_ddc.
+ *   output     n_out = (P >= 1 && Lv >= T) ? (Lv - T) / D + 1 : 0 int16 pairs.
+ * 1 <= interpolate L <= 32, 1 <= decimate D <= 256, 1 <= ntaps T <= 1024, pairs_in <= 2^58; gcd(L, D) need not be 1.  L = 1 is
+ * exactly mdc_iq_ddc: the same bits for the same arguments.  Pieces: the outputs of a prefix of the capture are a prefix of the
+ * outputs; a call on the pairs from a on, with a L = 0 (mod D) and phase0 + a*phase_step, returns the whole call's outputs from
+ * j0 = a L / D on.  Alignment, null and n_out conventions are mdc_iq_ddc's: taps_host is read and validated during the call and
+ * travels with the launch (it may be freed on return); iq_dev is aligned to one pair, out_dev to 4 bytes; n_out must equal
+ * mdc_iq_resample_out_count.  Every argument error is MDC_EINVAL before any device call -- a branch over 65535 names the branch
+ * and its sum.  n_out == 0 is MDC_OK.  The call only enqueues on hip_stream (no synchronisation, no allocation: capturable in a
+ * hipGraph) and runs on the current device.  mdc_iq_resample_out_count returns n_out, or a negative MDC_EINVAL. */
+MDC_API int64_t mdc_iq_resample_out_count(int64_t pairs_in, int ntaps, int interpolate, int decimate);
+MDC_API int mdc_iq_resample(const void* iq_dev, int format, int64_t pairs_in, uint32_t phase0, uint32_t phase_step, int interpolate,
+                            int decimate, const int16_t* taps_host, int ntaps, int16_t* out_dev, int64_t n_out, void* hip_stream);
 
 /* test_Y_hat = model.predict(X_test, batch_size=batch_size)  (cnn.py:198, 237) when X_test lies in HOST memory -- a
  * numpy array, or whatever buffer a cgo / JNI / N-API caller holds: the library's own driver in front of mdc_forward.

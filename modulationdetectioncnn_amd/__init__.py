@@ -6,6 +6,7 @@ from .model import VTCNN2, Model, NonFiniteInputError  # noqa: F401
 from .frontend import frames_from_iq_u8, normalized_frames_from_iq_u8, window_stats_iq_u8, window_power_dbfs  # noqa: F401
 from .frontend import frames_from_iq, normalized_frames_from_iq, window_stats_iq  # noqa: F401
 from .frontend import ddc, design_lowpass, phase_step  # noqa: F401
+from .frontend import design_resampler, resample, resample_ratio  # noqa: F401
 from . import callbacks  # noqa: F401
 
 __all__ = ["Topology", "VTCNN2", "Model", "callbacks", "synthetic_weights", "synthetic_frames", "frames_from_iq_u8", "NonFiniteInputError"]

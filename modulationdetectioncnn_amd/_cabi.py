@@ -35,6 +35,7 @@ EXPORTS = [
     "mdc_iq_u8_windows_norm", "mdc_predict_host_iq_u8_norm",
     "mdc_iq_windows", "mdc_iq_windows_norm", "mdc_predict_host_iq", "mdc_predict_host_iq_norm",
     "mdc_iq_ddc", "mdc_iq_ddc_out_count", "mdc_iq_ddc_nco_table",
+    "mdc_iq_resample", "mdc_iq_resample_out_count",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
@@ -53,6 +54,10 @@ IQ_WINDOW_STATS64 = np.dtype([("sum_i", np.int64), ("sum_q", np.int64), ("sum_sq
 # mdc_iq_ddc: limits of include/mdc.h, and the kernel's tiling (csrc/iq_ddc.hip: kDdcTilePairs, kDdcGridCap) for tests and tools
 DDC_MAX_DECIMATE, DDC_MAX_TAPS, DDC_MAX_TAPS_ABS_SUM, DDC_NCO_ENTRIES = 256, 1024, 65535, 4096
 DDC_TILE_PAIRS, DDC_GRID_CAP = 8192, 1024
+# mdc_iq_resample: limits of include/mdc.h (taps and decimation as the DDC's; the sum |h| bound holds per BRANCH), and the kernel's
+# tiling (csrc/iq_resample.hip): a tile is ((RESAMPLE_TILE_PAIRS - ceil(T / L)) // D) * L outputs, RESAMPLE_GRID_CAP work-groups
+RESAMPLE_MAX_INTERPOLATE, RESAMPLE_MAX_DECIMATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BRANCH_ABS_SUM = 32, 256, 1024, 65535
+RESAMPLE_TILE_PAIRS, RESAMPLE_GRID_CAP = 8192, 1024
 
 
 class MdcTopology(C.Structure):
@@ -128,12 +133,15 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_predict_host_iq", [vp, vp, i32, i64, i64, C.c_float, vp, vp, i64]),
                        ("mdc_predict_host_iq_norm", [vp, vp, i32, i64, i64, C.c_float, i32, vp, vp, vp, i64]),
                        ("mdc_iq_ddc_nco_table", [vp]),
-                       ("mdc_iq_ddc", [vp, i32, i64, C.c_uint32, C.c_uint32, i32, vp, i32, vp, i64, vp])):
+                       ("mdc_iq_ddc", [vp, i32, i64, C.c_uint32, C.c_uint32, i32, vp, i32, vp, i64, vp]),
+                       ("mdc_iq_resample", [vp, i32, i64, C.c_uint32, C.c_uint32, i32, i32, vp, i32, vp, i64, vp])):
         fn = getattr(L, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, i32
     if getattr(L, "mdc_iq_ddc_out_count", None) is not None:
         L.mdc_iq_ddc_out_count.argtypes, L.mdc_iq_ddc_out_count.restype = [i64, i32, i32], i64
+    if getattr(L, "mdc_iq_resample_out_count", None) is not None:
+        L.mdc_iq_resample_out_count.argtypes, L.mdc_iq_resample_out_count.restype = [i64, i32, i32, i32], i64
     fp = C.POINTER(C.c_float)
     L.mdc_trainer_create.argtypes = [C.POINTER(MdcTopology), i32, C.POINTER(vp)]
     L.mdc_trainer_num_layers.argtypes = [vp]

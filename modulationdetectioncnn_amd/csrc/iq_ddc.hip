@@ -20,86 +20,25 @@
 // mix step -- zeros beyond the capture -- so the result never depends on stale LDS.  All sums are the exact integers of the
 // definition: |I c - Q s| + 32768 < 2^31, |acc| <= 32767 sum|h| <= 32767 * 65535, |acc| + 8192 < 2^31 (int32 wraps nowhere,
 // and a dot2 without clamp is plain modular arithmetic in any case).
-// The call only enqueues; vector memory for every store.
-#include "mdc_internal.h"
+// The call only enqueues; vector memory for every store.  The loads, the table and the LDS geometry live in iq_mix.h
+// (mdc_iq_resample shares them).
+#include "iq_mix.h"
 
 namespace mdc {
 
 namespace {
 
-constexpr int kDdcThreads = 256;
-constexpr int kDdcTilePairs = 8192;      // input pairs a tile spans at most: (tile_out - 1) D + T
-constexpr int kDdcPadPairs = 32;         // beyond them: what the zero-padded tap groups (and the ODD look-ahead) still read
+constexpr int kDdcThreads = kIqMixThreads;
+constexpr int kDdcTilePairs = kIqTilePairs;      // input pairs a tile spans at most: (tile_out - 1) D + T
 constexpr long kDdcGridCap = 1024;       // work-groups; beyond it the kernel strides (_cabi.DDC_GRID_CAP)
-constexpr int kNcoEntries = 4096;
 constexpr int kMaxTaps = 1024, kMaxDecimate = 256;
 constexpr int kTapGroup = 8;             // tap dwords per step of the filter loop
 
-__host__ __device__ constexpr int lds_slot(int i) { return i + (i >> 5); }
-constexpr int kPlaneDwords = lds_slot((kDdcTilePairs + kDdcPadPairs) / 2) + 1;
-
-__device__ const unsigned d_nco[kNcoEntries] = {
-#include "iq_ddc_nco_table.h"
-};
 const unsigned h_nco[kNcoEntries] = {
 #include "iq_ddc_nco_table.h"
 };
 
 struct DdcTaps { unsigned pk[kMaxTaps / 2]; };      // pk[i] = h[2i] | h[2i+1] << 16, zeros beyond the taps
-
-typedef short short2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int dot2(unsigned a, unsigned b, int c) {
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b), c, false);
-}
-
-template <int FMT> struct Quad { using type = uint2; static constexpr int kPairBytes = 2; };
-template <> struct Quad<MDC_IQ_CI16> { using type = uint4; static constexpr int kPairBytes = 4; };
-
-template <int FMT> __device__ __forceinline__ int widen(int raw) {      // raw: the byte (CU8) or the signed sample
-    return FMT == MDC_IQ_CU8 ? (2 * raw - 255) * 128 : FMT == MDC_IQ_CI8 ? raw * 256 : raw;
-}
-
-// the widened samples of pairs n .. n+3 (I[e], Q[e]); pairs at or beyond `pairs` read nothing and are zero
-template <int FMT>
-__device__ __forceinline__ void load_quad(const unsigned char* __restrict__ iq, long n, long pairs, int (&I)[4], int (&Q)[4]) {
-    constexpr int kPB = Quad<FMT>::kPairBytes;
-    if (n + 4 <= pairs) {
-        typename Quad<FMT>::type w;
-        __builtin_memcpy(&w, iq + n * kPB, sizeof(w));
-        if constexpr (FMT == MDC_IQ_CI16) {
-            const unsigned v[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { I[e] = (int)(short)(v[e] & 0xFFFFu); Q[e] = (int)(short)(v[e] >> 16); }
-        } else {
-            const unsigned v[2] = {w.x, w.y};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const unsigned bi = (v[e >> 1] >> (16 * (e & 1))) & 0xFFu, bq = (v[e >> 1] >> (16 * (e & 1) + 8)) & 0xFFu;
-                I[e] = widen<FMT>(FMT == MDC_IQ_CU8 ? (int)bi : (int)(signed char)bi);
-                Q[e] = widen<FMT>(FMT == MDC_IQ_CU8 ? (int)bq : (int)(signed char)bq);
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        I[e] = Q[e] = 0;
-        if (n + e < pairs) {
-            const unsigned char* p = iq + (n + e) * kPB;
-            if constexpr (FMT == MDC_IQ_CI16) {
-                unsigned v;
-                __builtin_memcpy(&v, p, 4);
-                I[e] = (int)(short)(v & 0xFFFFu);
-                Q[e] = (int)(short)(v >> 16);
-            } else {
-                I[e] = widen<FMT>(FMT == MDC_IQ_CU8 ? (int)p[0] : (int)(signed char)p[0]);
-                Q[e] = widen<FMT>(FMT == MDC_IQ_CU8 ? (int)p[1] : (int)(signed char)p[1]);
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ int sat16(int v) { return v < -32768 ? -32768 : v > 32767 ? 32767 : v; }
 
 template <int FMT, bool ODD>
 __global__ __launch_bounds__(kDdcThreads) void iq_ddc_kernel(const unsigned char* __restrict__ iq, long pairs, unsigned phase0, unsigned step,

@@ -329,3 +329,116 @@ def ddc(iq, sample_format, shift: float = 0.0, decimate: int = 1, taps=None, pha
         _cabi.check(L.mdc_iq_ddc(t.data_ptr() if pairs else None, fmt, pairs, int(phase0) % (1 << 32), step, D, h.ctypes.data, h.size,
                                  out.data_ptr() if n_out else None, n_out, torch.cuda.current_stream(t.device).cuda_stream))
     return out
+
+
+# ---- rational resampler (mdc_iq_resample): frequency shift, low-pass, resample by L/D -- exact integers, on the device ------
+def resample_out_count(pairs_in: int, ntaps: int, interpolate: int, decimate: int) -> int:
+    """mdc_iq_resample_out_count: output pairs of a capture of pairs_in pairs, ((pairs_in - 1) L + 1 - ntaps) // D + 1 or 0."""
+    return _cabi.check(_cabi.lib().mdc_iq_resample_out_count(int(pairs_in), int(ntaps), int(interpolate), int(decimate)))
+
+
+def _check_resample_factors(interpolate, decimate):
+    L, D = int(interpolate), int(decimate)
+    if not 1 <= L <= _cabi.RESAMPLE_MAX_INTERPOLATE:
+        raise ValueError(f"interpolate must be in 1..{_cabi.RESAMPLE_MAX_INTERPOLATE} (got {L})")
+    if not 1 <= D <= _cabi.RESAMPLE_MAX_DECIMATE:
+        raise ValueError(f"decimate must be in 1..{_cabi.RESAMPLE_MAX_DECIMATE} (got {D})")
+    return L, D
+
+
+def design_resampler(interpolate: int, decimate: int, ntaps=None, cutoff=None, beta: float = 8.0) -> np.ndarray:
+    """The prototype low-pass of a resampling by interpolate / decimate = L / D, as int16 taps for mdc_iq_resample: a Kaiser-windowed
+    sinc at the INTERPOLATED rate of ntaps taps (default 8 M, M = max(L, D); beyond 1024 taps ntaps must be given) whose -6 dB
+    point lies at `cutoff` cycles per interpolated sample (default 0.4 / M), scaled to sum 32768 L and rounded; then, in each of
+    the L polyphase branches h[r::L], what is missing to 32768 goes to the branch's largest tap, so that EVERY branch has DC gain
+    exactly 1 (no output phase is louder than its neighbour at DC; the prototype's symmetry may be off by those few LSB).  With
+    the defaults: droop <= 0.95 dB over |f| <= 0.25 / M, >= 63 dB attenuation for |f| >= 0.75 / M -- design_lowpass's figures, at
+    the interpolated rate -- and every branch's sum |h| far below the 65,535 mdc_iq_resample wants.  L == 1 returns
+    design_lowpass(D, ntaps, cutoff, beta) unchanged.  Group delay: (ntaps - 1) / 2 interpolated samples."""
+    L, D = _check_resample_factors(interpolate, decimate)
+    if L == 1:
+        return design_lowpass(D, ntaps, cutoff, beta)
+    M = max(L, D)
+    if ntaps is None:
+        T = 8 * M
+        if T > _cabi.RESAMPLE_MAX_TAPS:
+            raise ValueError(f"the default of 8 * max(L, D) = {T} taps exceeds {_cabi.RESAMPLE_MAX_TAPS}: pass ntaps explicitly")
+    else:
+        T = int(ntaps)
+    if not 1 <= T <= _cabi.RESAMPLE_MAX_TAPS:
+        raise ValueError(f"ntaps must be in 1..{_cabi.RESAMPLE_MAX_TAPS} (got {T})")
+    fc = 0.4 / M if cutoff is None else float(cutoff)
+    if not 0.0 < fc <= 0.5:
+        raise ValueError(f"cutoff must lie in (0, 0.5] cycles per interpolated sample (got {fc!r})")
+    k = np.arange(T, dtype=np.float64) - (T - 1) / 2.0
+    h = 2.0 * fc * np.sinc(2.0 * fc * k) * np.kaiser(T, float(beta))
+    q = np.rint(h / h.sum() * (32768.0 * L)).astype(np.int64)
+    for r in range(min(L, T)):
+        branch = q[r::L]                                    # a view: the correction lands in q
+        branch[int(np.argmax(branch))] += 32768 - int(branch.sum())
+    if q.min() < -32768 or q.max() > 32767 or max(int(np.abs(q[r::L]).sum()) for r in range(min(L, T))) > _cabi.RESAMPLE_MAX_BRANCH_ABS_SUM:
+        raise ValueError("these parameters give taps outside int16 / a branch beyond the sum |h| <= 65535 of mdc_iq_resample")
+    return q.astype(np.int16)
+
+
+def resample_ratio(rate: float, symbol_rate: float, samples_per_symbol: float = 8, max_interpolate: int = _cabi.RESAMPLE_MAX_INTERPOLATE,
+                   max_decimate: int = _cabi.RESAMPLE_MAX_DECIMATE):
+    """(L, D, achieved samples per symbol) for a capture at `rate` Hz of a signal of `symbol_rate` symbols per second: L / D in
+    lowest terms is the rational number with L <= max_interpolate and D <= max_decimate closest to
+    samples_per_symbol * symbol_rate / rate (ties: the smaller L); the stream after mdc_iq_resample then has rate * L / D /
+    symbol_rate samples per symbol.  ValueError when nothing within the limits comes within 1 % of the target.  (The only
+    place Hz appear: everything else counts in samples.)"""
+    from fractions import Fraction
+    rate, symbol_rate, sps = float(rate), float(symbol_rate), float(samples_per_symbol)
+    if not (np.isfinite(rate) and np.isfinite(symbol_rate) and np.isfinite(sps) and rate > 0 and symbol_rate > 0 and sps > 0):
+        raise ValueError("rate, symbol_rate and samples_per_symbol must be finite and > 0")
+    Lmax, Dmax = _check_resample_factors(max_interpolate, max_decimate)
+    target = Fraction(sps) * Fraction(symbol_rate) / Fraction(rate)
+    best = None
+    for L in range(1, Lmax + 1):
+        d = Fraction(L) / target
+        for D in {max(1, min(Dmax, d.__floor__())), max(1, min(Dmax, d.__ceil__()))}:
+            err = abs(Fraction(L, D) - target)
+            if best is None or err < best[0]:
+                best = (err, Fraction(L, D))
+    err, f = best
+    if err > target / 100:
+        raise ValueError(f"no L / D with L <= {Lmax}, D <= {Dmax} comes within 1 % of {float(target):.6g} "
+                         f"({sps:g} samples per symbol at {symbol_rate:g} sym/s from {rate:g} S/s); closest {f.numerator}/{f.denominator}")
+    return f.numerator, f.denominator, rate * f.numerator / f.denominator / symbol_rate
+
+
+def resample(iq, sample_format, shift: float = 0.0, interpolate: int = 1, decimate: int = 1, taps=None, phase0: int = 0, device=None):
+    """Tune, low-pass and resample a capture by interpolate / decimate on the device (mdc_iq_resample, include/mdc.h: exact
+    integer arithmetic; interpolate == 1 is ddc, bit for bit).  iq, shift, phase0: as ddc (shift in cycles per INPUT sample).
+    taps: the int16 prototype at the interpolated rate, applied as written; None = design_resampler(L, D) of the factors reduced
+    by their gcd -- interpolate == decimate needs explicit taps.  With explicit taps the factors are used as given.  Returns the
+    (n_out, 2) int16 device tensor, n_out = resample_out_count(pairs, ntaps, L, D): an ordinary "ci16" capture.  Enqueues on
+    torch's current stream without synchronising."""
+    import math
+    import torch
+    fmt = sample_format_id(sample_format)
+    (L, D), step = _check_resample_factors(interpolate, decimate), phase_step(shift)
+    if taps is None:
+        g = math.gcd(L, D)
+        L, D = L // g, D // g
+        if L == 1 and D == 1:
+            raise ValueError("interpolate == decimate needs explicit taps (design_resampler designs filters for a change of rate)")
+        taps = design_resampler(L, D)
+    h = np.asarray(taps)
+    if h.dtype.kind != "i" or h.ndim != 1:
+        raise TypeError("taps must be a one-dimensional integer array (int16)")
+    if h.size and (h.min() < -32768 or h.max() > 32767):
+        raise ValueError("taps must fit int16")
+    h = np.ascontiguousarray(h.astype(np.int16))
+    t = _device_samples(iq, fmt, device)
+    pairs = t.numel() * t.element_size() // _cabi.IQ_PAIR_BYTES[fmt]
+    if pairs * _cabi.IQ_PAIR_BYTES[fmt] != t.numel() * t.element_size():
+        raise ValueError("the capture is not a whole number of (I,Q) pairs")
+    lib = _cabi.lib()
+    n_out = _cabi.check(lib.mdc_iq_resample_out_count(pairs, h.size, L, D))
+    out = torch.empty((n_out, 2), dtype=torch.int16, device=t.device)
+    with torch.cuda.device(t.device):
+        _cabi.check(lib.mdc_iq_resample(t.data_ptr() if pairs else None, fmt, pairs, int(phase0) % (1 << 32), step, L, D, h.ctypes.data, h.size,
+                                        out.data_ptr() if n_out else None, n_out, torch.cuda.current_stream(t.device).cuda_stream))
+    return out

@@ -862,7 +862,7 @@ class VTCNN2:
 
     def predict_iq(self, iq, sample_format, scale: Optional[float] = None, batch_size: int = 0, hop: int = 128,
                    normalize: Optional[str] = None, level: float = 7.8e-3, remove_dc: bool = True, squelch_dbfs: Optional[float] = None,
-                   return_power: bool = False, shift: float = 0.0, decimate: int = 1, taps=None):
+                   return_power: bool = False, shift: float = 0.0, decimate: int = 1, taps=None, interpolate: int = 1):
         """predict_iq_u8 for a capture in any integer sample format: sample_format "cu8" (unsigned bytes, RTL-SDR), "ci8"
         (signed bytes: HackRF) or "ci16" (signed 16-bit little-endian: USRP sc16, SDRplay, bladeRF, Airspy); SigMF's
         "ci16_le" etc. are aliases.  iq: a numpy array or torch tensor of the format's dtype (uint8 / int8 / int16; a
@@ -879,13 +879,21 @@ class VTCNN2:
         input sample is added to every frequency, taps=None is frontend.design_lowpass(decimate) --, and its int16 output is
         classified as a "ci16" capture with the same hop / normalize / level / squelch_dbfs / return_power (scale=None then means
         1/32768; hop counts OUTPUT pairs).  A numpy capture is moved to the device for this and numpy results come back.  With the
-        defaults (0.0, 1, None) nothing changes."""
+        defaults (0.0, 1, None) nothing changes.
+
+        interpolate: a rate that no integer decimation brings to 8 samples per symbol (2.4 MS/s on 250 ksym/s wants 5/6:
+        frontend.resample_ratio) goes through frontend.resample(iq, sample_format, shift, interpolate, decimate, taps) instead --
+        taps=None is frontend.design_resampler of the reduced factors --; everything after it is the same.  With interpolate == 1
+        the route above is taken unchanged."""
         torch = _torch()
         from . import frontend as F
         fmt = F.sample_format_id(sample_format)
         as_numpy = not isinstance(iq, torch.Tensor)
-        if shift != 0.0 or decimate != 1 or taps is not None:
-            down = F.ddc(iq, fmt, shift=shift, decimate=decimate, taps=taps, device=f"cuda:{self.device_index}")
+        if shift != 0.0 or decimate != 1 or taps is not None or interpolate != 1:
+            if interpolate != 1:
+                down = F.resample(iq, fmt, shift=shift, interpolate=interpolate, decimate=decimate, taps=taps, device=f"cuda:{self.device_index}")
+            else:
+                down = F.ddc(iq, fmt, shift=shift, decimate=decimate, taps=taps, device=f"cuda:{self.device_index}")
             res = self.predict_iq(down.view(-1), _cabi.IQ_CI16, scale, batch_size=batch_size, hop=hop, normalize=normalize, level=level,
                                   remove_dc=remove_dc, squelch_dbfs=squelch_dbfs, return_power=return_power)
             return tuple(r.cpu().numpy() for r in res) if as_numpy else res
