@@ -221,7 +221,12 @@ MDC_API int mdc_predict_host_checked(mdc_model* m, const float* x_host, int64_t 
  * validating ROM tables / test vectors written by the float2fix exporter (CNN.ipynb cells 23-24).  The integer
  * tables are made from the model's weights at mdc_finalize (float2fix: trunc(v * 4096)).
  * x_dev: (n,2,128) f32 frames (quantised on load, x_is_q612 = 0) or int32 Q6.12 words (x_is_q612 = 1).
- * dense_dev (n,C) int32 = post-ReLU class sums, value/4096 (or NULL); labels_dev (n) int32 first maximum (or NULL). */
+ * dense_dev (n,C) int32 = post-ReLU class sums, value/4096 (or NULL); labels_dev (n) int32 first maximum (or NULL).
+ * Input domain: an integer word is taken modulo 2^18 (bits 18..31 are ignored, whatever they hold).  A float sample v
+ * with |v| < 2^19 becomes trunc(v * 4096) wrapped to 18 bits, exactly as float2fix writes it.  A frame that holds a
+ * sample with |v| >= 2^19, a NaN or an infinity gets unspecified class sums and a label in [0, C); such a frame never
+ * affects another frame's results.  The kernel exists for F = 3 and F = 10 filters, the only deployed topologies
+ * mdc_create admits (any other F is MDC_ENOTSUP there, so no such model reaches this call). */
 MDC_API int mdc_forward_q612(const mdc_model* m, const void* x_dev, int x_is_q612, int64_t n,
                      int32_t* dense_dev, int32_t* labels_dev, void* hip_stream);
 

@@ -58,6 +58,9 @@ DDC_TILE_PAIRS, DDC_GRID_CAP = 8192, 1024
 # tiling (csrc/iq_resample.hip): a tile is ((RESAMPLE_TILE_PAIRS - ceil(T / L)) // D) * L outputs, RESAMPLE_GRID_CAP work-groups
 RESAMPLE_MAX_INTERPOLATE, RESAMPLE_MAX_DECIMATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BRANCH_ABS_SUM = 32, 256, 1024, 65535
 RESAMPLE_TILE_PAIRS, RESAMPLE_GRID_CAP = 8192, 1024
+# mdc_forward_q612: the kernel's walk (csrc/deployed_q612.hip: kQGridCap, kQBlockFrames) for tests and tools -- at most Q612_GRID_CAP
+# work-groups of 4 waves, each wave taking Q612_BLOCK_FRAMES frames at a time; more frames than that product are walked in passes
+Q612_GRID_CAP, Q612_BLOCK_FRAMES = 2048, 64
 
 
 class MdcTopology(C.Structure):

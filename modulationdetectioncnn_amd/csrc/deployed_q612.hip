@@ -15,8 +15,10 @@
 // w = 2l+1 and 2l+2 of both rows (samples x[2l], x[2l+1] by one 8-byte load per row, x[2l+2] from lane l+1 by DPP;
 // lane 63's second position is w = 128 with x[128] = 0) and keeps their integer dense weights -- 2 positions x F
 // filters x C classes x {I, Q} tables -- in registers for the whole kernel.  A product pair a*b + c*d of 18-bit
-// operands is formed exactly in 64 bits by two v_mad_i64_i32; {m[35], m[28:12]} comes out of its two halves.  The 32-bit
-// wrap-around sums are associative, so the per-lane partial sums are combined with a butterfly and the result is
+// operands is formed exactly in 64 bits by two v_mad_i64_i32; {m[35], m[28:12]} comes out of its two halves.  The dense
+// sums are integer adds (with F <= 10 the 32-bit accumulator cannot wrap: 258 F = 2,580 terms of magnitude at most 2^17 plus
+// the bias stay under 2^31; what does wrap is the 36-bit wire and the 18-bit out + bias), so they are associative: the
+// per-lane partial sums are combined with a butterfly and the result is
 // bit-identical to the FPGA's sequential accumulation; lane i of the wave parks the totals (and the quantised x[h][0])
 // of the block's frame i, and after 64 frames every lane finishes one frame: position w = 0 (x[-1] = 0; uniform
 // weights), bias, ReLU, first-max label, 768 + 256 B of coalesced stores.
@@ -41,6 +43,9 @@ namespace mdc {
 namespace {
 
 constexpr int kQC = 3;          // classes of the deployed nets (mdc_create admits no other)
+constexpr int kQBlockFrames = 64;      // frames a wave takes at a time, one per lane in the finish (_cabi.Q612_BLOCK_FRAMES)
+constexpr long kQGridCap = 2048;       // work-groups of 4 waves; beyond it the waves stride over the blocks (_cabi.Q612_GRID_CAP)
+static_assert(kQBlockFrames == 64, "a block is one frame per lane of a wave: the kernel cuts blocks with >> 6 and parks frame i in lane i");
 
 __device__ __forceinline__ int wrap18(int v) { return (v << 14) >> 14; }
 // {m[35], m[28:12]} of the 36-bit wire m = a*b + c*d, as a signed 18-bit value.  The sign is BIT 35 of the wrapped sum,
@@ -52,7 +57,10 @@ __device__ __forceinline__ int select18(long long m) {
 __device__ __forceinline__ int pair18(int a, int b, int c, int d) {      // select18(a*b + c*d), exact
     return select18((long long)a * b + (long long)c * d);
 }
-__device__ __forceinline__ int quant(float v) {                  // float2fix: truncate toward zero, wrap to 18 bits
+// float2fix: truncate toward zero, wrap to 18 bits.  Equal to the oracle's trunc-then-wrap while |v * 4096| < 2^31, i.e.
+// |v| < 2^19; beyond that, and for NaN / Inf, the float-to-int conversion saturates instead of wrapping (include/mdc.h: such a
+// frame's sums are unspecified).  A wrap for every finite v would add VALU work per sample to this issue-bound kernel.
+__device__ __forceinline__ int quant(float v) {
     return wrap18((int)truncf(v * 4096.f));
 }
 
@@ -133,9 +141,9 @@ __global__ __launch_bounds__(256, 2) void deployed_q612_kernel(const void* __res
                     aq = aq < 0 ? 0 : aq;
 #pragma unroll
                     for (int c = 0; c < kQC; ++c)
-                        acc[c] += (unsigned)pair18(ai, wq(s, f, c, 0), aq, wq(s, f, c, 1));      // sign-extended 18-bit term, 32-bit wrap
+                        acc[c] += (unsigned)pair18(ai, wq(s, f, c, 0), aq, wq(s, f, c, 1));      // sign-extended 18-bit term (unsigned: partial sums go negative)
                 }
-            // wave sum (wrap-around adds commute and associate: any order gives the same bits): a DPP butterfly over each 16-lane
+            // wave sum (integer adds commute and associate: any order gives the same bits): a DPP butterfly over each 16-lane
             // row, then the four row sums through scalar registers -- __shfl_xor would be six dependent ds_bpermute_b32 per class
 #pragma unroll
             for (int c = 0; c < kQC; ++c) {
@@ -221,8 +229,8 @@ int deployed_q612_forward(const mdc_model* m, const void* x, int x_is_q, int64_t
     if (!m->d_pack[1]) { set_error("Q6.12 tables missing"); return MDC_ESTATE; }
     if (n == 0) return MDC_OK;
     const int* tab = static_cast<const int*>(m->d_pack[1]);
-    long grid = ((n + 63) / 64 + 3) / 4;
-    if (grid > 2048) grid = 2048;
+    long grid = ((n + kQBlockFrames - 1) / kQBlockFrames + 3) / 4;
+    if (grid > kQGridCap) grid = kQGridCap;
     if (F == 3) hipLaunchKernelGGL(deployed_q612_kernel<3>, dim3((unsigned)grid), dim3(256), 0, s, x, x_is_q, (long)n, tab, dense, labels);
     else if (F == 10) hipLaunchKernelGGL(deployed_q612_kernel<10>, dim3((unsigned)grid), dim3(256), 0, s, x, x_is_q, (long)n, tab, dense, labels);
     else { set_error("Q6.12 path is built for F = 3 and F = 10 (got %d)", F); return MDC_ENOTSUP; }

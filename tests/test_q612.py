@@ -2,7 +2,9 @@
 
 CPU (`not gpu`): the integer oracle (oracle/oracle_q612.py) against what the reference recorded -- the float
 results of CNN.ipynb cell 18 / 12.16.testDataYunyun.txt (to the quantisation error) and the frozen labels.
-GPU: mdc_forward_q612 == the integer oracle, bit for bit, including 18-bit / 32-bit wrap-around.
+GPU: mdc_forward_q612 == the integer oracle, bit for bit, including the wraps of the 36-bit wire and of the 18-bit
+out + bias (with F <= 10 the 32-bit accumulator cannot wrap: 2,580 terms of at most 2^17 stay under 2^31).  The cases at
+full-range operands, every ragged block size and past the grid cap are tests/test_q612_gpu.py.
 Bit-level agreement with the FPGA itself is parity-unpinned: the reference holds no RTL outputs."""
 import json
 import os
@@ -89,6 +91,68 @@ def test_txt_tables_are_exact_in_q612():
         np.testing.assert_array_equal(bq, np.round(b * 4096).astype(np.int64))
 
 
+def _scalar_forward(frame, ck, cb, dk, db):
+    """One frame through the rules in the header of oracle/oracle_q612.py and at mdc_forward_q612 in include/mdc.h, on
+    plain Python integers (no numpy inside): frame [2][128], ck [2][F] taps, cb [F], dk [258 F][C], db [C], all 18-bit
+    two's-complement values.  Returns (conv [2][129][F], dense [C], label)."""
+    def wrap_bits(v, bits):
+        v &= (1 << bits) - 1
+        return v - (1 << bits) if v >> (bits - 1) else v
+
+    def neuron(a, b, c, d):                    # {m[35], m[28:12]} of the 36-bit wire, by masking
+        m = (a * b + c * d) & ((1 << 36) - 1)
+        return wrap_bits(((m >> 35) << 17) | ((m >> 12) & 0x1FFFF), 18)
+
+    F, C = len(cb), len(db)
+    conv = []
+    for h in range(2):
+        padded = [0] + [wrap_bits(v, 18) for v in frame[h]] + [0]
+        row = []
+        for w in range(129):
+            acts = []
+            for f in range(F):
+                v = wrap_bits(neuron(padded[w], ck[0][f], padded[w + 1], ck[1][f]) + cb[f], 18)
+                acts.append(0 if v < 0 else v)
+            row.append(acts)
+        conv.append(row)
+    dense = []
+    for c in range(C):
+        acc = db[c]                            # the accumulator starts at the sign-extended bias
+        for w in range(129):
+            for f in range(F):
+                acc = wrap_bits(acc + neuron(conv[0][w][f], dk[w * F + f][c], conv[1][w][f], dk[129 * F + w * F + f][c]), 32)
+        dense.append(0 if acc < 0 else acc)
+    label = 0
+    for c in range(1, C):
+        if dense[c] > dense[label]:
+            label = c
+    return conv, dense, label
+
+
+def test_oracle_equals_a_scalar_restatement_on_full_range_operands():
+    """The vectorised oracle carries products up to 2^35 in int64; a scalar restatement on Python integers, written from
+    the rules and not from the oracle's code, gives the same conv, dense and labels on uniform 18-bit operands (F = 3)
+    and on the frame whose samples and taps are all -2^17."""
+    F, lo, hi = 3, -(1 << 17), 1 << 17
+    rng = np.random.default_rng(17)
+    ck, cb = rng.integers(lo, hi, (1, 2, 1, F)), rng.integers(lo, hi, (F,))
+    dk, db = rng.integers(lo, hi, (258 * F, 3)), rng.integers(lo, hi, (3,))
+    x = rng.integers(lo, hi, (5, 2, 128))
+    x[4] = lo
+    cases = [(x[:4], ck, cb), (x[4:], np.full((1, 2, 1, F), lo), np.full((F,), -1))]
+    seen_conv = set()
+    for xs, k, b in cases:
+        ref = Q.forward_q612(xs, [(k, b), (dk, db)])
+        for i in range(xs.shape[0]):
+            conv, dense, label = _scalar_forward(xs[i].tolist(), k.reshape(2, F).tolist(), b.tolist(), dk.tolist(), db.tolist())
+            assert conv == ref["conv"][i].tolist()
+            assert dense == ref["dense"][i].tolist()
+            assert label == int(ref["labels"][i])
+            seen_conv.update(v for row in conv for pos in row for v in pos)
+    assert 0 in seen_conv and 131071 in seen_conv and max(seen_conv) > 1 << 16      # ReLU zeros, the +2^35 wrap, large acts
+    assert (ref["conv"][0, :, 1:128, :] == 131071).all()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,n", [("3convmodrecnets_CNN2_0.5", 1), ("3convmodrecnets_CNN2_0.5", 257),
                                     ("convmodrecnets_CNN2_0.5", 100), ("3convmodrecnets_CNN2_0.5", 0)])
@@ -101,7 +165,7 @@ def test_gpu_q612_is_bit_exact(name, n):
     rng = np.random.default_rng(5)
     x = (rng.standard_normal((n, 2, 128)) * 0.3).astype(np.float32)
     if n > 4:
-        x[1] *= 200.0          # saturating frame: exercises the 18-bit and 32-bit wrap-around
+        x[1] *= 200.0          # saturating frame: exercises the 18-bit wraps (quantiser, out + bias) and the 36-bit wire
         x[2, 0, 5] = -1e-5     # float2fix "-0"
     ref = Q.forward_from_float(x, w)
     dense, labels = m.predict_q612(x, as_float=False)
