@@ -17,7 +17,14 @@ exact arithmetic): give the factor as --interpolate L --decimate D, or let --sym
 
     python examples/classify_capture.py capture.bin --rate 2.4e6 --symbol-rate 250e3 --shift-hz -480e3
 
-Without a capture file it classifies a synthetic one: bursts of tones at three gains with silence between them."""
+When it is not known where in the band the signals are, --scan finds out: the capture's power spectrum (frontend.spectrogram, on
+the device) is searched for emitters, each one is tuned, resampled and classified (VTCNN2.scan_iq), and one line per emitter
+comes out -- in Hz when --rate is given, else in cycles per sample:
+
+    python examples/classify_capture.py capture.bin --format ci16 --rate 2.4e6 --scan --nfft 1024 --threshold 6
+
+Without a capture file it classifies a synthetic one: bursts of tones at three gains with silence between them (--scan: a
+band of three QPSK emitters of different widths over noise and a DC offset)."""
 import argparse
 import os
 import sys
@@ -48,6 +55,39 @@ def synthetic_capture(fmt="cu8", seed=1):
     iq = np.stack([k * (z.real + 1.8), k * (z.imag - 1.4)], axis=1)
     lo, hi = (-128, 127) if fmt == "ci8" else (-32768, 32767)
     return np.clip(np.rint(iq), lo, hi).astype(DTYPES[fmt]).reshape(-1)
+
+
+def synthetic_band(fmt="ci16", seed=1, pairs=1 << 18):
+    """Three QPSK emitters with a root-raised-cosine pulse (beta 0.35) at 96 / 48 / 20 samples per symbol, centred at -0.31 / +0.12 /
+    +0.36 cycles per sample with rms 0.02 / 0.05 / 0.01 of full scale, over noise of rms 0.002 and a tuner's DC offset."""
+    rng = np.random.default_rng(seed)
+    beta, n, z = 0.35, np.arange(pairs), np.zeros(pairs, complex)
+    for sps, fc, amp in ((96, -0.31, 0.02), (48, 0.12, 0.05), (20, 0.36, 0.01)):
+        t = np.arange(-12 * sps, 12 * sps + 1) / sps + 1e-9          # (off the pulse's removable singularities)
+        h = (np.sin(np.pi * t * (1 - beta)) + 4 * beta * t * np.cos(np.pi * t * (1 + beta))) / (np.pi * t * (1 - (4 * beta * t) ** 2))
+        sym = rng.choice([-1.0, 1.0], pairs // sps + 2) + 1j * rng.choice([-1.0, 1.0], pairs // sps + 2)
+        up = np.zeros(sym.size * sps, complex)
+        up[::sps] = sym
+        base = np.convolve(up, h, mode="same")[:pairs]
+        z += amp / np.sqrt(np.mean(np.abs(base) ** 2)) * base * np.exp(2j * np.pi * fc * n)
+    z += 0.002 / np.sqrt(2) * (rng.standard_normal(pairs) + 1j * rng.standard_normal(pairs)) + (0.01 - 0.02j)
+    if fmt == "cu8":
+        return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * 127.5 + 127.5), 0, 255).astype(np.uint8).reshape(-1)
+    full, lo, hi = (128.0, -128, 127) if fmt == "ci8" else (32768.0, -32768, 32767)
+    return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * full), lo, hi).astype(DTYPES[fmt]).reshape(-1)
+
+
+def scan(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0):
+    """Print one line per emitter of the capture (VTCNN2.scan_iq) and return the records.  rate: Hz columns instead of cycles per sample."""
+    found = model.scan_iq(iq[:iq.size // 2 * 2], fmt, nfft=nfft, threshold_db=threshold_db, hop=hop, level=level, squelch_dbfs=squelch)
+    k, unit = (rate, "Hz") if rate else (1.0, "cyc/sample")
+    print(f"{len(found)} emitters ({unit})")
+    print(f"{'centre':>12s} {'bandwidth':>12s} {'dBFS':>7s} {'SNR dB':>7s} {'L/D':>7s} {'windows':>8s} {'open':>6s} {'label':>6s}")
+    for e in found:
+        labels = np.asarray(e["labels"])
+        print(f"{e['centre'] * k:12.6g} {e['bandwidth'] * k:12.6g} {e['power_dbfs']:7.1f} {e['snr_db']:7.1f} "
+              f"{str(e['interpolate']) + '/' + str(e['decimate']):>7s} {labels.size:8d} {int((labels >= 0).sum()):6d} {e['label']:6d}")
+    return found
 
 
 def classify(model, iq, fmt, hop=128, level=7.8e-3, squelch=-35.0, shift=0.0, decimate=1, interpolate=1):
@@ -101,7 +141,19 @@ def main():
     ap.add_argument("--interpolate", type=int, default=1, help="with --decimate D: resample by this L over D (1..32)")
     ap.add_argument("--symbol-rate", type=float, default=None,
                     help="symbols per second of the signal: picks --interpolate / --decimate so that --rate becomes 8 samples per symbol")
+    ap.add_argument("--scan", action="store_true", help="find the emitters in the band first and classify each one (ignores --shift-hz, --decimate, ...)")
+    ap.add_argument("--nfft", type=int, default=1024, help="with --scan: bins of the spectrum (a power of two in 64..4096)")
+    ap.add_argument("--threshold", type=float, default=6.0, help="with --scan: dB above the noise floor at which a bin belongs to an emitter")
     a = ap.parse_args()
+    if a.scan:
+        iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_band(a.format)
+        if a.weights is None:
+            model = VTCNN2.synthetic("deployed3")
+        else:
+            model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
+        scan(model, iq, a.format, nfft=a.nfft, threshold_db=a.threshold, rate=a.rate if a.rate != 1.0 else None, hop=a.hop, level=a.level,
+             squelch=a.squelch)
+        return
     if a.symbol_rate is not None:
         from modulationdetectioncnn_amd import frontend
         a.interpolate, a.decimate, sps = frontend.resample_ratio(a.rate, a.symbol_rate)

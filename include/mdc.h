@@ -54,7 +54,8 @@ extern "C" {
                                   (signed 8- and 16-bit sample formats, MDC_IQ_*, mdc_iq_window_stats64);
                                   mdc_iq_ddc / mdc_iq_ddc_out_count / mdc_iq_ddc_nco_table (frequency shift, low-pass and
                                   decimation of a raw capture, exact integers);
-                                  mdc_iq_resample / mdc_iq_resample_out_count (the same with a rational factor L/D) */
+                                  mdc_iq_resample / mdc_iq_resample_out_count (the same with a rational factor L/D);
+                                  mdc_iq_spectrogram / mdc_iq_spectrogram_rows (averaged power spectra of a raw capture) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -419,6 +420,34 @@ MDC_API int mdc_iq_ddc(const void* iq_dev, int format, int64_t pairs_in, uint32_
 MDC_API int64_t mdc_iq_resample_out_count(int64_t pairs_in, int ntaps, int interpolate, int decimate);
 MDC_API int mdc_iq_resample(const void* iq_dev, int format, int64_t pairs_in, uint32_t phase0, uint32_t phase_step, int interpolate,
                             int decimate, const int16_t* taps_host, int ntaps, int16_t* out_dev, int64_t n_out, void* hip_stream);
+
+/* ---- power spectrogram: windowed FFTs of a raw capture, averaged (additive in ABI 5) ----------------------------------------
+ * mdc_iq_ddc and mdc_iq_resample want to be told where the signal is and how wide; mdc_iq_spectrogram is what finds out: the
+ * power spectrum of the capture, segment by segment, on the device (the float64 numpy restatement is tests/iq_spectrum_ref.py).
+ * Normatively, for the pairs_in = P input pairs x_n = (I_n, Q_n), n counted from iq_dev:
+ *   widening   to 16-bit full scale, as in mdc_iq_ddc: MDC_IQ_CU8 (2*byte - 255)*128, MDC_IQ_CI8 s*256, MDC_IQ_CI16 s.
+ *   segments   segment s starts at pair s*hop and holds nfft pairs; segs = P >= nfft ? (P - nfft) / hop + 1 : 0.  hop < nfft
+ *              (overlap), hop == nfft and hop > nfft (a sparse, fast scan that skips pairs) are all legal.
+ *   window     v_s[n] = x[s*hop + n] * w[n], n = 0 .. nfft-1, w the nfft int16 values at window_dev (a DEVICE buffer: 8 KiB do
+ *              not travel with a launch the way taps do), applied as written.  Both components are exact integers, |v| < 2^30.
+ *   spectrum   X_s[k] = sum_n v_s[n] e^{-2 pi i k n / nfft}, k = 0 .. nfft-1.
+ *   rows       rows = segs / avg; row r averages segments r*avg .. r*avg + avg-1:
+ *              P[r,k] = scale * (1/avg) * sum_s |X_s[k]|^2, float32, in natural DFT order (bin k is k/nfft cycles per sample,
+ *              k >= nfft/2 the negative frequencies), rows contiguous: power_dev holds rows * nfft floats.  Trailing segments
+ *              that do not fill a row are DROPPED.
+ * The transform runs in float32 (twiddle factors rounded from float64), the segments of a row are summed in a fixed order by
+ * one work-group: the same inputs give the same bits on every run, and row r of a call equals, bit for bit, the single row of a
+ * call on the pairs from r*avg*hop on.  With u = 2^-24 and eps = 8u (log2 nfft + 1) every value lies within
+ * mean_s[2 eps sqrt(P_s[k] T_s) + eps^2 T_s] + (avg + 4) u P[r,k] of the definition (P_s: one segment's scaled power, T_s its
+ * sum over the bins).
+ * nfft: a power of two in 64..4096; hop >= 1; 1 <= avg <= 4096; scale finite and > 0; rows must equal
+ * mdc_iq_spectrogram_rows.  iq_dev is aligned to one pair (2 / 2 / 4 bytes), window_dev to 2 bytes, power_dev to 4 bytes.  Every
+ * argument error is MDC_EINVAL before any device call.  rows == 0 is MDC_OK (nothing is launched; the buffers may be NULL); otherwise no
+ * buffer may be NULL.  The call only enqueues on hip_stream (no synchronisation, no allocation, no copy: capturable in a
+ * hipGraph) and runs on the current device.  mdc_iq_spectrogram_rows returns rows, or a negative MDC_EINVAL. */
+MDC_API int64_t mdc_iq_spectrogram_rows(int64_t pairs_in, int nfft, int64_t hop, int avg);
+MDC_API int mdc_iq_spectrogram(const void* iq_dev, int format, int64_t pairs_in, int nfft, int64_t hop, int avg,
+                               const int16_t* window_dev, float scale, float* power_dev, int64_t rows, void* hip_stream);
 
 /* test_Y_hat = model.predict(X_test, batch_size=batch_size)  (cnn.py:198, 237) when X_test lies in HOST memory -- a
  * numpy array, or whatever buffer a cgo / JNI / N-API caller holds: the library's own driver in front of mdc_forward.

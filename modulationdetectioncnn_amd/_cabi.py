@@ -36,6 +36,7 @@ EXPORTS = [
     "mdc_iq_windows", "mdc_iq_windows_norm", "mdc_predict_host_iq", "mdc_predict_host_iq_norm",
     "mdc_iq_ddc", "mdc_iq_ddc_out_count", "mdc_iq_ddc_nco_table",
     "mdc_iq_resample", "mdc_iq_resample_out_count",
+    "mdc_iq_spectrogram", "mdc_iq_spectrogram_rows",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
@@ -58,6 +59,10 @@ DDC_TILE_PAIRS, DDC_GRID_CAP = 8192, 1024
 # tiling (csrc/iq_resample.hip): a tile is ((RESAMPLE_TILE_PAIRS - ceil(T / L)) // D) * L outputs, RESAMPLE_GRID_CAP work-groups
 RESAMPLE_MAX_INTERPOLATE, RESAMPLE_MAX_DECIMATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BRANCH_ABS_SUM = 32, 256, 1024, 65535
 RESAMPLE_TILE_PAIRS, RESAMPLE_GRID_CAP = 8192, 1024
+# mdc_iq_spectrogram: limits of include/mdc.h, and the kernel's grid (csrc/iq_spectrogram.hip: kSpecGridCap): one work-group per
+# row, at most SPECTROGRAM_GRID_CAP of them; more rows are walked in passes
+SPECTROGRAM_MIN_NFFT, SPECTROGRAM_MAX_NFFT, SPECTROGRAM_MAX_AVG = 64, 4096, 4096
+SPECTROGRAM_GRID_CAP = 2048
 # mdc_forward_q612: the kernel's walk (csrc/deployed_q612.hip: kQGridCap, kQBlockFrames) for tests and tools -- at most Q612_GRID_CAP
 # work-groups of 4 waves, each wave taking Q612_BLOCK_FRAMES frames at a time; more frames than that product are walked in passes
 Q612_GRID_CAP, Q612_BLOCK_FRAMES = 2048, 64
@@ -137,7 +142,8 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_predict_host_iq_norm", [vp, vp, i32, i64, i64, C.c_float, i32, vp, vp, vp, i64]),
                        ("mdc_iq_ddc_nco_table", [vp]),
                        ("mdc_iq_ddc", [vp, i32, i64, C.c_uint32, C.c_uint32, i32, vp, i32, vp, i64, vp]),
-                       ("mdc_iq_resample", [vp, i32, i64, C.c_uint32, C.c_uint32, i32, i32, vp, i32, vp, i64, vp])):
+                       ("mdc_iq_resample", [vp, i32, i64, C.c_uint32, C.c_uint32, i32, i32, vp, i32, vp, i64, vp]),
+                       ("mdc_iq_spectrogram", [vp, i32, i64, i32, i64, i32, vp, C.c_float, vp, i64, vp])):
         fn = getattr(L, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, i32
@@ -145,6 +151,8 @@ def lib(variant: str = "product") -> C.CDLL:
         L.mdc_iq_ddc_out_count.argtypes, L.mdc_iq_ddc_out_count.restype = [i64, i32, i32], i64
     if getattr(L, "mdc_iq_resample_out_count", None) is not None:
         L.mdc_iq_resample_out_count.argtypes, L.mdc_iq_resample_out_count.restype = [i64, i32, i32, i32], i64
+    if getattr(L, "mdc_iq_spectrogram_rows", None) is not None:
+        L.mdc_iq_spectrogram_rows.argtypes, L.mdc_iq_spectrogram_rows.restype = [i64, i32, i64, i32], i64
     fp = C.POINTER(C.c_float)
     L.mdc_trainer_create.argtypes = [C.POINTER(MdcTopology), i32, C.POINTER(vp)]
     L.mdc_trainer_num_layers.argtypes = [vp]

@@ -381,6 +381,19 @@ def design_resampler(interpolate: int, decimate: int, ntaps=None, cutoff=None, b
     return q.astype(np.int16)
 
 
+def _closest_ratio(target, Lmax: int, Dmax: int):
+    """(|L/D - target|, L/D) as Fractions: the rational with L <= Lmax, D <= Dmax closest to target > 0 (ties: the smaller L)."""
+    from fractions import Fraction
+    best = None
+    for L in range(1, Lmax + 1):
+        d = Fraction(L) / target
+        for D in {max(1, min(Dmax, d.__floor__())), max(1, min(Dmax, d.__ceil__()))}:
+            err = abs(Fraction(L, D) - target)
+            if best is None or err < best[0]:
+                best = (err, Fraction(L, D))
+    return best
+
+
 def resample_ratio(rate: float, symbol_rate: float, samples_per_symbol: float = 8, max_interpolate: int = _cabi.RESAMPLE_MAX_INTERPOLATE,
                    max_decimate: int = _cabi.RESAMPLE_MAX_DECIMATE):
     """(L, D, achieved samples per symbol) for a capture at `rate` Hz of a signal of `symbol_rate` symbols per second: L / D in
@@ -394,14 +407,7 @@ def resample_ratio(rate: float, symbol_rate: float, samples_per_symbol: float = 
         raise ValueError("rate, symbol_rate and samples_per_symbol must be finite and > 0")
     Lmax, Dmax = _check_resample_factors(max_interpolate, max_decimate)
     target = Fraction(sps) * Fraction(symbol_rate) / Fraction(rate)
-    best = None
-    for L in range(1, Lmax + 1):
-        d = Fraction(L) / target
-        for D in {max(1, min(Dmax, d.__floor__())), max(1, min(Dmax, d.__ceil__()))}:
-            err = abs(Fraction(L, D) - target)
-            if best is None or err < best[0]:
-                best = (err, Fraction(L, D))
-    err, f = best
+    err, f = _closest_ratio(target, Lmax, Dmax)
     if err > target / 100:
         raise ValueError(f"no L / D with L <= {Lmax}, D <= {Dmax} comes within 1 % of {float(target):.6g} "
                          f"({sps:g} samples per symbol at {symbol_rate:g} sym/s from {rate:g} S/s); closest {f.numerator}/{f.denominator}")
@@ -442,3 +448,189 @@ def resample(iq, sample_format, shift: float = 0.0, interpolate: int = 1, decima
         _cabi.check(lib.mdc_iq_resample(t.data_ptr() if pairs else None, fmt, pairs, int(phase0) % (1 << 32), step, L, D, h.ctypes.data, h.size,
                                         out.data_ptr() if n_out else None, n_out, torch.cuda.current_stream(t.device).cuda_stream))
     return out
+
+
+# ---- power spectrogram (mdc_iq_spectrogram) and the emitter scan: where the signals are, and how wide ------------------------
+def spectrogram_rows(pairs: int, nfft: int, hop: int, avg: int) -> int:
+    """mdc_iq_spectrogram_rows: rows of a capture of `pairs` pairs -- ((pairs - nfft) // hop + 1) // avg, or 0 when pairs < nfft;
+    trailing segments that do not fill a row of `avg` are dropped."""
+    return _cabi.check(_cabi.lib().mdc_iq_spectrogram_rows(int(pairs), int(nfft), int(hop), int(avg)))
+
+
+def design_window(nfft: int, kind: str = "hann", beta: float = 8.0) -> np.ndarray:
+    """An int16 analysis window for mdc_iq_spectrogram: rint(32767 w), w the PERIODIC Hann window 0.5 - 0.5 cos(2 pi n / nfft)
+    (kind="hann") or numpy's Kaiser window of shape `beta` (kind="kaiser")."""
+    n = int(nfft)
+    if n < 1:
+        raise ValueError("nfft must be >= 1")
+    if kind == "hann":
+        w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n, dtype=np.float64) / n)
+    elif kind == "kaiser":
+        w = np.kaiser(n, float(beta))
+    else:
+        raise ValueError(f"kind must be 'hann' or 'kaiser' (got {kind!r})")
+    return np.rint(32767.0 * w).astype(np.int16)
+
+
+def _window_sums(window):
+    w = np.asarray(window.cpu().numpy() if hasattr(window, "cpu") else window)
+    if w.ndim != 1 or w.dtype.kind not in "iu":
+        raise TypeError("window must be a one-dimensional integer array (int16)")
+    w = w.astype(np.int64)
+    return w.size, int(w.sum()), int((w * w).sum())
+
+
+def window_scale(window) -> float:
+    """The `scale` of mdc_iq_spectrogram with which a full-scale "ci16" tone (amplitude 32768) on a bin reads 1.0, 0 dBFS:
+    1 / (32768 sum(w))^2.  ValueError unless sum(w) > 0."""
+    _, s1, _ = _window_sums(window)
+    if s1 <= 0:
+        raise ValueError(f"the window's values must sum to more than 0 (got {s1})")
+    return 1.0 / (32768.0 * s1) ** 2
+
+
+def window_enbw(window) -> float:
+    """Equivalent noise bandwidth in bins, nfft sum(w^2) / sum(w)^2: the factor by which the SUM of a noise-like signal's bins
+    overstates its power (1.5 for Hann).  ValueError unless sum(w) > 0."""
+    n, s1, s2 = _window_sums(window)
+    if s1 <= 0:
+        raise ValueError(f"the window's values must sum to more than 0 (got {s1})")
+    return n * s2 / float(s1) ** 2
+
+
+_default_windows: dict = {}      # (nfft, device) -> (int16 device tensor, scale)
+
+
+def _default_window(nfft: int, device):
+    import torch
+    key = (int(nfft), str(device))
+    if key not in _default_windows:
+        w = design_window(nfft)
+        _default_windows[key] = (torch.from_numpy(w).to(device), window_scale(w))
+    return _default_windows[key]
+
+
+def spectrogram(iq, sample_format, nfft: int = 1024, hop=None, avg: int = 1, window=None, device=None, scale=None):
+    """Averaged power spectra of a capture on the device (mdc_iq_spectrogram, include/mdc.h).  iq: as frames_from_iq.  Segments of
+    nfft pairs every `hop` pairs (default nfft // 2; hop > nfft skips pairs), each multiplied by the int16 `window` and
+    transformed; row r is the mean of segments r*avg .. r*avg + avg-1.  Returns the (rows, nfft) float32 device tensor in natural
+    DFT order (spectrum_freqs), rows = spectrogram_rows(pairs, nfft, hop, avg).  window: None = design_window(nfft), built once
+    per (nfft, device) and kept on the device; a numpy array (uploaded on every call); or an int16 device tensor, used where it
+    lies.  scale: None = window_scale(window) -- 1.0 is a full-scale "ci16" tone on a bin; for an explicit DEVICE window that
+    reads the window back (a synchronisation): pass scale to avoid it.  Otherwise the call enqueues on torch's current stream
+    without synchronising."""
+    import torch
+    fmt = sample_format_id(sample_format)
+    N = int(nfft)
+    H = N // 2 if hop is None else int(hop)
+    t = _device_samples(iq, fmt, device)
+    pairs = t.numel() * t.element_size() // _cabi.IQ_PAIR_BYTES[fmt]
+    if pairs * _cabi.IQ_PAIR_BYTES[fmt] != t.numel() * t.element_size():
+        raise ValueError("the capture is not a whole number of (I,Q) pairs")
+    lib = _cabi.lib()
+    rows = _cabi.check(lib.mdc_iq_spectrogram_rows(pairs, N, H, int(avg)))
+    if window is None:
+        w, default_scale = _default_window(N, t.device)
+    else:
+        if isinstance(window, torch.Tensor):
+            if window.dtype != torch.int16:
+                raise TypeError(f"window must be int16, got {window.dtype}")
+            w = window.to(t.device).contiguous().view(-1)
+        else:
+            h = np.asarray(window)
+            if h.dtype.kind not in "iu" or h.ndim != 1:
+                raise TypeError("window must be a one-dimensional integer array (int16)")
+            if h.size and (h.min() < -32768 or h.max() > 32767):
+                raise ValueError("window must fit int16")
+            w = torch.from_numpy(np.ascontiguousarray(h.astype(np.int16))).to(t.device)
+        default_scale = None
+    if w.numel() != N:
+        raise ValueError(f"the window has {w.numel()} values, nfft is {N}")
+    k = float(scale) if scale is not None else default_scale if default_scale is not None else window_scale(window)
+    out = torch.empty((rows, N), dtype=torch.float32, device=t.device)
+    with torch.cuda.device(t.device):
+        _cabi.check(lib.mdc_iq_spectrogram(t.data_ptr() if pairs else None, fmt, pairs, N, H, int(avg), w.data_ptr(), k,
+                                           out.data_ptr() if rows else None, rows, torch.cuda.current_stream(t.device).cuda_stream))
+    return out
+
+
+def spectrum_freqs(nfft: int) -> np.ndarray:
+    """The bins' frequencies in cycles per sample, in the natural order of spectrogram's columns: 0, 1/nfft, ... up to
+    0.5 - 1/nfft, then -0.5 ... -1/nfft.  All in [-0.5, 0.5)."""
+    return np.fft.fftfreq(int(nfft))
+
+
+def find_emitters(psd, threshold_db: float = 6.0, min_bins: int = 3, merge_bins: int = 2, dc_guard: int = 1, window=None):
+    """(centre, bandwidth, power_dbfs, snr_db) of every emitter in ONE power spectrum of nfft bins in natural order, for example
+    spectrogram(...).mean(0).cpu(); host numpy, float64.  The noise floor is the median bin.  Bins within dc_guard of bin 0
+    (both sides; dc_guard < 0: none) are set to the floor first: a tuner's DC spike is no emitter.  In centred order
+    (-0.5 .. 0.5) an emitter is a run of adjacent bins above floor * 10^(threshold_db / 10); runs separated by at most
+    merge_bins bins at or below the threshold are joined (the bins between them then belong to the run), and runs of fewer than
+    min_bins bins are dropped.  Per run: centre, the centroid of the power above the floor (bins below the floor count as 0), in
+    cycles per sample; bandwidth, the run's width in bins / nfft; power_dbfs, 10 log10 of the summed power above the floor,
+    divided by window_enbw(window) when the window is given (the bins of a noise-like signal overstate its power by that
+    factor); snr_db, the largest bin over the floor.  Returned in order of centre.  The spectrum is NOT treated as circular: a
+    signal straddling +-0.5 comes out as two emitters, one at each edge."""
+    from collections import namedtuple
+    Emitter = namedtuple("Emitter", "centre bandwidth power_dbfs snr_db")
+    p = np.array(psd.cpu().numpy() if hasattr(psd, "cpu") else psd, dtype=np.float64).reshape(-1)
+    n = p.size
+    if n < 2 or not np.all(np.isfinite(p)):
+        raise ValueError("psd must hold at least two finite bins")
+    floor = float(np.median(p))
+    if not floor > 0.0:
+        return []
+    if dc_guard >= 0:
+        p[np.arange(-int(dc_guard), int(dc_guard) + 1) % n] = floor
+    p = np.fft.fftshift(p)
+    f = np.fft.fftshift(np.fft.fftfreq(n))
+    above = np.flatnonzero(p > floor * 10.0 ** (float(threshold_db) / 10.0))
+    if above.size == 0:
+        return []
+    cut = np.flatnonzero(np.diff(above) > int(merge_bins) + 1)      # a gap of g bins is a difference of g + 1
+    first, last = above[np.r_[0, cut + 1]], above[np.r_[cut, above.size - 1]]
+    enbw = window_enbw(window) if window is not None else 1.0
+    found = []
+    for a, b in zip(first, last):
+        if b - a + 1 < int(min_bins):
+            continue
+        excess = np.maximum(p[a:b + 1] - floor, 0.0)
+        total = float(excess.sum())
+        found.append(Emitter(float((excess * f[a:b + 1]).sum() / total), float(b - a + 1) / n, 10.0 * np.log10(total / enbw),
+                             10.0 * np.log10(float(p[a:b + 1].max()) / floor)))
+    return found
+
+
+DEFAULT_FILL = 1.35 / 8      # occupied fraction of the output rate: a root-raised-cosine signal, beta 0.35, at 8 samples per symbol
+
+
+def channel_plan(centre: float, bandwidth: float, fill: float = DEFAULT_FILL, max_interpolate: int = _cabi.RESAMPLE_MAX_INTERPOLATE,
+                 max_decimate: int = _cabi.RESAMPLE_MAX_DECIMATE):
+    """(shift, L, D, fill_achieved) for an emitter of find_emitters: shift = -centre brings it to 0, and L / D in lowest terms is
+    the rational with L <= max_interpolate, D <= max_decimate closest to bandwidth / fill (resample_ratio's search): resampling by
+    L / D stretches every width by D / L, after which the emitter occupies fill_achieved = bandwidth * D / L of the output rate.  The default fill is what a root-raised-cosine
+    signal with beta = 0.35 occupies at the nets' 8 samples per symbol.  ValueError when nothing within the limits comes within
+    1 % of bandwidth / fill."""
+    from fractions import Fraction
+    centre, bandwidth, fill = float(centre), float(bandwidth), float(fill)
+    if not (np.isfinite(centre) and -0.5 <= centre <= 0.5):
+        raise ValueError(f"centre must lie in [-0.5, 0.5] cycles per sample (got {centre!r})")
+    if not (np.isfinite(bandwidth) and np.isfinite(fill) and bandwidth > 0 and fill > 0):
+        raise ValueError("bandwidth and fill must be finite and > 0")
+    Lmax, Dmax = _check_resample_factors(max_interpolate, max_decimate)
+    target = Fraction(bandwidth) / Fraction(fill)
+    err, f = _closest_ratio(target, Lmax, Dmax)
+    if err > target / 100:
+        raise ValueError(f"no L / D with L <= {Lmax}, D <= {Dmax} comes within 1 % of {float(target):.6g} "
+                         f"(fill {fill:g} of the output rate for a bandwidth of {bandwidth:g}); closest {f.numerator}/{f.denominator}")
+    return -centre, f.numerator, f.denominator, bandwidth * f.denominator / f.numerator
+
+
+def plan_taps(interpolate: int, decimate: int) -> np.ndarray:
+    """The filter VTCNN2.scan_iq puts behind a channel_plan: design_resampler(L, D) (for L == 1: design_lowpass(D)) with its default
+    8 max(L, D) taps where mdc_iq_resample's limit of 1024 taps allows them, else the same design cut to 1024 taps (max(L, D) > 128:
+    the transition band widens in proportion); L == D == 1, nothing to reject: one tap of (all but) unit gain."""
+    L, D = _check_resample_factors(interpolate, decimate)
+    if L == 1 and D == 1:
+        return np.array([32767], np.int16)
+    return design_resampler(L, D, ntaps=min(8 * max(L, D), _cabi.RESAMPLE_MAX_TAPS))

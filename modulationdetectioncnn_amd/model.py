@@ -965,6 +965,47 @@ class VTCNN2:
             return probs, labels, 10.0 * torch.log10(stats[:, 3].to(torch.float64) / F.full_scale_energy(fmt))
         return probs, labels
 
+    def scan_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_db: float = 6.0, hop: int = 128, level: float = 7.8e-3,
+                squelch_dbfs: Optional[float] = None, **find_kw):
+        """A wideband capture in, "what is transmitting where, and what modulation" out.  The capture's power spectrogram
+        (frontend.spectrogram: nfft bins, Hann window, segments nfft // 2 apart, `avg` of them per row, on the device) is averaged
+        over its rows into one spectrum; frontend.find_emitters(spectrum, threshold_db, window=the Hann window, **find_kw) lists
+        the emitters; each one is brought to 0 Hz and to the nets' rate by frontend.channel_plan's (shift, L, D) -- through
+        frontend.ddc when L == 1, else frontend.resample, with frontend.plan_taps(L, D) as the filter --, cut into windows `hop` output pairs apart
+        (hop == 128: the stream is trimmed to whole frames) and classified with predict_iq(..., "ci16", normalize="rms", level=,
+        squelch_dbfs=, return_power=True).  Returns one dict per emitter, in order of centre: centre, bandwidth (cycles per input
+        sample), power_dbfs, snr_db, shift, interpolate, decimate, probs, labels, window_dbfs (predict_iq's three results: device
+        tensors, or numpy arrays for a numpy capture) and label, the most frequent label among the windows the squelch let through
+        (the smallest on a tie; -1 if there are none)."""
+        torch = _torch()
+        from . import frontend as F
+        fmt = F.sample_format_id(sample_format)
+        as_numpy = not isinstance(iq, torch.Tensor)
+        dev = F._device_samples(iq, fmt, f"cuda:{self.device_index}")
+        window = F.design_window(nfft)
+        spec = F.spectrogram(dev, fmt, nfft=nfft, avg=avg)
+        if spec.shape[0] == 0:
+            raise ValueError(f"the capture is too short for one row of {avg} segments of {nfft} pairs")
+        psd = spec.to(torch.float64).mean(0).cpu().numpy()
+        out = []
+        for e in F.find_emitters(psd, threshold_db=threshold_db, window=window, **find_kw):
+            shift, L, D, _ = F.channel_plan(e.centre, e.bandwidth)
+            if L == 1:
+                down = F.ddc(dev, fmt, shift=shift, decimate=D, taps=F.plan_taps(L, D))
+            else:
+                down = F.resample(dev, fmt, shift=shift, interpolate=L, decimate=D, taps=F.plan_taps(L, D))
+            if hop == 128:
+                down = down[:down.shape[0] // 128 * 128]
+            probs, labels, dbfs = self.predict_iq(down.reshape(-1), _cabi.IQ_CI16, hop=hop, normalize="rms", level=level, squelch_dbfs=squelch_dbfs,
+                                                  return_power=True)
+            open_ = labels[labels >= 0]
+            label = int(torch.bincount(open_).argmax()) if open_.numel() else -1
+            if as_numpy:
+                probs, labels, dbfs = probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy()
+            out.append(dict(centre=e.centre, bandwidth=e.bandwidth, power_dbfs=e.power_dbfs, snr_db=e.snr_db, shift=shift, interpolate=L, decimate=D,
+                            labels=labels, probs=probs, window_dbfs=dbfs, label=label))
+        return out
+
     # ------------------------------------------------------------------ measurement hooks
     def set_profiling(self, on: bool) -> None:
         self._check(self._lib().mdc_set_profiling(self._engine(), int(on)))
