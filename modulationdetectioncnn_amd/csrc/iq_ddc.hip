@@ -4,24 +4,14 @@
 //   tile      the capture's outputs are cut into tiles of `tile_out` = (kDdcTilePairs - T) / D + 1 outputs: such a tile reads
 //             (tile_out - 1) D + T <= kDdcTilePairs input pairs, its own D tile_out and the T - D pairs of halo.  Work-groups
 //             stride over the tiles (grid cap kDdcGridCap).
-//   mix       each thread takes four adjacent pairs at a time (one unaligned 8- or 16-byte vector load; the capture's last,
-//             partial quads pair by pair with bounds), widens them to 16-bit full scale, reads the oscillator word of
-//             phi_n = phase0 + n step (mod 2^32: the low word of the 64-bit n suffices) from the table's copy in LDS, and
-//             writes m = x e^{j phi} / 2 as int16 into two PLANAR LDS images (re, im): adjacent samples share a dword.
-//   filter    one lane per output j: acc += dot2(m[jD + 2i], m[jD + 2i + 1]; h[2i], h[2i + 1]) with the packed 16-bit dot
-//             product (v_dot2c_i32_i16), the tap pairs uniform over the wave -- they are kernel ARGUMENTS (2 KiB by value: no
-//             copy to wait for, nothing to allocate, and the compiler reads them with scalar loads), zero-padded to whole
-//             groups of 8 dwords.  T odd: the last pair's second tap is that padding.  jD odd (only possible for odd D: the
-//             ODD instantiations): the output's first sample is the HIGH half of its dword; the lane then forms each operand
-//             from two neighbouring dwords with v_alignbit (shift 16; lanes with even jD shift by 0), the taps stay as they are.
-//   LDS       lane j starts at dword j D / 2: for D = 64 every lane of a wave would sit on ONE bank.  The images therefore skip
-//             one dword after every 32 (slot(i) = i + i / 32): a stride of 32 dwords becomes 33.
+//   mix       mix_tile of iq_mix.h: quads of pairs -> two planar int16 LDS images (re, im), 33-dword stride.
+//   filter    fir_output of iq_mix.h, one lane per output j from the local sample j D on, in groups of 8 tap dwords.  The tap
+//             pairs are uniform over the wave -- they are kernel ARGUMENTS (2 KiB by value: no copy to wait for, nothing to
+//             allocate, and the compiler reads them with scalar loads), zero-padded to whole groups.  T odd: the last pair's
+//             second tap is that padding.  j D odd is only possible for odd D: the ODD instantiations.
 // Everything the filter reads beyond the tile's last needed sample (the taps' zero padding times it) is still written by the
-// mix step -- zeros beyond the capture -- so the result never depends on stale LDS.  All sums are the exact integers of the
-// definition: |I c - Q s| + 32768 < 2^31, |acc| <= 32767 sum|h| <= 32767 * 65535, |acc| + 8192 < 2^31 (int32 wraps nowhere,
-// and a dot2 without clamp is plain modular arithmetic in any case).
-// The call only enqueues; vector memory for every store.  The loads, the table and the LDS geometry live in iq_mix.h
-// (mdc_iq_resample shares them).
+// mix step -- zeros beyond the capture -- so the result never depends on stale LDS.
+// The call only enqueues; vector memory for every store.  mdc_iq_resample shares the mix stage and the filter.
 #include "iq_mix.h"
 
 namespace mdc {
@@ -59,54 +49,12 @@ __global__ __launch_bounds__(kDdcThreads) void iq_ddc_kernel(const unsigned char
         const int span = (nout - 1) * D + 2 * kTapGroup * ngroups + 2;      // <= kDdcTilePairs + 17
         const int quads = (span + 3) >> 2;
         __syncthreads();      // the table is in place; the previous tile's filter has read its samples
-        for (int q = tid; q < quads; q += kDdcThreads) {
-            const long n = in0 + 4 * (long)q;
-            int I[4], Q[4], mr[4], mi[4];
-            load_quad<FMT>(iq, n, pairs, I, Q);
-            const unsigned phi = phase0 + (unsigned)(unsigned long)n * step;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const unsigned cs = nco[(phi + (unsigned)e * step) >> 20];
-                const int c = (int)(short)(cs & 0xFFFFu), s = (int)(short)(cs >> 16);
-                mr[e] = (I[e] * c - Q[e] * s + 32768) >> 16;
-                mi[e] = (I[e] * s + Q[e] * c + 32768) >> 16;
-            }
-            const int a = lds_slot(2 * q), b = lds_slot(2 * q + 1);
-            re[a] = ((unsigned)mr[0] & 0xFFFFu) | ((unsigned)mr[1] << 16);
-            re[b] = ((unsigned)mr[2] & 0xFFFFu) | ((unsigned)mr[3] << 16);
-            im[a] = ((unsigned)mi[0] & 0xFFFFu) | ((unsigned)mi[1] << 16);
-            im[b] = ((unsigned)mi[2] & 0xFFFFu) | ((unsigned)mi[3] << 16);
-        }
+        mix_tile<FMT>(iq, in0, pairs, phase0, step, quads, nco, re, im, tid);
         __syncthreads();
         for (int j = tid; j < nout; j += kDdcThreads) {
             const int start = j * D, base = start >> 1;
             const unsigned sh = (unsigned)(start & 1) << 4;
-            int ar = 0, ai = 0;
-            unsigned cr = 0, ci = 0;
-            if (ODD) { cr = re[lds_slot(base)]; ci = im[lds_slot(base)]; }
-            for (int g = 0; g < ngroups; ++g) {
-#pragma unroll
-                for (int u = 0; u < kTapGroup; ++u) {
-                    const unsigned tp = taps.pk[kTapGroup * g + u];
-                    unsigned wr, wi;
-                    if (ODD) {
-                        const int idx = lds_slot(base + kTapGroup * g + u + 1);
-                        const unsigned nr = re[idx], ni = im[idx];
-                        wr = __builtin_amdgcn_alignbit(nr, cr, sh);
-                        wi = __builtin_amdgcn_alignbit(ni, ci, sh);
-                        cr = nr;
-                        ci = ni;
-                    } else {
-                        const int idx = lds_slot(base + kTapGroup * g + u);
-                        wr = re[idx];
-                        wi = im[idx];
-                    }
-                    ar = dot2(wr, tp, ar);
-                    ai = dot2(wi, tp, ai);
-                }
-            }
-            const int r = sat16((ar + 8192) >> 14), i = sat16((ai + 8192) >> 14);
-            out[out0 + j] = ((unsigned)r & 0xFFFFu) | ((unsigned)i << 16);
+            out[out0 + j] = fir_output<ODD, kTapGroup>(re, im, base, sh, ngroups, [&](int k) { return taps.pk[k]; });
         }
     }
 }
@@ -154,10 +102,9 @@ int mdc_iq_ddc_nco_table(int16_t* cos_sin_host) {
 
 int mdc_iq_ddc(const void* iq_dev, int format, int64_t pairs_in, uint32_t phase0, uint32_t phase_step, int decimate, const int16_t* taps_host,
                int ntaps, int16_t* out_dev, int64_t n_out, void* hip_stream) {
-    const int pair_bytes = iq_pair_bytes(format);
-    if (pair_bytes == 0) { set_error("mdc_iq_ddc: unknown sample format %d (MDC_IQ_CU8, MDC_IQ_CI8, MDC_IQ_CI16)", format); return MDC_EINVAL; }
-    const int rc = ddc_shape_check("mdc_iq_ddc", pairs_in, ntaps, decimate);
+    int rc = iq_format_known("mdc_iq_ddc", format);
     if (rc != MDC_OK) return rc;
+    if ((rc = ddc_shape_check("mdc_iq_ddc", pairs_in, ntaps, decimate)) != MDC_OK) return rc;
     if (!taps_host) { set_error("mdc_iq_ddc: null taps"); return MDC_EINVAL; }
     long abs_sum = 0;
     for (int k = 0; k < ntaps; ++k) abs_sum += taps_host[k] < 0 ? -(long)taps_host[k] : (long)taps_host[k];
@@ -169,10 +116,7 @@ int mdc_iq_ddc(const void* iq_dev, int format, int64_t pairs_in, uint32_t phase0
         set_error("mdc_iq_ddc: n_out is %lld, mdc_iq_ddc_out_count gives %lld", (long long)n_out, (long long)ddc_out_count(pairs_in, ntaps, decimate));
         return MDC_EINVAL;
     }
-    if ((reinterpret_cast<uintptr_t>(iq_dev) & (uintptr_t)(pair_bytes - 1)) != 0) {
-        set_error("mdc_iq_ddc: input must start on a whole (I,Q) pair (%d-byte aligned)", pair_bytes);
-        return MDC_EINVAL;
-    }
+    if ((rc = iq_pair_aligned("mdc_iq_ddc", "input", format, iq_dev)) != MDC_OK) return rc;
     if ((reinterpret_cast<uintptr_t>(out_dev) & 3) != 0) { set_error("mdc_iq_ddc: output must be 4-byte aligned"); return MDC_EINVAL; }
     if (n_out == 0) return MDC_OK;
     if (!iq_dev || !out_dev) { set_error("mdc_iq_ddc: null buffer"); return MDC_EINVAL; }
@@ -183,8 +127,7 @@ int mdc_iq_ddc(const void* iq_dev, int format, int64_t pairs_in, uint32_t phase0
     const unsigned char* p = static_cast<const unsigned char*>(iq_dev);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     return guarded("mdc_iq_ddc", [&]() -> int {
-        if (format == MDC_IQ_CU8) return ddc_launch<MDC_IQ_CU8>(p, pairs_in, phase0, phase_step, decimate, ngroups, tile_out, n_out, out_dev, taps, s);
-        if (format == MDC_IQ_CI8) return ddc_launch<MDC_IQ_CI8>(p, pairs_in, phase0, phase_step, decimate, ngroups, tile_out, n_out, out_dev, taps, s);
-        return ddc_launch<MDC_IQ_CI16>(p, pairs_in, phase0, phase_step, decimate, ngroups, tile_out, n_out, out_dev, taps, s);
+        return with_format(format, [&](auto fmt) {
+            return ddc_launch<decltype(fmt)::value>(p, pairs_in, phase0, phase_step, decimate, ngroups, tile_out, n_out, out_dev, taps, s); });
     });
 }

@@ -6,19 +6,23 @@
 //   tile      `tile_out` = q L outputs with q = (kIqTilePairs - B) / D, B = ceil(T / L) the longest branch: such a tile starts
 //             at the input pair t q D EXACTLY (and at branch 0), so everything inside a tile is 32-bit arithmetic on local
 //             indices, and it reads at most q D + B <= kIqTilePairs pairs.  Work-groups stride over the tiles (kResGridCap).
-//   mix       the DDC's, through the shared loads of iq_mix.h: quads of pairs -> two planar int16 LDS images, 33-dword stride.
+//   mix       the DDC's, written out here: quads of pairs -> two planar int16 LDS images, 33-dword stride.
 //   taps      adjacent outputs use different branches, so the taps cannot be wave-uniform scalar operands as in the DDC.  The
 //             host reorders them BRANCH-MAJOR into packed pairs (branch r, dword u: h[r + 2uL] | h[r + (2u+1)L] << 16, zeros
 //             beyond T; every branch padded to whole groups of kResTapGroup dwords, the branch stride made ODD so that the L
 //             branches of a wave's lanes start on L different banks); that image travels by value as a kernel argument
 //             (<= kResTapDwords dwords: no copy to wait for, nothing to allocate) and each work-group copies it into LDS once.
-//   filter    one lane per output: acc += dot2(m[s + 2i], m[s + 2i + 1]; branch pair i) -- two sample dwords (re, im) and one
-//             tap dword from LDS per two dot products.  s odd (ODD instantiations: any class of outputs starts on an odd local
-//             sample): the lane forms each operand from two neighbouring dwords with v_alignbit, shift 16 or 0 per lane.
-//             An empty branch (r >= T) is all padding: its outputs are (0 + 8192) >> 14 = 0.
+//   filter    the DDC's, written out here with groups of kResTapGroup dwords: one lane per output from the local sample s on
+//             against its branch's pairs -- two sample dwords (re, im) and one tap dword from LDS per two dot products.  ODD
+//             instantiations: any class of outputs starts on an odd local sample.  An empty branch (r >= T) is all padding:
+//             its outputs are (0 + 8192) >> 14 = 0.
 // Everything the filter reads beyond the tile's last needed sample (the branches' zero padding times it) is still written by
 // the mix step -- zeros beyond the capture -- so the result never depends on stale LDS.  |acc| <= 32767 * 65535 per branch.
 // The call only enqueues; vector memory for every store.
+// iq_mix.h describes both stages and holds them as mix_tile and fir_output, which the DDC calls.  This kernel keeps its own
+// copies, line for line the same: with either call in its place rows of tools/resample_probe.py measured up to 6 % slower on the
+// MI355X, outside the spread of this code against itself (the rows: DESIGN.md 5.16, profiles/iq_frontend_ab.txt).  A change to
+// either stage is made in both places; tests/test_iq_resample_gpu.py::test_one_branch_is_the_ddc holds them to the same bits.
 #include "iq_mix.h"
 
 namespace mdc {
@@ -180,10 +184,9 @@ int64_t mdc_iq_resample_out_count(int64_t pairs_in, int ntaps, int interpolate, 
 
 int mdc_iq_resample(const void* iq_dev, int format, int64_t pairs_in, uint32_t phase0, uint32_t phase_step, int interpolate, int decimate,
                     const int16_t* taps_host, int ntaps, int16_t* out_dev, int64_t n_out, void* hip_stream) {
-    const int pair_bytes = iq_pair_bytes(format);
-    if (pair_bytes == 0) { set_error("mdc_iq_resample: unknown sample format %d (MDC_IQ_CU8, MDC_IQ_CI8, MDC_IQ_CI16)", format); return MDC_EINVAL; }
-    const int rc = resample_shape_check("mdc_iq_resample", pairs_in, ntaps, interpolate, decimate);
+    int rc = iq_format_known("mdc_iq_resample", format);
     if (rc != MDC_OK) return rc;
+    if ((rc = resample_shape_check("mdc_iq_resample", pairs_in, ntaps, interpolate, decimate)) != MDC_OK) return rc;
     if (!taps_host) { set_error("mdc_iq_resample: null taps"); return MDC_EINVAL; }
     for (int r = 0; r < interpolate && r < ntaps; ++r) {
         long abs_sum = 0;
@@ -199,10 +202,7 @@ int mdc_iq_resample(const void* iq_dev, int format, int64_t pairs_in, uint32_t p
         set_error("mdc_iq_resample: n_out is %lld, mdc_iq_resample_out_count gives %lld", (long long)n_out, (long long)want);
         return MDC_EINVAL;
     }
-    if ((reinterpret_cast<uintptr_t>(iq_dev) & (uintptr_t)(pair_bytes - 1)) != 0) {
-        set_error("mdc_iq_resample: input must start on a whole (I,Q) pair (%d-byte aligned)", pair_bytes);
-        return MDC_EINVAL;
-    }
+    if ((rc = iq_pair_aligned("mdc_iq_resample", "input", format, iq_dev)) != MDC_OK) return rc;
     if ((reinterpret_cast<uintptr_t>(out_dev) & 3) != 0) { set_error("mdc_iq_resample: output must be 4-byte aligned"); return MDC_EINVAL; }
     if (n_out == 0) return MDC_OK;
     if (!iq_dev || !out_dev) { set_error("mdc_iq_resample: null buffer"); return MDC_EINVAL; }
@@ -215,8 +215,6 @@ int mdc_iq_resample(const void* iq_dev, int format, int64_t pairs_in, uint32_t p
     const unsigned char* p = static_cast<const unsigned char*>(iq_dev);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     return guarded("mdc_iq_resample", [&]() -> int {
-        if (format == MDC_IQ_CU8) return resample_launch<MDC_IQ_CU8>(p, pairs_in, phase0, phase_step, plan, n_out, out_dev, taps, s);
-        if (format == MDC_IQ_CI8) return resample_launch<MDC_IQ_CI8>(p, pairs_in, phase0, phase_step, plan, n_out, out_dev, taps, s);
-        return resample_launch<MDC_IQ_CI16>(p, pairs_in, phase0, phase_step, plan, n_out, out_dev, taps, s);
+        return with_format(format, [&](auto fmt) { return resample_launch<decltype(fmt)::value>(p, pairs_in, phase0, phase_step, plan, n_out, out_dev, taps, s); });
     });
 }

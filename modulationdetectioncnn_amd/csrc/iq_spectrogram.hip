@@ -221,19 +221,15 @@ int64_t mdc_iq_spectrogram_rows(int64_t pairs_in, int nfft, int64_t hop, int avg
 
 int mdc_iq_spectrogram(const void* iq_dev, int format, int64_t pairs_in, int nfft, int64_t hop, int avg, const int16_t* window_dev, float scale,
                        float* power_dev, int64_t rows, void* hip_stream) {
-    const int pair_bytes = iq_pair_bytes(format);
-    if (pair_bytes == 0) { set_error("mdc_iq_spectrogram: unknown sample format %d (MDC_IQ_CU8, MDC_IQ_CI8, MDC_IQ_CI16)", format); return MDC_EINVAL; }
-    const int rc = spec_shape_check("mdc_iq_spectrogram", pairs_in, nfft, hop, avg);
+    int rc = iq_format_known("mdc_iq_spectrogram", format);
     if (rc != MDC_OK) return rc;
+    if ((rc = spec_shape_check("mdc_iq_spectrogram", pairs_in, nfft, hop, avg)) != MDC_OK) return rc;
     if (!(scale > 0.f) || !(scale <= 3.402823466e38f)) { set_error("mdc_iq_spectrogram: scale must be finite and > 0 (got %g)", (double)scale); return MDC_EINVAL; }
     if (rows != spec_rows(pairs_in, nfft, hop, avg)) {
         set_error("mdc_iq_spectrogram: rows is %lld, mdc_iq_spectrogram_rows gives %lld", (long long)rows, (long long)spec_rows(pairs_in, nfft, hop, avg));
         return MDC_EINVAL;
     }
-    if ((reinterpret_cast<uintptr_t>(iq_dev) & (uintptr_t)(pair_bytes - 1)) != 0) {
-        set_error("mdc_iq_spectrogram: iq_dev must start on a whole (I,Q) pair (%d-byte aligned)", pair_bytes);
-        return MDC_EINVAL;
-    }
+    if ((rc = iq_pair_aligned("mdc_iq_spectrogram", "iq_dev", format, iq_dev)) != MDC_OK) return rc;
     if ((reinterpret_cast<uintptr_t>(window_dev) & 1) != 0) { set_error("mdc_iq_spectrogram: window_dev must be 2-byte aligned"); return MDC_EINVAL; }
     if ((reinterpret_cast<uintptr_t>(power_dev) & 3) != 0) { set_error("mdc_iq_spectrogram: power_dev must be 4-byte aligned"); return MDC_EINVAL; }
     if (rows == 0) return MDC_OK;
@@ -243,8 +239,7 @@ int mdc_iq_spectrogram(const void* iq_dev, int format, int64_t pairs_in, int nff
     const unsigned char* p = static_cast<const unsigned char*>(iq_dev);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     return guarded("mdc_iq_spectrogram", [&]() -> int {
-        if (format == MDC_IQ_CU8) return spec_launch_fmt<MDC_IQ_CU8>(log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, s);
-        if (format == MDC_IQ_CI8) return spec_launch_fmt<MDC_IQ_CI8>(log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, s);
-        return spec_launch_fmt<MDC_IQ_CI16>(log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, s);
+        return with_format(format, [&](auto fmt) {
+            return spec_launch_fmt<decltype(fmt)::value>(log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, s); });
     });
 }

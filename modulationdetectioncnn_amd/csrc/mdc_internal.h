@@ -230,12 +230,24 @@ int iq_u8_launch(const uint8_t* iq, int64_t n, int64_t hop, float scale, float* 
 int iq_norm_check(const char* who, int64_t hop, float level, int flags);      // mdc_api.hip
 // iq_norm.hip: mdc_iq_u8_windows_norm behind its argument checks (x or stats may be NULL, not both)
 int iq_norm_launch(const uint8_t* iq, int64_t n, int64_t hop, float level, int flags, float* x, mdc_iq_window_stats* stats, hipStream_t s);
-// iq_formats.hip: mdc_iq_windows / mdc_iq_windows_norm behind their argument checks (MDC_IQ_CU8 frames: the two launchers above)
+// iq_formats.hip: what every raw-I/Q entry states once
+constexpr long kIqGridCap = 16384;      // work-groups of the window kernels; beyond it they stride
 int iq_pair_bytes(int format);      // 2 / 2 / 4; 0 for an unknown format
+// the two checks every raw-I/Q entry makes of its capture, each where the entry's order of errors has it:
+int iq_format_known(const char* who, int format);      // else `who: unknown sample format ...`
+// p starts on a whole pair of a known format, else `who: <what> must start on a whole (I,Q) pair ...` (what: the entry's word
+// for the capture, "input" or "iq_dev")
+int iq_pair_aligned(const char* who, const char* what, int format, const void* p);
 int iq_format_check(const char* who, int format, int64_t hop);
-int iq_fmt_windows_launch(const void* iq, int format, int64_t n, int64_t hop, float scale, float* x, hipStream_t s);
-int iq_fmt_norm_launch(const void* iq, int format, int64_t n, int64_t hop, float level, int flags, float* x, mdc_iq_window_stats64* stats,
-                       hipStream_t s);
+// the wave-per-window normaliser's MDC_IQ_CU8 instantiation with the record in 32-bit fields (n > 0; x or stats may be NULL)
+int iq_norm_wave_launch(const uint8_t* iq, int64_t n, int64_t hop, float level, int flags, float* x, mdc_iq_window_stats* stats, hipStream_t s);
+// fn(std::integral_constant<int, MDC_IQ_*>) for a format that iq_format_known has passed: the runtime format as a template argument
+template <class Fn>
+inline int with_format(int format, Fn&& fn) {
+    if (format == MDC_IQ_CU8) return fn(std::integral_constant<int, MDC_IQ_CU8>{});
+    if (format == MDC_IQ_CI8) return fn(std::integral_constant<int, MDC_IQ_CI8>{});
+    return fn(std::integral_constant<int, MDC_IQ_CI16>{});
+}
 // flags[i] = 1 iff frame i of x holds a NaN / +-Inf sample (else 0), *count += their number (count may be NULL); poison: the
 // flagged frames' probability rows become NaN and their labels 0 (probs / labels may be NULL).  mdc_forward_checked.
 int nonfinite_launch(const float* x, int64_t n, uint8_t* flags, int64_t* count, float* probs, int32_t* labels, int classes, bool poison,

@@ -7,7 +7,7 @@
     normalised two-call path (mdc_iq_u8_windows_norm + mdc_forward through predict_iq_u8(normalize="rms")).
 
 Writes profiles/iq_norm_timing.json (or --out).  Run it under `timeout`; it needs the GPU and has no fallback.
-    timeout -k 10 600 python tools/time_iq_norm.py [--windows 1048576] [--reps 30] [--out profiles/iq_norm_timing.json]"""
+    timeout -k 10 600 python tools/time_iq_norm.py [--windows 1048576] [--reps 30] [--out profiles/iq_norm_timing.json] [--lib PATH]"""
 import argparse
 import json
 import os
@@ -43,12 +43,15 @@ def main():
     ap.add_argument("--windows", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "iq_norm_timing.json"))
+    ap.add_argument("--lib", default=None, help="time this build of libmdc.so instead of the tree's (an A/B against a saved library)")
     a = ap.parse_args()
     if a.reps < 20:
         ap.error("--reps must be >= 20")
     if not torch.cuda.is_available():
         sys.exit("no ROCm device: nothing is measured without the GPU")
     n = a.windows
+    if a.lib:
+        _cabi.LIB_PATHS["product"] = os.path.abspath(a.lib)      # before the first use: lib() loads once
     L = _cabi.lib()
     stream = torch.cuda.current_stream().cuda_stream
     iq = torch.randint(0, 256, (n * 256,), dtype=torch.uint8, device="cuda")
