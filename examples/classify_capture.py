@@ -23,8 +23,13 @@ comes out -- in Hz when --rate is given, else in cycles per sample:
 
     python examples/classify_capture.py capture.bin --format ci16 --rate 2.4e6 --scan --nfft 1024 --threshold 6
 
+A band with a channel raster -- PMR / LMR, GSM, FM broadcast, ISM sub-bands -- is split into all its M evenly spaced channels in
+one pass instead (frontend.channelize, a polyphase filter bank on the device; VTCNN2.predict_channels), one line per channel:
+
+    python examples/classify_capture.py capture.bin --format ci16 --rate 2.4e6 --channels 16
+
 Without a capture file it classifies a synthetic one: bursts of tones at three gains with silence between them (--scan: a
-band of three QPSK emitters of different widths over noise and a DC offset)."""
+band of three QPSK emitters of different widths over noise and a DC offset; --channels: QPSK on two channels of the raster)."""
 import argparse
 import os
 import sys
@@ -90,6 +95,40 @@ def scan(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=
     return found
 
 
+def synthetic_raster(fmt="ci16", channels=16, seed=1, pairs=1 << 16):
+    """QPSK with a root-raised-cosine pulse (beta 0.35), 8 samples per symbol at the channelizer's default output rate 2 / M, on the
+    raster's channels 3 and M - 5, rms 0.05 of full scale each, over noise of rms 0.002."""
+    rng = np.random.default_rng(seed)
+    M, sps, beta, n, z = int(channels), 4 * int(channels), 0.35, np.arange(pairs), np.zeros(pairs, complex)
+    for k in (3, M - 5):
+        t = np.arange(-12 * sps, 12 * sps + 1) / sps + 1e-9          # (off the pulse's removable singularities)
+        h = (np.sin(np.pi * t * (1 - beta)) + 4 * beta * t * np.cos(np.pi * t * (1 + beta))) / (np.pi * t * (1 - (4 * beta * t) ** 2))
+        sym = rng.choice([-1.0, 1.0], pairs // sps + 2) + 1j * rng.choice([-1.0, 1.0], pairs // sps + 2)
+        up = np.zeros(sym.size * sps, complex)
+        up[::sps] = sym
+        base = np.convolve(up, h, mode="same")[:pairs]
+        z += 0.05 / np.sqrt(np.mean(np.abs(base) ** 2)) * base * np.exp(2j * np.pi * k / M * n)
+    z += 0.002 / np.sqrt(2) * (rng.standard_normal(pairs) + 1j * rng.standard_normal(pairs))
+    if fmt == "cu8":
+        return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * 127.5 + 127.5), 0, 255).astype(np.uint8).reshape(-1)
+    full, lo, hi = (128.0, -128, 127) if fmt == "ci8" else (32768.0, -32768, 32767)
+    return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * full), lo, hi).astype(DTYPES[fmt]).reshape(-1)
+
+
+def channels(model, iq, fmt, nchannels, rate=None, hop=128, level=7.8e-3, squelch=-60.0):
+    """Print one line per channel of the raster (VTCNN2.predict_channels: M = nchannels channels, each 2 x oversampled) and return
+    (labels, window dBFS, label per channel).  rate: the centres in Hz instead of cycles per sample."""
+    from modulationdetectioncnn_amd import frontend
+    _, labels, dbfs, label = model.predict_channels(iq[:iq.size // 2 * 2], fmt, nchannels, hop=hop, level=level, squelch_dbfs=squelch)
+    k, unit = (rate, "Hz") if rate else (1.0, "cyc/sample")
+    print(f"{nchannels} channels ({unit}), {labels.shape[1]} windows each")
+    print(f"{'centre':>12s} {'median dBFS':>12s} {'open':>6s} {'label':>6s}")
+    for fc, l, d, verdict in zip(frontend.channel_freqs(nchannels), labels, dbfs, label):
+        median = float(np.median(d)) if d.size else float("nan")
+        print(f"{fc * k:12.6g} {median:12.1f} {int((l >= 0).sum()):6d} {int(verdict):6d}")
+    return labels, dbfs, label
+
+
 def classify(model, iq, fmt, hop=128, level=7.8e-3, squelch=-35.0, shift=0.0, decimate=1, interpolate=1):
     """(probs, labels, dBFS) per window.  shift (cycles per sample, ADDED to the capture) / decimate: the capture is tuned,
     low-pass filtered (frontend.design_lowpass) and decimated on the device first, and the windows are cut from that stream.
@@ -144,7 +183,17 @@ def main():
     ap.add_argument("--scan", action="store_true", help="find the emitters in the band first and classify each one (ignores --shift-hz, --decimate, ...)")
     ap.add_argument("--nfft", type=int, default=1024, help="with --scan: bins of the spectrum (a power of two in 64..4096)")
     ap.add_argument("--threshold", type=float, default=6.0, help="with --scan: dB above the noise floor at which a bin belongs to an emitter")
+    ap.add_argument("--channels", type=int, default=0,
+                    help="split the band into this many evenly spaced channels (a power of two in 8..1024) and classify every one")
     a = ap.parse_args()
+    if a.channels:
+        iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_raster(a.format, a.channels)
+        if a.weights is None:
+            model = VTCNN2.synthetic("deployed3")
+        else:
+            model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
+        channels(model, iq, a.format, a.channels, rate=a.rate if a.rate != 1.0 else None, hop=a.hop, level=a.level, squelch=a.squelch)
+        return
     if a.scan:
         iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_band(a.format)
         if a.weights is None:

@@ -449,6 +449,50 @@ MDC_API int64_t mdc_iq_spectrogram_rows(int64_t pairs_in, int nfft, int64_t hop,
 MDC_API int mdc_iq_spectrogram(const void* iq_dev, int format, int64_t pairs_in, int nfft, int64_t hop, int avg,
                                const int16_t* window_dev, float scale, float* power_dev, int64_t rows, void* hip_stream);
 
+/* ---- channelizer: all M evenly spaced channels of a capture in one pass (additive in ABI 5) ---------------------------------
+ * A band with a channel raster (PMR / LMR, GSM, FM broadcast, ISM sub-bands) wants every channel at once.  M calls of mdc_iq_ddc
+ * read the capture M times and run M full-length filters; mdc_iq_channelizer is the polyphase filter bank that does it in one
+ * pass: per output step the prototype filter once (T multiply-adds, shared by all channels) and one M-point transform (the
+ * float64 numpy restatement is tests/iq_channelizer_ref.py).  Normatively, for the pairs_in = P input pairs x_n = (I_n, Q_n),
+ * n counted from iq_dev, with M = channels, D = decimate, T = ntaps, s = tap_shift:
+ *   widening   to 16-bit full scale, as in mdc_iq_ddc: MDC_IQ_CU8 (2*byte - 255)*128, MDC_IQ_CI8 s*256, MDC_IQ_CI16 s
+ *              (|.| <= 32768; 0 dBFS stays 0 dBFS).
+ *   taps       h_0 .. h_{T-1}: int16 at taps_dev (a DEVICE buffer, like the spectrogram's window: up to 32 KiB do not travel
+ *              with a launch), applied as written (no reversal), in Q(15+s): DC gain 1 is a sum of 32768 * 2^s.  (A unit sum
+ *              of 32768 spread over 8 M taps leaves the largest tap near 100 at M = 1024 and a stop band of 35 dB: the shift
+ *              is what keeps the taps' precision.)
+ *              Hard precondition, mdc_iq_resample's per-branch rule: for EVERY residue r in 0 .. M-1, sum_i |h_{r+iM}| <= 65535.
+ *              The taps lie on the device and reading them back would be a synchronisation: the call does NOT validate them.
+ *              The precondition is the caller's; with taps that break it the call is still memory-safe, only the values wrap.
+ *   branch sums   for output j and residue r: v_j[r] = sum over t in 0 .. T-1 with (first_index + j D + t) mod M == r of
+ *              h_t x_{jD+t}, re and im separately, int32; |v| <= 32768 * 65535 < 2^31: 32-bit accumulation is exact.  A residue
+ *              without taps (possible when T < M) gives 0.
+ *   transform  Y_j[k] = sum_r v_j[r] e^{-2 pi i k r / M}, k = 0 .. M-1, in float32 on v converted to f32, twiddle factors rounded
+ *              from float64 (a table: no device sines).  This is
+ *                  Y_j[k] = sum_t h_t x_{jD+t} e^{-2 pi i k (first_index + j D + t) / M}:
+ *              channel k is the capture shifted by -k/M cycles per sample, the phase referenced to ABSOLUTE sample index 0
+ *              (first_index is the absolute index of the pair at iq_dev), low-passed by h and decimated by D -- what mdc_iq_ddc
+ *              does with phase_step = -k 2^32 / M and phase0 = first_index * phase_step, without its oscillator table's
+ *              rounding.  Channel k is centred at k/M cycles per sample; k >= M/2 are the negative frequencies.
+ *   output     out[k][j] = clamp(rint(Y_j[k] * 2^-(15+s)), -32768, 32767) (round half to even), re and im: int16 pairs,
+ *              CHANNEL-MAJOR: out_dev holds M rows of n_out pairs, every row an ordinary MDC_IQ_CI16 capture for
+ *              mdc_iq_windows / mdc_iq_windows_norm.  n_out = P >= T ? (P - T) / D + 1 : 0: a "valid" convolution.  The
+ *              filter's group delay is not compensated.
+ * With u = 2^-24 and eps = 8u (log2 M + 1) every output lies within 0.5 + eps S_j 2^-(15+s) of the unrounded, clamped
+ * definition, S_j = sqrt(sum_k |Y_j[k]|^2) -- the spectrogram's bound, in amplitude form, plus the final rounding.
+ * The same inputs give the same bits on every run; column j of a call does not depend on what else the call computes; a call on
+ * the pairs from a on, a a multiple of D, with first_index + a returns the whole call's columns from j0 = a / D on, bit for
+ * bit.
+ * channels: a power of two in 8..1024; 1 <= decimate <= channels; 1 <= ntaps <= 16 * channels; 0 <= tap_shift <= 15;
+ * first_index >= 0 (only its value mod M matters); n_out must equal mdc_iq_channelizer_out_count.  iq_dev is aligned to one
+ * pair (2 / 2 / 4 bytes), taps_dev to 2 bytes, out_dev to 4 bytes.  Every argument error is MDC_EINVAL before any device call.
+ * n_out == 0 is MDC_OK (nothing is launched; the buffers may be NULL); otherwise no buffer may be NULL.  The call only enqueues
+ * on hip_stream (no synchronisation, no allocation, no copy: capturable in a hipGraph) and runs on the current device.
+ * mdc_iq_channelizer_out_count returns n_out, or a negative MDC_EINVAL. */
+MDC_API int64_t mdc_iq_channelizer_out_count(int64_t pairs_in, int channels, int ntaps, int decimate);
+MDC_API int mdc_iq_channelizer(const void* iq_dev, int format, int64_t pairs_in, int64_t first_index, int channels, int decimate,
+                               const int16_t* taps_dev, int ntaps, int tap_shift, int16_t* out_dev, int64_t n_out, void* hip_stream);
+
 /* test_Y_hat = model.predict(X_test, batch_size=batch_size)  (cnn.py:198, 237) when X_test lies in HOST memory -- a
  * numpy array, or whatever buffer a cgo / JNI / N-API caller holds: the library's own driver in front of mdc_forward.
  * Frames are copied into a pinned ring by a few host threads, DMA'd, computed and the results DMA'd back in three

@@ -37,6 +37,7 @@ EXPORTS = [
     "mdc_iq_ddc", "mdc_iq_ddc_out_count", "mdc_iq_ddc_nco_table",
     "mdc_iq_resample", "mdc_iq_resample_out_count",
     "mdc_iq_spectrogram", "mdc_iq_spectrogram_rows",
+    "mdc_iq_channelizer", "mdc_iq_channelizer_out_count",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
@@ -63,6 +64,18 @@ RESAMPLE_TILE_PAIRS, RESAMPLE_GRID_CAP = 8192, 1024
 # row, at most SPECTROGRAM_GRID_CAP of them; more rows are walked in passes
 SPECTROGRAM_MIN_NFFT, SPECTROGRAM_MAX_NFFT, SPECTROGRAM_MAX_AVG = 64, 4096, 4096
 SPECTROGRAM_GRID_CAP = 2048
+# mdc_iq_channelizer: limits of include/mdc.h (channels a power of two in MIN..MAX, decimate <= channels, ntaps <= 16 per channel,
+# per-residue sum |h| <= 65535), and the kernel's tiling (csrc/iq_channelizer.hip: kChanGridCap, chan_tile_steps): a work-group
+# owns channelizer_tile_steps(channels) consecutive output steps, at most CHANNELIZER_GRID_CAP work-groups; more tiles are
+# walked in passes
+CHANNELIZER_MIN_CHANNELS, CHANNELIZER_MAX_CHANNELS, CHANNELIZER_MAX_TAPS_PER_CHANNEL, CHANNELIZER_MAX_TAP_SHIFT = 8, 1024, 16, 15
+CHANNELIZER_MAX_BRANCH_ABS_SUM = 65535
+CHANNELIZER_GRID_CAP = 2048
+
+
+def channelizer_tile_steps(channels: int) -> int:
+    """Output steps one work-group of mdc_iq_channelizer owns at a time: max(16, 1024 / channels)."""
+    return max(16, 1024 // int(channels))
 # mdc_forward_q612: the kernel's walk (csrc/deployed_q612.hip: kQGridCap, kQBlockFrames) for tests and tools -- at most Q612_GRID_CAP
 # work-groups of 4 waves, each wave taking Q612_BLOCK_FRAMES frames at a time; more frames than that product are walked in passes
 Q612_GRID_CAP, Q612_BLOCK_FRAMES = 2048, 64
@@ -143,7 +156,8 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_iq_ddc_nco_table", [vp]),
                        ("mdc_iq_ddc", [vp, i32, i64, C.c_uint32, C.c_uint32, i32, vp, i32, vp, i64, vp]),
                        ("mdc_iq_resample", [vp, i32, i64, C.c_uint32, C.c_uint32, i32, i32, vp, i32, vp, i64, vp]),
-                       ("mdc_iq_spectrogram", [vp, i32, i64, i32, i64, i32, vp, C.c_float, vp, i64, vp])):
+                       ("mdc_iq_spectrogram", [vp, i32, i64, i32, i64, i32, vp, C.c_float, vp, i64, vp]),
+                       ("mdc_iq_channelizer", [vp, i32, i64, i64, i32, i32, vp, i32, i32, vp, i64, vp])):
         fn = getattr(L, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, i32
@@ -153,6 +167,8 @@ def lib(variant: str = "product") -> C.CDLL:
         L.mdc_iq_resample_out_count.argtypes, L.mdc_iq_resample_out_count.restype = [i64, i32, i32, i32], i64
     if getattr(L, "mdc_iq_spectrogram_rows", None) is not None:
         L.mdc_iq_spectrogram_rows.argtypes, L.mdc_iq_spectrogram_rows.restype = [i64, i32, i64, i32], i64
+    if getattr(L, "mdc_iq_channelizer_out_count", None) is not None:
+        L.mdc_iq_channelizer_out_count.argtypes, L.mdc_iq_channelizer_out_count.restype = [i64, i32, i32, i32], i64
     fp = C.POINTER(C.c_float)
     L.mdc_trainer_create.argtypes = [C.POINTER(MdcTopology), i32, C.POINTER(vp)]
     L.mdc_trainer_num_layers.argtypes = [vp]

@@ -634,3 +634,148 @@ def plan_taps(interpolate: int, decimate: int) -> np.ndarray:
     if L == 1 and D == 1:
         return np.array([32767], np.int16)
     return design_resampler(L, D, ntaps=min(8 * max(L, D), _cabi.RESAMPLE_MAX_TAPS))
+
+
+# ---- channelizer (mdc_iq_channelizer): all M evenly spaced channels of a capture in one pass -- a polyphase filter bank ------
+def _check_channels(channels) -> int:
+    M = int(channels)
+    if not (_cabi.CHANNELIZER_MIN_CHANNELS <= M <= _cabi.CHANNELIZER_MAX_CHANNELS and M & (M - 1) == 0):
+        raise ValueError(f"channels must be a power of two in {_cabi.CHANNELIZER_MIN_CHANNELS}..{_cabi.CHANNELIZER_MAX_CHANNELS} (got {channels!r})")
+    return M
+
+
+def _check_channelizer_taps(h, M: int) -> np.ndarray:
+    """host taps for mdc_iq_channelizer -> contiguous int16, or TypeError / ValueError: the checks the library cannot make of a
+    device buffer without a synchronisation"""
+    h = np.asarray(h)
+    if h.dtype.kind not in "iu" or h.ndim != 1:
+        raise TypeError("taps must be a one-dimensional integer array (int16)")
+    if not 1 <= h.size <= _cabi.CHANNELIZER_MAX_TAPS_PER_CHANNEL * M:
+        raise ValueError(f"ntaps must be in 1..{_cabi.CHANNELIZER_MAX_TAPS_PER_CHANNEL * M} for {M} channels (got {h.size})")
+    if h.min() < -32768 or h.max() > 32767:
+        raise ValueError("taps must fit int16")
+    a = np.abs(h.astype(np.int64))
+    for r in range(min(M, h.size)):
+        total = int(a[r::M].sum())
+        if total > _cabi.CHANNELIZER_MAX_BRANCH_ABS_SUM:
+            raise ValueError(f"residue {r} of the taps has sum |h| = {total}: mdc_iq_channelizer wants <= {_cabi.CHANNELIZER_MAX_BRANCH_ABS_SUM} "
+                             f"per residue mod {M}")
+    return np.ascontiguousarray(h.astype(np.int16))
+
+
+def design_channelizer(channels: int, taps_per_channel: int = 8, cutoff=None, beta: float = 8.0):
+    """(taps int16, tap_shift): the prototype low-pass of an M = channels channel filter bank for mdc_iq_channelizer.  A
+    Kaiser-windowed sinc of taps_per_channel * M taps whose -6 dB point lies at `cutoff` cycles per input sample (default 0.5 / M,
+    the channel edge: neighbouring channels cross at -6 dB), in Q(15 + tap_shift) with tap_shift = log2(M) - 1: scaled to sum
+    exactly 32768 * 2^tap_shift (DC gain 1), rounded, the centre tap(s) taking what is missing so that the taps stay symmetric.
+    ValueError if a tap leaves int16 or a residue's sum |h| exceeds 65535.
+
+    With the defaults, for M in {8, 16, 64, 256, 1024} (from the taps themselves, dense FFT): droop <= 0.1 dB over |f| <= 0.25 / M
+    (0.068 .. 0.078 dB), -6.0 +- 0.1 dB at 0.5 / M, >= 75 dB attenuation for |f| >= 0.85 / M (76.1 .. 80.7 dB); the largest tap
+    is about 16,380 and the largest residue's sum |h| about 24,600.  (A plain Q15 unit sum would leave the largest tap near 100 at
+    M = 1024: the shift is what keeps the stop band.)
+
+    Aliasing: a decimation by D folds the frequency f (relative to the channel's centre) onto f - m / D.  With D = M / 2 the output
+    rate is 2 / M and its band |f'| <= 1 / M; whatever folds INTO that band comes from |f| >= 2 / M - 1 / M = 1 / M, which lies in
+    the stop band: over the whole output band every alias is >= 75 dB down, and the transition band 0.5 / M .. 0.85 / M, where
+    the neighbours leak in, stays where it is, outside the channel.  With D = M (critically sampled) the output band is
+    |f'| <= 0.5 / M and the transition band folds back onto 0.15 / M .. 0.5 / M: only |f'| <= 0.15 / M is alias-free to 75 dB.
+    Group delay: (ntaps - 1) / 2 input samples."""
+    M = _check_channels(channels)
+    tpc = int(taps_per_channel)
+    if not 1 <= tpc <= _cabi.CHANNELIZER_MAX_TAPS_PER_CHANNEL:
+        raise ValueError(f"taps_per_channel must be in 1..{_cabi.CHANNELIZER_MAX_TAPS_PER_CHANNEL} (got {taps_per_channel!r})")
+    fc = 0.5 / M if cutoff is None else float(cutoff)
+    if not 0.0 < fc <= 0.5:
+        raise ValueError(f"cutoff must lie in (0, 0.5] cycles per sample (got {fc!r})")
+    T, shift = tpc * M, M.bit_length() - 2
+    total = 32768 << shift
+    k = np.arange(T, dtype=np.float64) - (T - 1) / 2.0
+    h = 2.0 * fc * np.sinc(2.0 * fc * k) * np.kaiser(T, float(beta))
+    q = np.rint(h / h.sum() * float(total)).astype(np.int64)
+    rest = total - int(q.sum())      # T is even: symmetric taps sum to an even number, both centre taps take half of what is missing
+    q[T // 2 - 1] += rest // 2
+    q[T // 2] += rest - rest // 2
+    if q.min() < -32768 or q.max() > 32767 or max(int(np.abs(q[r::M]).sum()) for r in range(M)) > _cabi.CHANNELIZER_MAX_BRANCH_ABS_SUM:
+        raise ValueError("these parameters give taps outside int16 / a residue beyond the sum |h| <= 65535 of mdc_iq_channelizer")
+    return q.astype(np.int16), shift
+
+
+def channelizer_out_count(pairs_in: int, channels: int, ntaps: int, decimate: int) -> int:
+    """mdc_iq_channelizer_out_count: output pairs PER CHANNEL of a capture of pairs_in pairs, (pairs_in - ntaps) // decimate + 1 or
+    0 (a "valid" convolution)."""
+    return _cabi.check(_cabi.lib().mdc_iq_channelizer_out_count(int(pairs_in), int(channels), int(ntaps), int(decimate)))
+
+
+def channel_freqs(channels: int) -> np.ndarray:
+    """The channels' centres in cycles per input sample, in the order of channelize's rows: k / M folded into [-0.5, 0.5) --
+    0, 1/M, ... up to 0.5 - 1/M, then -0.5 ... -1/M."""
+    return np.fft.fftfreq(_check_channels(channels))
+
+
+_default_channelizers: dict = {}      # (channels, device) -> (int16 device tensor, tap_shift)
+
+
+def _default_channelizer(channels: int, device):
+    import torch
+    key = (int(channels), str(device))
+    if key not in _default_channelizers:
+        h, shift = design_channelizer(channels)
+        _default_channelizers[key] = (torch.from_numpy(h).to(device), shift)
+    return _default_channelizers[key]
+
+
+def channelize(iq, sample_format, channels: int, decimate=None, taps=None, tap_shift=None, first_index: int = 0, whole_frames: bool = False,
+               device=None):
+    """Split a capture into M = channels evenly spaced channels in one pass on the device (mdc_iq_channelizer, include/mdc.h: exact
+    integer branch sums, one float32 M-point transform per output step).  iq: as frames_from_iq.  Returns the (M, n_out, 2) int16
+    device tensor: row k is the capture shifted by -k / M cycles per sample (channel_freqs; the phase referenced to absolute sample
+    first_index at iq's first pair), low-passed by the taps and decimated by `decimate` -- an ordinary "ci16" capture for
+    frames_from_iq / normalized_frames_from_iq / VTCNN2.predict_iq; n_out = channelizer_out_count(pairs, M, ntaps, decimate).
+
+    decimate: None = M / 2.  The channels are then 2 x oversampled: the output rate 2 / M is twice the channel spacing, so the
+    filter's transition band beyond the channel edge 0.5 / M stays inside the output band instead of folding back onto the
+    channel -- nothing aliases onto a channel that the prototype has not taken down to its stop band (design_channelizer).  M
+    (critically sampled) halves the output but folds each channel's edges onto itself.
+    taps: None = design_channelizer(M), built once per (M, device) and kept on the device; a numpy array, int16 in Q(15 + tap_shift),
+    validated (int16, per-residue sum |h| <= 65535) and uploaded on every call; or an int16 device tensor, used where it lies and
+    NOT validated -- the precondition is then the caller's.  tap_shift: required with explicit taps.
+    whole_frames: use only as many input pairs as give the largest n_out that is a multiple of 128 (hop == 128 windows then never
+    straddle two channels of the flat block).  Enqueues on torch's current stream without synchronising."""
+    import torch
+    fmt = sample_format_id(sample_format)
+    M = _check_channels(channels)
+    D = M // 2 if decimate is None else int(decimate)
+    t = _device_samples(iq, fmt, device)
+    pairs = t.numel() * t.element_size() // _cabi.IQ_PAIR_BYTES[fmt]
+    if pairs * _cabi.IQ_PAIR_BYTES[fmt] != t.numel() * t.element_size():
+        raise ValueError("the capture is not a whole number of (I,Q) pairs")
+    if int(first_index) < 0:
+        raise ValueError("first_index must be >= 0")
+    if taps is None:
+        if tap_shift is not None:
+            raise ValueError("tap_shift belongs to explicit taps (the default design brings its own)")
+        h, shift = _default_channelizer(M, t.device)
+    else:
+        if tap_shift is None:
+            raise ValueError("explicit taps need their tap_shift (the taps are Q(15 + tap_shift))")
+        shift = int(tap_shift)
+        if isinstance(taps, torch.Tensor):
+            if taps.dtype != torch.int16:
+                raise TypeError(f"taps must be int16, got {taps.dtype}")
+            h = taps.to(t.device).contiguous().view(-1)
+        else:
+            h = torch.from_numpy(_check_channelizer_taps(taps, M)).to(t.device)
+    if not 0 <= shift <= _cabi.CHANNELIZER_MAX_TAP_SHIFT:
+        raise ValueError(f"tap_shift must be in 0..{_cabi.CHANNELIZER_MAX_TAP_SHIFT} (got {shift})")
+    T = h.numel()
+    lib = _cabi.lib()
+    n_out = _cabi.check(lib.mdc_iq_channelizer_out_count(pairs, M, T, D))
+    if whole_frames:
+        n_out = n_out // HOP_FRAME * HOP_FRAME
+        pairs = (n_out - 1) * D + T if n_out else 0
+    out = torch.empty((M, n_out, 2), dtype=torch.int16, device=t.device)
+    with torch.cuda.device(t.device):
+        _cabi.check(lib.mdc_iq_channelizer(t.data_ptr() if pairs else None, fmt, pairs, int(first_index), M, D, h.data_ptr(), T, shift,
+                                           out.data_ptr() if n_out else None, n_out, torch.cuda.current_stream(t.device).cuda_stream))
+    return out

@@ -1006,6 +1006,39 @@ class VTCNN2:
                             labels=labels, probs=probs, window_dbfs=dbfs, label=label))
         return out
 
+    def predict_channels(self, iq, sample_format, channels: int, decimate: Optional[int] = None, taps=None, tap_shift: Optional[int] = None,
+                         hop: int = 128, level: float = 7.8e-3, squelch_dbfs: Optional[float] = None, batch_size: int = 0):
+        """A band with a channel raster in, "what is on every channel" out.  The capture is split into M = channels evenly spaced
+        channels in one pass (frontend.channelize(iq, sample_format, channels, decimate, taps, tap_shift, whole_frames=True):
+        decimate=None is M / 2, taps=None frontend.design_channelizer(M)), and every channel's stream is cut into windows `hop`
+        output pairs apart and classified with predict_iq(..., "ci16", normalize="rms", level=, squelch_dbfs=, return_power=True).
+        With hop == 128 that is ONE predict_iq call over the flat (M * n_out) block: the rows are whole frames, so no window
+        straddles two channels; other hops go channel by channel.  Returns probs (M, W, C), labels (M, W), window_dbfs (M, W) and
+        label (M,), int64: per channel the most frequent label among the windows the squelch let through (the smallest on a tie;
+        -1 if there are none) -- scan_iq's rule.  Row k is the channel centred at frontend.channel_freqs(M)[k].  Device tensors
+        for a device capture, numpy arrays for a numpy capture."""
+        torch = _torch()
+        from . import frontend as F
+        fmt = F.sample_format_id(sample_format)
+        as_numpy = not isinstance(iq, torch.Tensor)
+        down = F.channelize(iq, fmt, channels, decimate=decimate, taps=taps, tap_shift=tap_shift, whole_frames=True,
+                            device=f"cuda:{self.device_index}")
+        M, n_out = down.shape[0], down.shape[1]
+        kw = dict(batch_size=batch_size, hop=hop, normalize="rms", level=level, squelch_dbfs=squelch_dbfs, return_power=True)
+        if hop == 128:
+            probs, labels, dbfs = self.predict_iq(down.view(-1), _cabi.IQ_CI16, **kw)
+            W = n_out // 128
+            probs, labels, dbfs = probs.view(M, W, self.topology.classes), labels.view(M, W), dbfs.view(M, W)
+        else:
+            per = [self.predict_iq(down[k].reshape(-1), _cabi.IQ_CI16, **kw) for k in range(M)]
+            probs, labels, dbfs = (torch.stack([p[i] for p in per]) for i in range(3))
+        classes = torch.arange(self.topology.classes, dtype=labels.dtype, device=labels.device)
+        counts = (labels[:, :, None] == classes).sum(1)      # (M, C): squelched windows (-1) count for no class
+        label = torch.where(counts.sum(1) > 0, counts.argmax(1), torch.full((M,), -1, dtype=torch.int64, device=labels.device))
+        if as_numpy:
+            return probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy(), label.cpu().numpy()
+        return probs, labels, dbfs, label
+
     # ------------------------------------------------------------------ measurement hooks
     def set_profiling(self, on: bool) -> None:
         self._check(self._lib().mdc_set_profiling(self._engine(), int(on)))
