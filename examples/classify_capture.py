@@ -23,6 +23,10 @@ comes out -- in Hz when --rate is given, else in cycles per sample:
 
     python examples/classify_capture.py capture.bin --format ci16 --rate 2.4e6 --scan --nfft 1024 --threshold 6
 
+With --refine the scan takes each emitter's symbol rate and carrier from its spectral lines instead of its width and centroid
+(frontend.estimate_symbol_rate, estimate_carrier_offset: the spectra of |x|^2 and of x^2 / x^4, on the device) and prints them
+as two more columns.
+
 A band with a channel raster -- PMR / LMR, GSM, FM broadcast, ISM sub-bands -- is split into all its M evenly spaced channels in
 one pass instead (frontend.channelize, a polyphase filter bank on the device; VTCNN2.predict_channels), one line per channel:
 
@@ -82,16 +86,24 @@ def synthetic_band(fmt="ci16", seed=1, pairs=1 << 18):
     return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * full), lo, hi).astype(DTYPES[fmt]).reshape(-1)
 
 
-def scan(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0):
-    """Print one line per emitter of the capture (VTCNN2.scan_iq) and return the records.  rate: Hz columns instead of cycles per sample."""
-    found = model.scan_iq(iq[:iq.size // 2 * 2], fmt, nfft=nfft, threshold_db=threshold_db, hop=hop, level=level, squelch_dbfs=squelch)
+def scan(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0, refine=False):
+    """Print one line per emitter of the capture (VTCNN2.scan_iq) and return the records.  rate: Hz columns instead of cycles per sample.
+    refine: symbol rate and carrier from the emitter's spectral lines (scan_iq's refine=True), as two more columns -- the symbol
+    rate ("-" where no line was found) and the refined centre."""
+    found = model.scan_iq(iq[:iq.size // 2 * 2], fmt, nfft=nfft, threshold_db=threshold_db, hop=hop, level=level, squelch_dbfs=squelch,
+                          refine=refine)
     k, unit = (rate, "Hz") if rate else (1.0, "cyc/sample")
     print(f"{len(found)} emitters ({unit})")
-    print(f"{'centre':>12s} {'bandwidth':>12s} {'dBFS':>7s} {'SNR dB':>7s} {'L/D':>7s} {'windows':>8s} {'open':>6s} {'label':>6s}")
+    print(f"{'centre':>12s} {'bandwidth':>12s} {'dBFS':>7s} {'SNR dB':>7s} {'L/D':>7s} {'windows':>8s} {'open':>6s} {'label':>6s}"
+          + (f" {'symbol rate':>12s} {'refined':>12s}" if refine else ""))
     for e in found:
         labels = np.asarray(e["labels"])
+        more = ""
+        if refine:
+            symbol = "-" if e["symbol_rate"] is None else f"{e['symbol_rate'] * k:.6g}"
+            more = f" {symbol:>12s} {(e['centre'] + e['carrier_offset']) * k:12.8g}"
         print(f"{e['centre'] * k:12.6g} {e['bandwidth'] * k:12.6g} {e['power_dbfs']:7.1f} {e['snr_db']:7.1f} "
-              f"{str(e['interpolate']) + '/' + str(e['decimate']):>7s} {labels.size:8d} {int((labels >= 0).sum()):6d} {e['label']:6d}")
+              f"{str(e['interpolate']) + '/' + str(e['decimate']):>7s} {labels.size:8d} {int((labels >= 0).sum()):6d} {e['label']:6d}{more}")
     return found
 
 
@@ -183,6 +195,8 @@ def main():
     ap.add_argument("--scan", action="store_true", help="find the emitters in the band first and classify each one (ignores --shift-hz, --decimate, ...)")
     ap.add_argument("--nfft", type=int, default=1024, help="with --scan: bins of the spectrum (a power of two in 64..4096)")
     ap.add_argument("--threshold", type=float, default=6.0, help="with --scan: dB above the noise floor at which a bin belongs to an emitter")
+    ap.add_argument("--refine", action="store_true",
+                    help="with --scan: symbol rate and carrier of each emitter from its spectral lines; two more columns")
     ap.add_argument("--channels", type=int, default=0,
                     help="split the band into this many evenly spaced channels (a power of two in 8..1024) and classify every one")
     a = ap.parse_args()
@@ -201,7 +215,7 @@ def main():
         else:
             model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
         scan(model, iq, a.format, nfft=a.nfft, threshold_db=a.threshold, rate=a.rate if a.rate != 1.0 else None, hop=a.hop, level=a.level,
-             squelch=a.squelch)
+             squelch=a.squelch, refine=a.refine)
         return
     if a.symbol_rate is not None:
         from modulationdetectioncnn_amd import frontend

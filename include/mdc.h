@@ -55,7 +55,9 @@ extern "C" {
                                   mdc_iq_ddc / mdc_iq_ddc_out_count / mdc_iq_ddc_nco_table (frequency shift, low-pass and
                                   decimation of a raw capture, exact integers);
                                   mdc_iq_resample / mdc_iq_resample_out_count (the same with a rational factor L/D);
-                                  mdc_iq_spectrogram / mdc_iq_spectrogram_rows (averaged power spectra of a raw capture) */
+                                  mdc_iq_spectrogram / mdc_iq_spectrogram_rows (averaged power spectra of a raw capture);
+                                  mdc_iq_line_spectrum (the same of the capture's envelope, square or fourth power: the
+                                  spectral lines at the symbol rate and at 2 / 4 times the carrier offset) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -448,6 +450,33 @@ MDC_API int mdc_iq_resample(const void* iq_dev, int format, int64_t pairs_in, ui
 MDC_API int64_t mdc_iq_spectrogram_rows(int64_t pairs_in, int nfft, int64_t hop, int avg);
 MDC_API int mdc_iq_spectrogram(const void* iq_dev, int format, int64_t pairs_in, int nfft, int64_t hop, int avg,
                                const int16_t* window_dev, float scale, float* power_dev, int64_t rows, void* hip_stream);
+
+/* ---- line spectrum: the power spectrogram of a pointwise power of the capture (additive in ABI 5) ---------------------------
+ * A pulse-shaped linear modulation hides two spectral lines: the spectrum of |x|^2 has one at the symbol rate, and the spectrum
+ * of x^2 (BPSK, PAM) or x^4 (QPSK, QAM) one at 2 or 4 times the residual carrier offset.  mdc_iq_line_spectrum is
+ * mdc_iq_spectrogram with one more step between widening and window (the float64 numpy restatement is tests/iq_line_ref.py).
+ * Normatively, with (I, Q) the pair widened to 16-bit full scale, y_n is the exact integer pair
+ *   order 0    MDC_IQ_LINE_ENVELOPE: y = (I^2 + Q^2, 0), |y| <= 2^31;
+ *   order 1    y = (I, Q): the result is mdc_iq_spectrogram's, bit for bit;
+ *   order 2    y = (I^2 - Q^2, 2 I Q), the square of I + iQ; both components within +-2^31 (I = Q = -32768 reaches 2^31);
+ *   order 4    y = (a^2 - b^2, 2 a b), (a, b) the order-2 pair: the fourth power, both components within +-2^62;
+ * any other order is MDC_EINVAL.  The staged value is
+ *   window     v_s[n] = y[s*hop + n] * w[n] * 2^-q,  q = 16 for orders 0 and 2, 48 for order 4, 0 for order 1:  |v| <= 2^30,
+ *              so that |X|^2 summed over avg <= 4096 segments stays inside float32 at every order.
+ * Segments, spectrum, rows, averaging and scale are the power spectrogram's, with v_s as above; so are the output order, the
+ * dropped trailing segments, the limits on nfft, hop, avg and scale, the alignment and NULL rules, rows == 0, "only enqueues",
+ * graph capture and both determinism statements (the same bits on every run; row r equals the one-row call on the pairs from
+ * r*avg*hop on).  rows must equal mdc_iq_spectrogram_rows(pairs_in, nfft, hop, avg): there is no second counting function.
+ * Error bound: the power spectrogram's formula with eps = u (8 (log2 nfft + 1) + c), c = 2 for orders 0, 2 and 4 (c = 0 for
+ * order 1, whose integers convert exactly).  c counts the float32 roundings on a value before the transform: y is formed in
+ * integers (32-bit for orders 0 and 2, 64-bit for order 4) and is exact; its conversion to float32 rounds once (|y| is no longer
+ * below 2^24); w[n] * 2^-q is an int16 times a power of two, exact (the factor 2 of 2 I Q and of 2 a b is folded into it or into
+ * the integer, exactly); the product of the two rounds once more.  No value is subnormal: |y w| >= 1 or 0, and 2^-48 is far
+ * from float32's smallest normal.  By Parseval a relative perturbation c u of every v moves every bin of X_s by at most
+ * c u sqrt(T_s / scale), which is the form the bound already has. */
+#define MDC_IQ_LINE_ENVELOPE 0
+MDC_API int mdc_iq_line_spectrum(const void* iq_dev, int format, int64_t pairs_in, int order, int nfft, int64_t hop, int avg,
+                                 const int16_t* window_dev, float scale, float* power_dev, int64_t rows, void* hip_stream);
 
 /* ---- channelizer: all M evenly spaced channels of a capture in one pass (additive in ABI 5) ---------------------------------
  * A band with a channel raster (PMR / LMR, GSM, FM broadcast, ISM sub-bands) wants every channel at once.  M calls of mdc_iq_ddc

@@ -36,7 +36,7 @@ EXPORTS = [
     "mdc_iq_windows", "mdc_iq_windows_norm", "mdc_predict_host_iq", "mdc_predict_host_iq_norm",
     "mdc_iq_ddc", "mdc_iq_ddc_out_count", "mdc_iq_ddc_nco_table",
     "mdc_iq_resample", "mdc_iq_resample_out_count",
-    "mdc_iq_spectrogram", "mdc_iq_spectrogram_rows",
+    "mdc_iq_spectrogram", "mdc_iq_spectrogram_rows", "mdc_iq_line_spectrum",
     "mdc_iq_channelizer", "mdc_iq_channelizer_out_count",
 ]
 ABI_VERSION = 5
@@ -64,6 +64,9 @@ RESAMPLE_TILE_PAIRS, RESAMPLE_GRID_CAP = 8192, 1024
 # row, at most SPECTROGRAM_GRID_CAP of them; more rows are walked in passes
 SPECTROGRAM_MIN_NFFT, SPECTROGRAM_MAX_NFFT, SPECTROGRAM_MAX_AVG = 64, 4096, 4096
 SPECTROGRAM_GRID_CAP = 2048
+# mdc_iq_line_spectrum: the same kernel and limits; `order` is 0 (MDC_IQ_LINE_ENVELOPE: I^2 + Q^2), 1 (the spectrogram), 2 or 4
+IQ_LINE_ENVELOPE = 0
+LINE_SPECTRUM_ORDERS = (0, 1, 2, 4)
 # mdc_iq_channelizer: limits of include/mdc.h (channels a power of two in MIN..MAX, decimate <= channels, ntaps <= 16 per channel,
 # per-residue sum |h| <= 65535), and the kernel's tiling (csrc/iq_channelizer.hip: kChanGridCap, chan_tile_steps): a work-group
 # owns channelizer_tile_steps(channels) consecutive output steps, at most CHANNELIZER_GRID_CAP work-groups; more tiles are
@@ -157,6 +160,7 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_iq_ddc", [vp, i32, i64, C.c_uint32, C.c_uint32, i32, vp, i32, vp, i64, vp]),
                        ("mdc_iq_resample", [vp, i32, i64, C.c_uint32, C.c_uint32, i32, i32, vp, i32, vp, i64, vp]),
                        ("mdc_iq_spectrogram", [vp, i32, i64, i32, i64, i32, vp, C.c_float, vp, i64, vp]),
+                       ("mdc_iq_line_spectrum", [vp, i32, i64, i32, i32, i64, i32, vp, C.c_float, vp, i64, vp]),
                        ("mdc_iq_channelizer", [vp, i32, i64, i64, i32, i32, vp, i32, i32, vp, i64, vp])):
         fn = getattr(L, name, None)
         if fn is not None:

@@ -22,6 +22,8 @@
 //   LDS       complex f32 elements, one element of padding after every 16 (spec_slot): the writes of the first pass, element
 //             stride 4 over the lanes, would otherwise put each 16-lane group of a 64-bit store on 4 of its 16 bank pairs.  nfft = 4096:
 //             34 KiB of image + 24 KiB of twiddles, two work-groups per CU.
+// mdc_iq_line_spectrum is the same kernel with ORDER != 1: the staging alone differs (spec_stage; include/mdc.h, "line spectrum";
+// tests/iq_line_ref.py), everything from the image on is shared -- DESIGN.md 5.19.
 // The call only enqueues; vector memory for every store.
 #include "iq_mix.h"
 
@@ -53,7 +55,32 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 w) { return make_float2(
 __device__ __forceinline__ float2 cmuli(float2 a) { return make_float2(-a.y, a.x); }      // a * i
 __device__ __forceinline__ float norm2(float2 a) { return a.x * a.x + a.y * a.y; }
 
-template <int FMT, int LOG2N>
+// What is transformed (ORDER; include/mdc.h, "line spectrum"): the widened pair itself (1: mdc_iq_spectrogram), or an exact
+// integer function of it -- its envelope I^2 + Q^2 (0), its square (2) or its fourth power (4) -- times the window's value and
+// 2^-q, q = 16 / 0 / 16 / 48.  Orders 0 and 2 stay in 32-bit integers (I^2 + Q^2 <= 2^31 as unsigned; I^2 - Q^2 and I Q within
+// +-2^30, the factor 2 of 2 I Q goes into the window's factor); order 4 squares that pair in 64-bit integers (|.| <= 2^62).
+// Each value is rounded twice on its way into the image: the integer's conversion to f32, and the product with w 2^-q (itself
+// exact: an int16 times a power of two).
+template <int ORDER>
+__device__ __forceinline__ float2 spec_stage(int I, int Q, int w) {
+    if constexpr (ORDER == 1) {
+        return make_float2((float)(I * w), (float)(Q * w));
+    } else if constexpr (ORDER == 0) {
+        return make_float2((float)((unsigned)(I * I) + (unsigned)(Q * Q)) * ((float)w * 0x1p-16f), 0.f);
+    } else {
+        const int a = I * I - Q * Q, b = I * Q;      // the square is (a, 2b)
+        if constexpr (ORDER == 2) {
+            return make_float2((float)a * ((float)w * 0x1p-16f), (float)b * ((float)w * 0x1p-15f));
+        } else {
+            static_assert(ORDER == 4, "orders 0, 1, 2 and 4");
+            const long long aa = (long long)a * a, bb = (long long)b * b, ab = (long long)a * b;
+            const float ws = (float)w * 0x1p-48f;
+            return make_float2((float)(aa - 4 * bb) * ws, (float)(4 * ab) * ws);
+        }
+    }
+}
+
+template <int FMT, int LOG2N, int ORDER>
 __global__ __launch_bounds__(spec_threads(LOG2N)) void iq_spectrogram_kernel(const unsigned char* __restrict__ iq, long pairs, long hop, int avg,
                                                                             const short* __restrict__ window, float gain,
                                                                             float* __restrict__ power, long rows) {
@@ -89,7 +116,7 @@ __global__ __launch_bounds__(spec_threads(LOG2N)) void iq_spectrogram_kernel(con
                     short w[4];
                     __builtin_memcpy(w, window + 4 * q, sizeof(w));
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) x[spec_slot(4 * q + e)] = make_float2((float)(I[e] * (int)w[e]), (float)(Q[e] * (int)w[e]));
+                    for (int e = 0; e < 4; ++e) x[spec_slot(4 * q + e)] = spec_stage<ORDER>(I[e], Q[e], (int)w[e]);
                 }
             }
             __syncthreads();
@@ -166,26 +193,26 @@ __global__ __launch_bounds__(spec_threads(LOG2N)) void iq_spectrogram_kernel(con
     }
 }
 
-template <int FMT, int LOG2N>
+template <int FMT, int LOG2N, int ORDER>
 int spec_launch(const unsigned char* iq, int64_t pairs, int64_t hop, int avg, const int16_t* window, float gain, float* power, int64_t rows, hipStream_t s) {
     const dim3 g((unsigned)(rows < kSpecGridCap ? rows : kSpecGridCap)), b(spec_threads(LOG2N));
-    hipLaunchKernelGGL((iq_spectrogram_kernel<FMT, LOG2N>), g, b, 0, s, iq, (long)pairs, (long)hop, avg, reinterpret_cast<const short*>(window), gain, power,
+    hipLaunchKernelGGL((iq_spectrogram_kernel<FMT, LOG2N, ORDER>), g, b, 0, s, iq, (long)pairs, (long)hop, avg, reinterpret_cast<const short*>(window), gain, power,
                        (long)rows);
     MDC_HIP(hipGetLastError());
     return MDC_OK;
 }
 
-template <int FMT>
+template <int FMT, int ORDER>
 int spec_launch_fmt(int log2n, const unsigned char* iq, int64_t pairs, int64_t hop, int avg, const int16_t* window, float gain, float* power, int64_t rows,
                     hipStream_t s) {
     switch (log2n) {
-        case 6: return spec_launch<FMT, 6>(iq, pairs, hop, avg, window, gain, power, rows, s);
-        case 7: return spec_launch<FMT, 7>(iq, pairs, hop, avg, window, gain, power, rows, s);
-        case 8: return spec_launch<FMT, 8>(iq, pairs, hop, avg, window, gain, power, rows, s);
-        case 9: return spec_launch<FMT, 9>(iq, pairs, hop, avg, window, gain, power, rows, s);
-        case 10: return spec_launch<FMT, 10>(iq, pairs, hop, avg, window, gain, power, rows, s);
-        case 11: return spec_launch<FMT, 11>(iq, pairs, hop, avg, window, gain, power, rows, s);
-        default: return spec_launch<FMT, 12>(iq, pairs, hop, avg, window, gain, power, rows, s);
+        case 6: return spec_launch<FMT, 6, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
+        case 7: return spec_launch<FMT, 7, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
+        case 8: return spec_launch<FMT, 8, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
+        case 9: return spec_launch<FMT, 9, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
+        case 10: return spec_launch<FMT, 10, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
+        case 11: return spec_launch<FMT, 11, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
+        default: return spec_launch<FMT, 12, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
     }
 }
 
@@ -219,27 +246,46 @@ int64_t mdc_iq_spectrogram_rows(int64_t pairs_in, int nfft, int64_t hop, int avg
     return rc != MDC_OK ? (int64_t)rc : spec_rows(pairs_in, nfft, hop, avg);
 }
 
-int mdc_iq_spectrogram(const void* iq_dev, int format, int64_t pairs_in, int nfft, int64_t hop, int avg, const int16_t* window_dev, float scale,
-                       float* power_dev, int64_t rows, void* hip_stream) {
-    int rc = iq_format_known("mdc_iq_spectrogram", format);
+// both entry points: order 1 is mdc_iq_spectrogram
+static int spec_run(const char* who, const void* iq_dev, int format, int64_t pairs_in, int order, int nfft, int64_t hop, int avg, const int16_t* window_dev,
+                    float scale, float* power_dev, int64_t rows, void* hip_stream) {
+    int rc = iq_format_known(who, format);
     if (rc != MDC_OK) return rc;
-    if ((rc = spec_shape_check("mdc_iq_spectrogram", pairs_in, nfft, hop, avg)) != MDC_OK) return rc;
-    if (!(scale > 0.f) || !(scale <= 3.402823466e38f)) { set_error("mdc_iq_spectrogram: scale must be finite and > 0 (got %g)", (double)scale); return MDC_EINVAL; }
+    if (order != 0 && order != 1 && order != 2 && order != 4) { set_error("%s: order must be 0 (envelope), 1, 2 or 4 (got %d)", who, order); return MDC_EINVAL; }
+    if ((rc = spec_shape_check(who, pairs_in, nfft, hop, avg)) != MDC_OK) return rc;
+    if (!(scale > 0.f) || !(scale <= 3.402823466e38f)) { set_error("%s: scale must be finite and > 0 (got %g)", who, (double)scale); return MDC_EINVAL; }
     if (rows != spec_rows(pairs_in, nfft, hop, avg)) {
-        set_error("mdc_iq_spectrogram: rows is %lld, mdc_iq_spectrogram_rows gives %lld", (long long)rows, (long long)spec_rows(pairs_in, nfft, hop, avg));
+        set_error("%s: rows is %lld, mdc_iq_spectrogram_rows gives %lld", who, (long long)rows, (long long)spec_rows(pairs_in, nfft, hop, avg));
         return MDC_EINVAL;
     }
-    if ((rc = iq_pair_aligned("mdc_iq_spectrogram", "iq_dev", format, iq_dev)) != MDC_OK) return rc;
-    if ((reinterpret_cast<uintptr_t>(window_dev) & 1) != 0) { set_error("mdc_iq_spectrogram: window_dev must be 2-byte aligned"); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(power_dev) & 3) != 0) { set_error("mdc_iq_spectrogram: power_dev must be 4-byte aligned"); return MDC_EINVAL; }
+    if ((rc = iq_pair_aligned(who, "iq_dev", format, iq_dev)) != MDC_OK) return rc;
+    if ((reinterpret_cast<uintptr_t>(window_dev) & 1) != 0) { set_error("%s: window_dev must be 2-byte aligned", who); return MDC_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(power_dev) & 3) != 0) { set_error("%s: power_dev must be 4-byte aligned", who); return MDC_EINVAL; }
     if (rows == 0) return MDC_OK;
-    if (!iq_dev || !window_dev || !power_dev) { set_error("mdc_iq_spectrogram: null buffer"); return MDC_EINVAL; }
+    if (!iq_dev || !window_dev || !power_dev) { set_error("%s: null buffer", who); return MDC_EINVAL; }
     const float gain = (float)((double)scale / (double)avg);
     const int log2n = spec_log2(nfft);
     const unsigned char* p = static_cast<const unsigned char*>(iq_dev);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    return guarded("mdc_iq_spectrogram", [&]() -> int {
+    return guarded(who, [&]() -> int {
         return with_format(format, [&](auto fmt) {
-            return spec_launch_fmt<decltype(fmt)::value>(log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, s); });
+            constexpr int F = decltype(fmt)::value;
+            switch (order) {
+                case 0: return spec_launch_fmt<F, 0>(log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, s);
+                case 1: return spec_launch_fmt<F, 1>(log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, s);
+                case 2: return spec_launch_fmt<F, 2>(log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, s);
+                default: return spec_launch_fmt<F, 4>(log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, s);
+            }
+        });
     });
+}
+
+int mdc_iq_spectrogram(const void* iq_dev, int format, int64_t pairs_in, int nfft, int64_t hop, int avg, const int16_t* window_dev, float scale,
+                       float* power_dev, int64_t rows, void* hip_stream) {
+    return spec_run("mdc_iq_spectrogram", iq_dev, format, pairs_in, 1, nfft, hop, avg, window_dev, scale, power_dev, rows, hip_stream);
+}
+
+int mdc_iq_line_spectrum(const void* iq_dev, int format, int64_t pairs_in, int order, int nfft, int64_t hop, int avg, const int16_t* window_dev, float scale,
+                         float* power_dev, int64_t rows, void* hip_stream) {
+    return spec_run("mdc_iq_line_spectrum", iq_dev, format, pairs_in, order, nfft, hop, avg, window_dev, scale, power_dev, rows, hip_stream);
 }

@@ -966,7 +966,7 @@ class VTCNN2:
         return probs, labels
 
     def scan_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_db: float = 6.0, hop: int = 128, level: float = 7.8e-3,
-                squelch_dbfs: Optional[float] = None, **find_kw):
+                squelch_dbfs: Optional[float] = None, refine: bool = False, min_line_db: float = 8.0, **find_kw):
         """A wideband capture in, "what is transmitting where, and what modulation" out.  The capture's power spectrogram
         (frontend.spectrogram: nfft bins, Hann window, segments nfft // 2 apart, `avg` of them per row, on the device) is averaged
         over its rows into one spectrum; frontend.find_emitters(spectrum, threshold_db, window=the Hann window, **find_kw) lists
@@ -976,7 +976,21 @@ class VTCNN2:
         squelch_dbfs=, return_power=True).  Returns one dict per emitter, in order of centre: centre, bandwidth (cycles per input
         sample), power_dbfs, snr_db, shift, interpolate, decimate, probs, labels, window_dbfs (predict_iq's three results: device
         tensors, or numpy arrays for a numpy capture) and label, the most frequent label among the windows the squelch let through
-        (the smallest on a tie; -1 if there are none)."""
+        (the smallest on a tie; -1 if there are none).
+
+        refine=True replaces the plan's two guesses -- a symbol rate from the thresholded width, a carrier from the centroid -- by
+        the emitter's spectral lines.  Per emitter: (1) isolate it at about four times its width, D0 = clamp(floor(1 / (4
+        bandwidth)), 1, 256), iso = frontend.ddc(capture, shift=-centre, decimate=D0, taps=frontend.plan_taps(1, D0)); b =
+        bandwidth D0 is its width there.  (2) frontend.estimate_symbol_rate(iso, "ci16", lo=b / 2.5, hi=min(0.45, 1.25 b),
+        min_line_db=): a linear modulation's symbol rate is b / (1 + beta), beta in 0..1, and a thresholded width may be 25 % off;
+        the band also keeps the line's harmonics out.  symbol_rate = rate / D0 (None without a line).  (3)
+        frontend.estimate_carrier_offset(iso, "ci16", max_offset=b / 8, min_line_db=) (at most 0.12: an emitter filling the whole
+        band); carrier_offset = offset / D0, and shift = -(centre + carrier_offset), folded into [-0.5, 0.5].  (4) (L, D) = frontend.resample_ratio(1.0, symbol_rate, 8) when the symbol line was found and
+        a ratio within its 1 % exists, else channel_plan's.  (5) The ORIGINAL capture is resampled with that shift and ratio and
+        plan_taps(L, D), and classified as above.  The record gains symbol_rate (cycles per input sample, or None),
+        symbol_line_db, carrier_offset, carrier_order (2, 4, or 0: no line -- 8PSK, analogue and frequency-shift signals show
+        none -- and the centroid stands) and carrier_line_db; centre stays the centroid.  refine=False is the plan alone, and its
+        record has none of the five."""
         torch = _torch()
         from . import frontend as F
         fmt = F.sample_format_id(sample_format)
@@ -990,6 +1004,23 @@ class VTCNN2:
         out = []
         for e in F.find_emitters(psd, threshold_db=threshold_db, window=window, **find_kw):
             shift, L, D, _ = F.channel_plan(e.centre, e.bandwidth)
+            extra = {}
+            if refine:
+                D0 = min(max(int(1.0 / (4.0 * e.bandwidth)), 1), 256)
+                iso = F.ddc(dev, fmt, shift=-e.centre, decimate=D0, taps=F.plan_taps(1, D0)).reshape(-1)
+                b = e.bandwidth * D0
+                rate, rate_db = F.estimate_symbol_rate(iso, _cabi.IQ_CI16, lo=b / 2.5, hi=min(0.45, 1.25 * b), min_line_db=min_line_db)
+                offset, order, offset_db = F.estimate_carrier_offset(iso, _cabi.IQ_CI16, max_offset=min(b / 8.0, 0.12), min_line_db=min_line_db)
+                shift = -(e.centre + offset / D0)
+                if abs(shift) > 0.5:      # an emitter at the band's edge: the same frequency, one turn on
+                    shift -= round(shift)
+                if rate is not None:
+                    try:
+                        L, D, _ = F.resample_ratio(1.0, rate / D0, 8)
+                    except ValueError:      # nothing within 1 %: the plan's ratio stands
+                        pass
+                extra = dict(symbol_rate=None if rate is None else rate / D0, symbol_line_db=rate_db, carrier_offset=offset / D0, carrier_order=order,
+                             carrier_line_db=offset_db)
             if L == 1:
                 down = F.ddc(dev, fmt, shift=shift, decimate=D, taps=F.plan_taps(L, D))
             else:
@@ -1003,7 +1034,7 @@ class VTCNN2:
             if as_numpy:
                 probs, labels, dbfs = probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy()
             out.append(dict(centre=e.centre, bandwidth=e.bandwidth, power_dbfs=e.power_dbfs, snr_db=e.snr_db, shift=shift, interpolate=L, decimate=D,
-                            labels=labels, probs=probs, window_dbfs=dbfs, label=label))
+                            labels=labels, probs=probs, window_dbfs=dbfs, label=label, **extra))
         return out
 
     def predict_channels(self, iq, sample_format, channels: int, decimate: Optional[int] = None, taps=None, tap_shift: Optional[int] = None,
