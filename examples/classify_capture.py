@@ -27,13 +27,21 @@ With --refine the scan takes each emitter's symbol rate and carrier from its spe
 (frontend.estimate_symbol_rate, estimate_carrier_offset: the spectra of |x|^2 and of x^2 / x^4, on the device) and prints them
 as two more columns.
 
+With --bursts the scan also finds emitters that are on only now and then -- push-to-talk, telemetry, packet traffic --, which the
+spectrum averaged over the whole capture dilutes: the emitters are searched in the level each bin reaches in its top 1 - HOLD of
+the spectrogram's rows (--hold, default 0.98; frontend.spectrum_quantiles, on the device), each emitter's bursts are cut out of
+its band power over time, only windows inside a burst are classified, and two more columns give the number of bursts and the
+share of the time the emitter was on:
+
+    python examples/classify_capture.py capture.bin --format ci16 --scan --bursts --hold 0.98
+
 A band with a channel raster -- PMR / LMR, GSM, FM broadcast, ISM sub-bands -- is split into all its M evenly spaced channels in
 one pass instead (frontend.channelize, a polyphase filter bank on the device; VTCNN2.predict_channels), one line per channel:
 
     python examples/classify_capture.py capture.bin --format ci16 --rate 2.4e6 --channels 16
 
 Without a capture file it classifies a synthetic one: bursts of tones at three gains with silence between them (--scan: a
-band of three QPSK emitters of different widths over noise and a DC offset; --channels: QPSK on two channels of the raster)."""
+band of three QPSK emitters of different widths over noise and a DC offset, with --bursts a fourth that is on 4.5 % of the time; --channels: QPSK on two channels of the raster)."""
 import argparse
 import os
 import sys
@@ -66,19 +74,33 @@ def synthetic_capture(fmt="cu8", seed=1):
     return np.clip(np.rint(iq), lo, hi).astype(DTYPES[fmt]).reshape(-1)
 
 
-def synthetic_band(fmt="ci16", seed=1, pairs=1 << 18):
+def synthetic_band(fmt="ci16", seed=1, pairs=1 << 18, bursty=False):
     """Three QPSK emitters with a root-raised-cosine pulse (beta 0.35) at 96 / 48 / 20 samples per symbol, centred at -0.31 / +0.12 /
-    +0.36 cycles per sample with rms 0.02 / 0.05 / 0.01 of full scale, over noise of rms 0.002 and a tuner's DC offset."""
+    +0.36 cycles per sample with rms 0.02 / 0.05 / 0.01 of full scale, over noise of rms 0.002 and a tuner's DC offset.  bursty: a
+    fourth one at 32 samples per symbol, centred at -0.08 with rms 0.003, that is on only during [0.40, 0.43) and [0.80, 0.815)
+    of the capture."""
     rng = np.random.default_rng(seed)
     beta, n, z = 0.35, np.arange(pairs), np.zeros(pairs, complex)
-    for sps, fc, amp in ((96, -0.31, 0.02), (48, 0.12, 0.05), (20, 0.36, 0.01)):
+
+    def emitter(rng, sps, fc, amp, on=None):
         t = np.arange(-12 * sps, 12 * sps + 1) / sps + 1e-9          # (off the pulse's removable singularities)
         h = (np.sin(np.pi * t * (1 - beta)) + 4 * beta * t * np.cos(np.pi * t * (1 + beta))) / (np.pi * t * (1 - (4 * beta * t) ** 2))
         sym = rng.choice([-1.0, 1.0], pairs // sps + 2) + 1j * rng.choice([-1.0, 1.0], pairs // sps + 2)
         up = np.zeros(sym.size * sps, complex)
         up[::sps] = sym
         base = np.convolve(up, h, mode="same")[:pairs]
-        z += amp / np.sqrt(np.mean(np.abs(base) ** 2)) * base * np.exp(2j * np.pi * fc * n)
+        base = amp / np.sqrt(np.mean(np.abs(base) ** 2)) * base
+        if on is not None:
+            gate = np.zeros(pairs)
+            for a, b in on:
+                gate[int(a * pairs):int(b * pairs)] = 1.0
+            base = base * gate
+        return base * np.exp(2j * np.pi * fc * n)
+
+    for sps, fc, amp in ((96, -0.31, 0.02), (48, 0.12, 0.05), (20, 0.36, 0.01)):
+        z += emitter(rng, sps, fc, amp)
+    if bursty:      # symbols from a stream of its own: the draws of everything else stay what they are
+        z += emitter(np.random.default_rng(seed + 100), 32, -0.08, 0.003, on=((0.40, 0.43), (0.80, 0.815)))
     z += 0.002 / np.sqrt(2) * (rng.standard_normal(pairs) + 1j * rng.standard_normal(pairs)) + (0.01 - 0.02j)
     if fmt == "cu8":
         return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * 127.5 + 127.5), 0, 255).astype(np.uint8).reshape(-1)
@@ -86,22 +108,27 @@ def synthetic_band(fmt="ci16", seed=1, pairs=1 << 18):
     return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * full), lo, hi).astype(DTYPES[fmt]).reshape(-1)
 
 
-def scan(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0, refine=False):
+def scan(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0, refine=False, bursts=False, hold=0.98):
     """Print one line per emitter of the capture (VTCNN2.scan_iq) and return the records.  rate: Hz columns instead of cycles per sample.
     refine: symbol rate and carrier from the emitter's spectral lines (scan_iq's refine=True), as two more columns -- the symbol
-    rate ("-" where no line was found) and the refined centre."""
+    rate ("-" where no line was found) and the refined centre.  bursts: the scan for intermittent emitters (scan_iq's bursts=True
+    on the `hold` quantile spectrum, spectrogram rows of 2 segments), as two more columns -- the number of bursts and the share of
+    the rows the emitter was on."""
+    more = dict(bursts=True, hold=hold, avg=2) if bursts else {}
     found = model.scan_iq(iq[:iq.size // 2 * 2], fmt, nfft=nfft, threshold_db=threshold_db, hop=hop, level=level, squelch_dbfs=squelch,
-                          refine=refine)
+                          refine=refine, **more)
     k, unit = (rate, "Hz") if rate else (1.0, "cyc/sample")
     print(f"{len(found)} emitters ({unit})")
     print(f"{'centre':>12s} {'bandwidth':>12s} {'dBFS':>7s} {'SNR dB':>7s} {'L/D':>7s} {'windows':>8s} {'open':>6s} {'label':>6s}"
-          + (f" {'symbol rate':>12s} {'refined':>12s}" if refine else ""))
+          + (f" {'symbol rate':>12s} {'refined':>12s}" if refine else "") + (f" {'bursts':>7s} {'duty':>6s}" if bursts else ""))
     for e in found:
         labels = np.asarray(e["labels"])
         more = ""
         if refine:
             symbol = "-" if e["symbol_rate"] is None else f"{e['symbol_rate'] * k:.6g}"
             more = f" {symbol:>12s} {(e['centre'] + e['carrier_offset']) * k:12.8g}"
+        if bursts:
+            more += f" {len(e['bursts']):7d} {e['duty']:6.3f}"
         print(f"{e['centre'] * k:12.6g} {e['bandwidth'] * k:12.6g} {e['power_dbfs']:7.1f} {e['snr_db']:7.1f} "
               f"{str(e['interpolate']) + '/' + str(e['decimate']):>7s} {labels.size:8d} {int((labels >= 0).sum()):6d} {e['label']:6d}{more}")
     return found
@@ -197,6 +224,9 @@ def main():
     ap.add_argument("--threshold", type=float, default=6.0, help="with --scan: dB above the noise floor at which a bin belongs to an emitter")
     ap.add_argument("--refine", action="store_true",
                     help="with --scan: symbol rate and carrier of each emitter from its spectral lines; two more columns")
+    ap.add_argument("--bursts", action="store_true",
+                    help="with --scan: find intermittent emitters too and classify only inside their bursts; two more columns")
+    ap.add_argument("--hold", type=float, default=0.98, help="with --bursts: the quantile over time of each bin that the emitters are searched in")
     ap.add_argument("--channels", type=int, default=0,
                     help="split the band into this many evenly spaced channels (a power of two in 8..1024) and classify every one")
     a = ap.parse_args()
@@ -209,13 +239,13 @@ def main():
         channels(model, iq, a.format, a.channels, rate=a.rate if a.rate != 1.0 else None, hop=a.hop, level=a.level, squelch=a.squelch)
         return
     if a.scan:
-        iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_band(a.format)
+        iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_band(a.format, bursty=a.bursts)
         if a.weights is None:
             model = VTCNN2.synthetic("deployed3")
         else:
             model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
         scan(model, iq, a.format, nfft=a.nfft, threshold_db=a.threshold, rate=a.rate if a.rate != 1.0 else None, hop=a.hop, level=a.level,
-             squelch=a.squelch, refine=a.refine)
+             squelch=a.squelch, refine=a.refine, bursts=a.bursts, hold=a.hold)
         return
     if a.symbol_rate is not None:
         from modulationdetectioncnn_amd import frontend

@@ -57,7 +57,8 @@ extern "C" {
                                   mdc_iq_resample / mdc_iq_resample_out_count (the same with a rational factor L/D);
                                   mdc_iq_spectrogram / mdc_iq_spectrogram_rows (averaged power spectra of a raw capture);
                                   mdc_iq_line_spectrum (the same of the capture's envelope, square or fourth power: the
-                                  spectral lines at the symbol rate and at 2 / 4 times the carrier offset) */
+                                  spectral lines at the symbol rate and at 2 / 4 times the carrier offset);
+                                  mdc_iq_spectrum_quantiles (order statistics of a spectrogram along time, per bin) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -477,6 +478,29 @@ MDC_API int mdc_iq_spectrogram(const void* iq_dev, int format, int64_t pairs_in,
 #define MDC_IQ_LINE_ENVELOPE 0
 MDC_API int mdc_iq_line_spectrum(const void* iq_dev, int format, int64_t pairs_in, int order, int nfft, int64_t hop, int avg,
                                  const int16_t* window_dev, float scale, float* power_dev, int64_t rows, void* hip_stream);
+
+/* ---- spectrum quantiles: per-bin order statistics of a spectrogram along time (additive in ABI 5) ---------------------------
+ * The mean over a spectrogram's rows dilutes an emitter that is on for 3 % of the capture by 15 dB.  A high quantile over time
+ * per bin ("the level this bin reaches in its top 2 % of rows") shows it at full strength and, unlike max-hold, shrugs off single
+ * noisy rows; the median over time is a noise floor that bursts do not lift.  mdc_iq_spectrum_quantiles computes up to 8 such
+ * order statistics of every column in one call (the numpy restatement is tests/iq_quantile_ref.py).
+ * Normatively, for power_dev = rows * nfft floats, rows contiguous (what mdc_iq_spectrogram / mdc_iq_line_spectrum write):
+ *   order      for every column k, the `rows` 32-bit patterns power_dev[r*nfft + k] are sorted ascending AS UNSIGNED INTEGERS;
+ *   result     out_dev[i*nfft + k] is the pattern at position ranks_host[i] (0-based) of that order: out_dev holds
+ *              nranks * nfft floats, rank-major.
+ * For finite non-negative floats, +0, subnormals and +Inf that order is the numeric one, and the spectrogram produces nothing
+ * else.  A pattern with the sign bit set, or a NaN, is ordered by the same rule -- after every non-negative float, -0 before
+ * the other negative values, those by growing magnitude -- which is defined and memory-safe, if of no numeric use.  The result
+ * is an element of the column: nothing is interpolated, so it is the same bits on every run and on every machine, and column
+ * k's result depends on no other column.
+ * 1 <= rows <= 2^31 - 1; nfft: a power of two in 64..4096; 0 <= nranks <= 8; every rank in 0 .. rows-1, in any order, repeats
+ * allowed.  ranks_host is a HOST array, read and validated during the call: the ranks travel with the launch (as mdc_iq_ddc's
+ * taps do) and the array may be freed on return.  power_dev and out_dev are 4-byte aligned.  nranks == 0 is MDC_OK (nothing is
+ * launched; the buffers may be NULL); otherwise no buffer may be NULL.  Every argument error is MDC_EINVAL before any device
+ * call.  The call only enqueues on hip_stream (no synchronisation, no allocation, no copy: capturable in a hipGraph) and runs
+ * on the current device. */
+MDC_API int mdc_iq_spectrum_quantiles(const float* power_dev, int64_t rows, int nfft, const int64_t* ranks_host, int nranks,
+                                      float* out_dev, void* hip_stream);
 
 /* ---- channelizer: all M evenly spaced channels of a capture in one pass (additive in ABI 5) ---------------------------------
  * A band with a channel raster (PMR / LMR, GSM, FM broadcast, ISM sub-bands) wants every channel at once.  M calls of mdc_iq_ddc

@@ -38,6 +38,7 @@ EXPORTS = [
     "mdc_iq_resample", "mdc_iq_resample_out_count",
     "mdc_iq_spectrogram", "mdc_iq_spectrogram_rows", "mdc_iq_line_spectrum",
     "mdc_iq_channelizer", "mdc_iq_channelizer_out_count",
+    "mdc_iq_spectrum_quantiles",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
@@ -67,6 +68,10 @@ SPECTROGRAM_GRID_CAP = 2048
 # mdc_iq_line_spectrum: the same kernel and limits; `order` is 0 (MDC_IQ_LINE_ENVELOPE: I^2 + Q^2), 1 (the spectrogram), 2 or 4
 IQ_LINE_ENVELOPE = 0
 LINE_SPECTRUM_ORDERS = (0, 1, 2, 4)
+# mdc_iq_spectrum_quantiles: limits of include/mdc.h, and the kernel's tile (csrc/iq_quantiles.hip: kQuantTile): one work-group
+# per QUANTILES_TILE adjacent columns
+QUANTILES_MAX_RANKS, QUANTILES_MAX_ROWS = 8, 2 ** 31 - 1
+QUANTILES_TILE = 16
 # mdc_iq_channelizer: limits of include/mdc.h (channels a power of two in MIN..MAX, decimate <= channels, ntaps <= 16 per channel,
 # per-residue sum |h| <= 65535), and the kernel's tiling (csrc/iq_channelizer.hip: kChanGridCap, chan_tile_steps): a work-group
 # owns channelizer_tile_steps(channels) consecutive output steps, at most CHANNELIZER_GRID_CAP work-groups; more tiles are
@@ -161,7 +166,8 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_iq_resample", [vp, i32, i64, C.c_uint32, C.c_uint32, i32, i32, vp, i32, vp, i64, vp]),
                        ("mdc_iq_spectrogram", [vp, i32, i64, i32, i64, i32, vp, C.c_float, vp, i64, vp]),
                        ("mdc_iq_line_spectrum", [vp, i32, i64, i32, i32, i64, i32, vp, C.c_float, vp, i64, vp]),
-                       ("mdc_iq_channelizer", [vp, i32, i64, i64, i32, i32, vp, i32, i32, vp, i64, vp])):
+                       ("mdc_iq_channelizer", [vp, i32, i64, i64, i32, i32, vp, i32, i32, vp, i64, vp]),
+                       ("mdc_iq_spectrum_quantiles", [vp, i64, i32, vp, i32, vp, vp])):
         fn = getattr(L, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, i32

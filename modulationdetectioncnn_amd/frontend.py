@@ -704,6 +704,117 @@ def find_emitters(psd, threshold_db: float = 6.0, min_bins: int = 3, merge_bins:
     return found
 
 
+# ---- intermittent emitters: quantile spectra along time (mdc_iq_spectrum_quantiles), band power per row, bursts ---------------
+def _quantile_ranks(q, rows: int):
+    """(ranks, scalar): floor(q * (rows - 1)) per value of q, in Python floats; ValueError for what spectrum_quantiles refuses"""
+    import math
+    scalar = isinstance(q, (int, float, np.floating, np.integer)) and not isinstance(q, bool)
+    qs = [q] if scalar else list(q)
+    if len(qs) > _cabi.QUANTILES_MAX_RANKS:
+        raise ValueError(f"at most {_cabi.QUANTILES_MAX_RANKS} quantiles per call (got {len(qs)})")
+    if rows < 1:
+        raise ValueError("the spectrogram has no rows")
+    ranks = []
+    for v in qs:
+        v = float(v)
+        if not 0.0 <= v <= 1.0:      # (a NaN fails both comparisons)
+            raise ValueError(f"q must lie in [0, 1] (got {v!r})")
+        ranks.append(math.floor(v * (rows - 1)))
+    return ranks, scalar
+
+
+def spectrum_quantiles(spec, q, device=None):
+    """Order statistics of a spectrogram along time, per bin, on the device (mdc_iq_spectrum_quantiles, include/mdc.h).  spec: the
+    (rows, nfft) float32 tensor of spectrogram / line_spectrum (a host tensor or array is moved to the device); q: a float or
+    up to 8 floats in [0, 1].  Row i of the result is, for every bin, the element at position floor(q[i] * (rows - 1)) of the
+    bin's values sorted ascending: an element of the column, never an interpolation -- q = 0.5 is the (lower) median over time,
+    a noise floor that bursts do not lift; q = 0.98 the level a bin reaches in its top 2 % of rows, which shows an intermittent
+    emitter at full strength.  Returns (len(q), nfft) float32 on the device, (nfft,) for a scalar q.  ValueError -- before
+    anything touches a device -- for q outside [0, 1], more than 8 values, a spectrogram without rows, or a shape that is not
+    (rows, nfft) with nfft a power of two in 64..4096.  Enqueues on torch's current stream without synchronising."""
+    import torch
+    shape = tuple(spec.shape) if hasattr(spec, "shape") else ()
+    if len(shape) != 2 or not (_cabi.SPECTROGRAM_MIN_NFFT <= shape[1] <= _cabi.SPECTROGRAM_MAX_NFFT and shape[1] & (shape[1] - 1) == 0):
+        raise ValueError(f"spec must be a (rows, nfft) spectrogram, nfft a power of two in {_cabi.SPECTROGRAM_MIN_NFFT}.."
+                         f"{_cabi.SPECTROGRAM_MAX_NFFT} (got shape {shape})")
+    rows, nfft = int(shape[0]), int(shape[1])
+    ranks, scalar = _quantile_ranks(q, rows)
+    if rows > _cabi.QUANTILES_MAX_ROWS:
+        raise ValueError(f"at most {_cabi.QUANTILES_MAX_ROWS} rows (got {rows})")
+    t = spec if isinstance(spec, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(spec)))
+    if t.dtype != torch.float32:
+        raise TypeError(f"spec must be float32, got {t.dtype}")
+    if not t.is_cuda:
+        t = t.to(device if device is not None else "cuda:0")
+    t = t.contiguous()
+    out = torch.empty((len(ranks), nfft), dtype=torch.float32, device=t.device)
+    r = np.asarray(ranks, np.int64)
+    if len(ranks):
+        with torch.cuda.device(t.device):
+            _cabi.check(_cabi.lib().mdc_iq_spectrum_quantiles(t.data_ptr(), rows, nfft, r.ctypes.data, len(ranks), out.data_ptr(),
+                                                              torch.cuda.current_stream(t.device).cuda_stream))
+    return out[0] if scalar else out
+
+
+def emitter_bins(emitter, nfft: int):
+    """(first, count): the bins of an emitter of find_emitters in natural DFT order -- its width placed around its centroid.
+    count = max(1, round(bandwidth * nfft)); first = round(centre * nfft - (count - 1) / 2) mod nfft; the bins are
+    (first + i) mod nfft, i < count (an emitter around 0 wraps from the last bins to the first)."""
+    n = int(nfft)
+    count = max(1, int(round(float(emitter.bandwidth) * n)))
+    first = int(round(float(emitter.centre) * n - (count - 1) / 2.0)) % n
+    return first, count
+
+
+def band_power(spec, first: int, count: int):
+    """(rows,) float64 device tensor: per row the sum of spec[:, (first + i) mod nfft], i < count, taken in float64 -- the power
+    in an emitter's bins (emitter_bins) row by row, which against count times the noise floor per bin gives its bursts
+    (find_bursts)."""
+    import torch
+    nfft = spec.shape[1]
+    cols = (int(first) + torch.arange(int(count), device=spec.device)) % nfft
+    return spec[:, cols].to(torch.float64).sum(1)
+
+
+def find_bursts(band, floor: float, threshold_db: float = 3.0, min_rows: int = 1, merge_rows: int = 1):
+    """Half-open (first_row, stop_row) of every burst in one band-power series, in order; host numpy.  Row r is on when
+    band[r] > floor * 10^(threshold_db / 10); runs of on-rows separated by at most merge_rows off-rows are joined (the rows
+    between them then belong to the run), and runs of fewer than min_rows rows are dropped: find_emitters' run logic, along
+    time."""
+    b = np.array(band.cpu().numpy() if hasattr(band, "cpu") else band, dtype=np.float64).reshape(-1)
+    on = np.flatnonzero(b > float(floor) * 10.0 ** (float(threshold_db) / 10.0))
+    if on.size == 0:
+        return []
+    cut = np.flatnonzero(np.diff(on) > int(merge_rows) + 1)      # a gap of g rows is a difference of g + 1
+    first, last = on[np.r_[0, cut + 1]], on[np.r_[cut, on.size - 1]]
+    return [(int(a), int(z) + 1) for a, z in zip(first, last) if z - a + 1 >= int(min_rows)]
+
+
+def burst_pairs(first_row: int, stop_row: int, nfft: int, hop: int, avg: int):
+    """Half-open interval of input pairs that rows first_row .. stop_row - 1 of a spectrogram read: row r averages segments
+    r*avg .. r*avg + avg-1, segment s holds pairs s*hop .. s*hop + nfft-1."""
+    return int(first_row) * int(avg) * int(hop), ((int(stop_row) - 1) * int(avg) + int(avg) - 1) * int(hop) + int(nfft)
+
+
+def window_support(w: int, hop: int, ntaps: int, interpolate: int, decimate: int):
+    """Inclusive (first, last) input pair read by window w -- outputs w*hop .. w*hop + 127 -- of a stream of mdc_iq_ddc /
+    mdc_iq_resample with ntaps taps and the factors L / D (include/mdc.h): output j reads the pairs n with
+    j D <= n L <= j D + ntaps - 1, that is ceil(j D / L) .. floor((j D + ntaps - 1) / L); for L = 1, j D .. j D + ntaps - 1.
+    An output whose stretch of the zero-stuffed stream holds no input pair (possible only with ntaps < L) reads nothing and
+    counts for nothing; among 128 consecutive outputs at least one reads a pair (L <= 32)."""
+    first, last = _window_supports([int(w)], hop, ntaps, interpolate, decimate)
+    return int(first[0]), int(last[0])
+
+
+def _window_supports(windows, hop, ntaps, interpolate, decimate):
+    """window_support for an array of window indices: (first, last), int64 arrays"""
+    L, D, T = int(interpolate), int(decimate), int(ntaps)
+    j = np.asarray(windows, np.int64).reshape(-1, 1) * int(hop) + np.arange(HOP_FRAME, dtype=np.int64)[None, :]
+    lo, hi = -((-j * D) // L), (j * D + T - 1) // L
+    reads = hi >= lo
+    return np.where(reads, lo, np.iinfo(np.int64).max).min(axis=1), np.where(reads, hi, -1).max(axis=1)
+
+
 DEFAULT_FILL = 1.35 / 8      # occupied fraction of the output rate: a root-raised-cosine signal, beta 0.35, at 8 samples per symbol
 
 

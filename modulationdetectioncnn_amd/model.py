@@ -966,7 +966,8 @@ class VTCNN2:
         return probs, labels
 
     def scan_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_db: float = 6.0, hop: int = 128, level: float = 7.8e-3,
-                squelch_dbfs: Optional[float] = None, refine: bool = False, min_line_db: float = 8.0, **find_kw):
+                squelch_dbfs: Optional[float] = None, refine: bool = False, min_line_db: float = 8.0, bursts: bool = False, hold: float = 0.98,
+                burst_threshold_db: float = 3.0, min_rows: int = 1, merge_rows: int = 1, **find_kw):
         """A wideband capture in, "what is transmitting where, and what modulation" out.  The capture's power spectrogram
         (frontend.spectrogram: nfft bins, Hann window, segments nfft // 2 apart, `avg` of them per row, on the device) is averaged
         over its rows into one spectrum; frontend.find_emitters(spectrum, threshold_db, window=the Hann window, **find_kw) lists
@@ -990,7 +991,23 @@ class VTCNN2:
         plan_taps(L, D), and classified as above.  The record gains symbol_rate (cycles per input sample, or None),
         symbol_line_db, carrier_offset, carrier_order (2, 4, or 0: no line -- 8PSK, analogue and frequency-shift signals show
         none -- and the centroid stands) and carrier_line_db; centre stays the centroid.  refine=False is the plan alone, and its
-        record has none of the five."""
+        record has none of the five.
+
+        bursts=True is the scan for INTERMITTENT emitters -- push-to-talk, telemetry bursts, packet traffic --, which the mean over
+        the rows dilutes (on 3 % of the time: by 15 dB) until they are missed or found in fragments.  The spectrogram is then looked
+        at along time per bin: Q = frontend.spectrum_quantiles(spec, (0.5, hold)), one call on the device.  The emitters are
+        find_emitters(Q[1], threshold_db, ...): the spectrum each bin reaches in its top 1 - hold of the rows, whose own median bin
+        is find_emitters' floor, so that the noise's high quantile cancels.  The noise per bin is the median over the bins of
+        Q[0], the median over time, which bursts do not lift.  Per emitter, (first, count) = frontend.emitter_bins(e, nfft), band =
+        frontend.band_power(spec, first, count), and frontend.find_bursts(band, count * noise, burst_threshold_db, min_rows,
+        merge_rows) gives the rows it was on.  The record gains bursts, a list of half-open intervals of INPUT pairs
+        (frontend.burst_pairs), and duty, on-rows / rows.  Plan, refine, tuning, resampling and predict_iq run on the whole
+        capture as without bursts; then every window whose frontend.window_support (the input pairs its 128 outputs read through
+        the filter) is not wholly inside one burst gets label -1, as the squelch does, and label is the majority among the
+        windows still open; probs and window_dbfs are untouched.  A spectrogram's rows drop trailing segments that do not fill a
+        row (and a window's support is wider than the window): the last windows of a capture can therefore be gated even for an
+        emitter that never pauses.  An emitter must revisit its bins in at least 1 - hold of the rows to be seen.  bursts=False
+        (the default) is the mean spectrum, and its record has neither key."""
         torch = _torch()
         from . import frontend as F
         fmt = F.sample_format_id(sample_format)
@@ -1000,7 +1017,11 @@ class VTCNN2:
         spec = F.spectrogram(dev, fmt, nfft=nfft, avg=avg)
         if spec.shape[0] == 0:
             raise ValueError(f"the capture is too short for one row of {avg} segments of {nfft} pairs")
-        psd = spec.to(torch.float64).mean(0).cpu().numpy()
+        if bursts:
+            quant = F.spectrum_quantiles(spec, (0.5, float(hold))).to(torch.float64).cpu().numpy()
+            psd, noise = quant[1], float(np.median(quant[0]))
+        else:
+            psd = spec.to(torch.float64).mean(0).cpu().numpy()
         out = []
         for e in F.find_emitters(psd, threshold_db=threshold_db, window=window, **find_kw):
             shift, L, D, _ = F.channel_plan(e.centre, e.bandwidth)
@@ -1021,14 +1042,25 @@ class VTCNN2:
                         pass
                 extra = dict(symbol_rate=None if rate is None else rate / D0, symbol_line_db=rate_db, carrier_offset=offset / D0, carrier_order=order,
                              carrier_line_db=offset_db)
+            taps = F.plan_taps(L, D)
             if L == 1:
-                down = F.ddc(dev, fmt, shift=shift, decimate=D, taps=F.plan_taps(L, D))
+                down = F.ddc(dev, fmt, shift=shift, decimate=D, taps=taps)
             else:
-                down = F.resample(dev, fmt, shift=shift, interpolate=L, decimate=D, taps=F.plan_taps(L, D))
+                down = F.resample(dev, fmt, shift=shift, interpolate=L, decimate=D, taps=taps)
             if hop == 128:
                 down = down[:down.shape[0] // 128 * 128]
             probs, labels, dbfs = self.predict_iq(down.reshape(-1), _cabi.IQ_CI16, hop=hop, normalize="rms", level=level, squelch_dbfs=squelch_dbfs,
                                                   return_power=True)
+            if bursts:
+                first_bin, count = F.emitter_bins(e, nfft)
+                rows_on = F.find_bursts(F.band_power(spec, first_bin, count).cpu(), count * noise, burst_threshold_db, min_rows, merge_rows)
+                on = [F.burst_pairs(a, z, nfft, nfft // 2, avg) for a, z in rows_on]
+                extra.update(bursts=on, duty=sum(z - a for a, z in rows_on) / spec.shape[0])
+                lo, hi = F._window_supports(np.arange(labels.shape[0]), hop, taps.size, L, D)
+                inside = np.zeros(labels.shape[0], bool)
+                for a, z in on:
+                    inside |= (lo >= a) & (hi < z)
+                labels.masked_fill_(torch.from_numpy(~inside).to(labels.device), -1)
             open_ = labels[labels >= 0]
             label = int(torch.bincount(open_).argmax()) if open_.numel() else -1
             if as_numpy:
