@@ -35,13 +35,21 @@ share of the time the emitter was on:
 
     python examples/classify_capture.py capture.bin --format ci16 --scan --bursts --hold 0.98
 
+With --detections the band is searched in two dimensions instead (VTCNN2.detect_iq): the spectrogram is thresholded cell by cell,
+neighbouring cells are joined into boxes in time and frequency on the device (frontend.find_detections), and only the pairs inside
+a box are tuned, resampled and classified -- one line per box.  That finds what both scans above miss: a frequency hopper (one
+line per dwell), two emitters that use the same bins at different times (two lines), a single short packet:
+
+    python examples/classify_capture.py capture.bin --format ci16 --detections --threshold 6
+
 A band with a channel raster -- PMR / LMR, GSM, FM broadcast, ISM sub-bands -- is split into all its M evenly spaced channels in
 one pass instead (frontend.channelize, a polyphase filter bank on the device; VTCNN2.predict_channels), one line per channel:
 
     python examples/classify_capture.py capture.bin --format ci16 --rate 2.4e6 --channels 16
 
 Without a capture file it classifies a synthetic one: bursts of tones at three gains with silence between them (--scan: a
-band of three QPSK emitters of different widths over noise and a DC offset, with --bursts a fourth that is on 4.5 % of the time; --channels: QPSK on two channels of the raster)."""
+band of three QPSK emitters of different widths over noise and a DC offset, with --bursts a fourth that is on 4.5 % of the time; --detections: a QPSK hopper of six dwells and a second emitter on an
+earlier dwell's bins; --channels: QPSK on two channels of the raster)."""
 import argparse
 import os
 import sys
@@ -131,6 +139,44 @@ def scan(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=
             more += f" {len(e['bursts']):7d} {e['duty']:6.3f}"
         print(f"{e['centre'] * k:12.6g} {e['bandwidth'] * k:12.6g} {e['power_dbfs']:7.1f} {e['snr_db']:7.1f} "
               f"{str(e['interpolate']) + '/' + str(e['decimate']):>7s} {labels.size:8d} {int((labels >= 0).sum()):6d} {e['label']:6d}{more}")
+    return found
+
+
+def synthetic_hopper(fmt="ci16", seed=1, pairs=1 << 19):
+    """A frequency hopper over noise of rms 0.002: six QPSK dwells (root-raised-cosine, 32 samples per symbol, rms 0.002 of full scale:
+    about 14 dB per bin of 1024) of 65,536 pairs, 8,192 pairs apart, centred at -0.475 / +0.21 / +0.02 / -0.18 / +0.475 / +0.33 cycles per sample, and a second emitter
+    of the same kind on the second dwell's bins during the last dwell: seven boxes in time and frequency."""
+    rng = np.random.default_rng(seed)
+    beta, sps, n = 0.35, 32, np.arange(pairs)
+    z = 0.002 / np.sqrt(2) * (rng.standard_normal(pairs) + 1j * rng.standard_normal(pairs))
+    centres = (-0.475, 0.21, 20 / 1024, -0.18, 0.475, 0.33)
+    spans = [((1 << 14) + i * ((1 << 16) + (1 << 13)), (1 << 14) + i * ((1 << 16) + (1 << 13)) + (1 << 16)) for i in range(6)]
+    t = np.arange(-12 * sps, 12 * sps + 1) / sps + 1e-9          # (off the pulse's removable singularities)
+    h = (np.sin(np.pi * t * (1 - beta)) + 4 * beta * t * np.cos(np.pi * t * (1 + beta))) / (np.pi * t * (1 - (4 * beta * t) ** 2))
+    for (a, b), fc in list(zip(spans, centres)) + [(spans[5], centres[1])]:
+        sym = rng.choice([-1.0, 1.0], (b - a) // sps + 2) + 1j * rng.choice([-1.0, 1.0], (b - a) // sps + 2)
+        up = np.zeros(sym.size * sps, complex)
+        up[::sps] = sym
+        base = np.convolve(up, h, mode="same")[:b - a]
+        z[a:b] += 0.002 / np.sqrt(np.mean(np.abs(base) ** 2)) * base * np.exp(2j * np.pi * fc * n[a:b])
+    if fmt == "cu8":
+        return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * 127.5 + 127.5), 0, 255).astype(np.uint8).reshape(-1)
+    full, lo, hi = (128.0, -128, 127) if fmt == "ci8" else (32768.0, -32768, 32767)
+    return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * full), lo, hi).astype(DTYPES[fmt]).reshape(-1)
+
+
+def detections(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0):
+    """Print one line per detection of the capture (VTCNN2.detect_iq: boxes in time and frequency) and return the records: the
+    box's span in input pairs, centre and width (Hz with rate, else cycles per sample), the peak over the threshold, the plan and
+    the label."""
+    found = model.detect_iq(iq[:iq.size // 2 * 2], fmt, nfft=nfft, threshold_db=threshold_db, hop=hop, level=level, squelch_dbfs=squelch)
+    k, unit = (rate, "Hz") if rate else (1.0, "cyc/sample")
+    print(f"{len(found)} detections ({unit})")
+    print(f"{'first pair':>12s} {'stop pair':>12s} {'centre':>12s} {'bandwidth':>12s} {'peak dB':>8s} {'L/D':>7s} {'windows':>8s} {'open':>6s} {'label':>6s}")
+    for d in found:
+        labels = np.asarray(d["labels"])
+        print(f"{d['first_pair']:12d} {d['stop_pair']:12d} {d['centre'] * k:12.6g} {d['bandwidth'] * k:12.6g} {d['snr_db']:8.1f} "
+              f"{str(d['interpolate']) + '/' + str(d['decimate']):>7s} {d['windows']:8d} {int((labels >= 0).sum()):6d} {d['label']:6d}")
     return found
 
 
@@ -229,7 +275,19 @@ def main():
     ap.add_argument("--hold", type=float, default=0.98, help="with --bursts: the quantile over time of each bin that the emitters are searched in")
     ap.add_argument("--channels", type=int, default=0,
                     help="split the band into this many evenly spaced channels (a power of two in 8..1024) and classify every one")
+    ap.add_argument("--detections", action="store_true",
+                    help="search the spectrogram in two dimensions (hoppers, emitters sharing bins, single packets): one line per box in "
+                         "time and frequency; uses --nfft and --threshold")
     a = ap.parse_args()
+    if a.detections:
+        iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_hopper(a.format)
+        if a.weights is None:
+            model = VTCNN2.synthetic("deployed3")
+        else:
+            model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
+        detections(model, iq, a.format, nfft=a.nfft, threshold_db=a.threshold, rate=a.rate if a.rate != 1.0 else None, hop=a.hop, level=a.level,
+                   squelch=a.squelch)
+        return
     if a.channels:
         iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_raster(a.format, a.channels)
         if a.weights is None:

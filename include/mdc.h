@@ -58,7 +58,9 @@ extern "C" {
                                   mdc_iq_spectrogram / mdc_iq_spectrogram_rows (averaged power spectra of a raw capture);
                                   mdc_iq_line_spectrum (the same of the capture's envelope, square or fourth power: the
                                   spectral lines at the symbol rate and at 2 / 4 times the carrier offset);
-                                  mdc_iq_spectrum_quantiles (order statistics of a spectrogram along time, per bin) */
+                                  mdc_iq_spectrum_quantiles (order statistics of a spectrogram along time, per bin);
+                                  mdc_iq_spectrogram_components / mdc_iq_spectrogram_components_workspace, mdc_iq_component
+                                  (connected components of a thresholded spectrogram: boxes in time and frequency) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -501,6 +503,53 @@ MDC_API int mdc_iq_line_spectrum(const void* iq_dev, int format, int64_t pairs_i
  * on the current device. */
 MDC_API int mdc_iq_spectrum_quantiles(const float* power_dev, int64_t rows, int nfft, const int64_t* ranks_host, int nranks,
                                       float* out_dev, void* hip_stream);
+
+/* ---- spectrogram components: a time-frequency detector on a thresholded spectrogram (additive in ABI 5) ----------------------
+ * A frequency hopper never dwells in one bin long enough to show in a quantile spectrum, two intermittent emitters that share
+ * bins at different times come out of it as one, and a single short packet is below any quantile the rows allow.  All three are
+ * plain to see in two dimensions: threshold the spectrogram cell by cell, join neighbouring on-cells into connected components,
+ * and reduce each component to a box in time and frequency.  mdc_iq_spectrogram_components does that on the device in one call
+ * (the Python restatement is tests/iq_components_ref.py).  Normatively, for power_dev = rows * nfft floats, rows contiguous, in
+ * the natural DFT order mdc_iq_spectrogram writes:
+ *   centred    column c = (k + nfft/2) mod nfft of natural bin k: the order -0.5 .. 0.5 of a spectrum display.  The band is
+ *              NOT circular: natural bins nfft-1 and 0 are neighbours (c = nfft/2 - 1 and nfft/2), natural bins nfft/2 - 1
+ *              and nfft/2 are the two ends (c = nfft - 1 and 0).
+ *   on         cell (r, c) is on iff power_dev[r*nfft + k] > thresh_dev[k], an f32 comparison: equality is off, a NaN on either
+ *              side is off, a threshold of +Inf switches its bin off (a DC guard).
+ *   link       two on-cells are linked iff |r1 - r2| <= reach_rows and |c1 - c2| <= reach_bins: reach (1, 1) is
+ *              8-connectivity, a reach of g + 1 joins runs across a gap of g off cells, reach (0, 0) makes every on-cell a
+ *              component of its own.  A component is a connected component of this graph.
+ *   number     a component's root is its cell with the smallest r*nfft + c; components are numbered 0, 1, ... in ascending root.
+ *   results    labels_dev[r*nfft + k] (the cell's natural position) is the number of the cell's component, -1 for an off cell;
+ *              *count_dev is the number of components, whether or not they fit; comps_dev[i], i < min(count, capacity), is
+ *              component i: row_first / row_stop and bin_first / bin_stop, its half-open bounding box in rows and CENTRED columns;
+ *              cells, how many cells it has; peak, its largest value, and peak_row / peak_bin (centred), where that is.  "Largest"
+ *              is mdc_iq_spectrum_quantiles' order of the bit patterns as unsigned integers -- the numeric order for everything
+ *              a spectrogram produces --, and among equal patterns the cell with the smallest r*nfft + c wins.  Records at or
+ *              beyond capacity are not written; the labels are complete regardless.
+ * Everything is a function of the inputs alone: floats are only compared, never summed, and what is accumulated atomically
+ * (integer minima, maxima and counts, the packed peak key) does not depend on the order of arrival -- the same bits on every run
+ * and on every machine.
+ * rows >= 1 and rows * nfft <= 2^31 - 1; nfft: a power of two in 64..4096; 0 <= reach_rows, reach_bins <= 4; capacity >= 0, and
+ * capacity == 0 with comps_dev == NULL is legal (labels and count alone); no other buffer may be NULL.  power_dev, thresh_dev
+ * (nfft floats) and labels_dev (rows * nfft int32) are 4-byte aligned, comps_dev (capacity records) and count_dev 8-byte
+ * aligned; work_dev is 16-byte aligned and holds at least mdc_iq_spectrogram_components_workspace(rows, nfft) bytes (a 32-bit
+ * counter per 1024 cells, rounded up to 16 bytes; negative MDC_EINVAL for a shape outside the limits; needs no device).  Its
+ * contents are scratch: nothing is expected in it before the call and nothing is promised after.  Every argument error is
+ * MDC_EINVAL before any device call.  The call only enqueues on hip_stream (no synchronisation, no allocation, no copy:
+ * capturable in a hipGraph) and runs on the current device; no work-group waits for another. */
+typedef struct mdc_iq_component {      /* 32 bytes */
+    int32_t row_first, row_stop;       /* rows, half-open */
+    int32_t bin_first, bin_stop;       /* centred columns, half-open */
+    int32_t cells;
+    float   peak;
+    int32_t peak_row, peak_bin;        /* centred column */
+} mdc_iq_component;
+
+MDC_API int64_t mdc_iq_spectrogram_components_workspace(int64_t rows, int nfft);
+MDC_API int mdc_iq_spectrogram_components(const float* power_dev, int64_t rows, int nfft, const float* thresh_dev, int reach_rows,
+                                          int reach_bins, int32_t* labels_dev, mdc_iq_component* comps_dev, int64_t capacity,
+                                          int64_t* count_dev, void* work_dev, void* hip_stream);
 
 /* ---- channelizer: all M evenly spaced channels of a capture in one pass (additive in ABI 5) ---------------------------------
  * A band with a channel raster (PMR / LMR, GSM, FM broadcast, ISM sub-bands) wants every channel at once.  M calls of mdc_iq_ddc

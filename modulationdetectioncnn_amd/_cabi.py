@@ -39,6 +39,7 @@ EXPORTS = [
     "mdc_iq_spectrogram", "mdc_iq_spectrogram_rows", "mdc_iq_line_spectrum",
     "mdc_iq_channelizer", "mdc_iq_channelizer_out_count",
     "mdc_iq_spectrum_quantiles",
+    "mdc_iq_spectrogram_components", "mdc_iq_spectrogram_components_workspace",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
@@ -72,6 +73,12 @@ LINE_SPECTRUM_ORDERS = (0, 1, 2, 4)
 # per QUANTILES_TILE adjacent columns
 QUANTILES_MAX_RANKS, QUANTILES_MAX_ROWS = 8, 2 ** 31 - 1
 QUANTILES_TILE = 16
+# mdc_iq_spectrogram_components: limits of include/mdc.h, the record (mdc_iq_component, 32 B), and the kernels' decomposition
+# (csrc/iq_components.hip: kTileRows x kTileCols cells are labelled in LDS; the workspace holds one counter per COMPONENTS_CHUNK cells)
+COMPONENTS_MAX_REACH, COMPONENTS_MAX_CELLS = 4, 2 ** 31 - 1
+COMPONENTS_TILE_ROWS, COMPONENTS_TILE_COLS, COMPONENTS_CHUNK = 32, 64, 1024
+IQ_COMPONENT = np.dtype([("row_first", np.int32), ("row_stop", np.int32), ("bin_first", np.int32), ("bin_stop", np.int32),
+                         ("cells", np.int32), ("peak", np.float32), ("peak_row", np.int32), ("peak_bin", np.int32)])
 # mdc_iq_channelizer: limits of include/mdc.h (channels a power of two in MIN..MAX, decimate <= channels, ntaps <= 16 per channel,
 # per-residue sum |h| <= 65535), and the kernel's tiling (csrc/iq_channelizer.hip: kChanGridCap, chan_tile_steps): a work-group
 # owns channelizer_tile_steps(channels) consecutive output steps, at most CHANNELIZER_GRID_CAP work-groups; more tiles are
@@ -167,7 +174,8 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_iq_spectrogram", [vp, i32, i64, i32, i64, i32, vp, C.c_float, vp, i64, vp]),
                        ("mdc_iq_line_spectrum", [vp, i32, i64, i32, i32, i64, i32, vp, C.c_float, vp, i64, vp]),
                        ("mdc_iq_channelizer", [vp, i32, i64, i64, i32, i32, vp, i32, i32, vp, i64, vp]),
-                       ("mdc_iq_spectrum_quantiles", [vp, i64, i32, vp, i32, vp, vp])):
+                       ("mdc_iq_spectrum_quantiles", [vp, i64, i32, vp, i32, vp, vp]),
+                       ("mdc_iq_spectrogram_components", [vp, i64, i32, vp, i32, i32, vp, vp, i64, vp, vp, vp])):
         fn = getattr(L, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, i32
@@ -179,6 +187,8 @@ def lib(variant: str = "product") -> C.CDLL:
         L.mdc_iq_spectrogram_rows.argtypes, L.mdc_iq_spectrogram_rows.restype = [i64, i32, i64, i32], i64
     if getattr(L, "mdc_iq_channelizer_out_count", None) is not None:
         L.mdc_iq_channelizer_out_count.argtypes, L.mdc_iq_channelizer_out_count.restype = [i64, i32, i32, i32], i64
+    if getattr(L, "mdc_iq_spectrogram_components_workspace", None) is not None:
+        L.mdc_iq_spectrogram_components_workspace.argtypes, L.mdc_iq_spectrogram_components_workspace.restype = [i64, i32], i64
     fp = C.POINTER(C.c_float)
     L.mdc_trainer_create.argtypes = [C.POINTER(MdcTopology), i32, C.POINTER(vp)]
     L.mdc_trainer_num_layers.argtypes = [vp]

@@ -993,3 +993,152 @@ def channelize(iq, sample_format, channels: int, decimate=None, taps=None, tap_s
         _cabi.check(lib.mdc_iq_channelizer(t.data_ptr() if pairs else None, fmt, pairs, int(first_index), M, D, h.data_ptr(), T, shift,
                                            out.data_ptr() if n_out else None, n_out, torch.cuda.current_stream(t.device).cuda_stream))
     return out
+
+
+# ---- time-frequency detection (mdc_iq_spectrogram_components): hoppers, overlapping bursts, single packets -------------------------
+def _check_spectrogram_shape(spec):
+    shape = tuple(spec.shape) if hasattr(spec, "shape") else ()
+    if len(shape) != 2 or not (_cabi.SPECTROGRAM_MIN_NFFT <= shape[1] <= _cabi.SPECTROGRAM_MAX_NFFT and shape[1] & (shape[1] - 1) == 0):
+        raise ValueError(f"spec must be a (rows, nfft) spectrogram, nfft a power of two in {_cabi.SPECTROGRAM_MIN_NFFT}.."
+                         f"{_cabi.SPECTROGRAM_MAX_NFFT} (got shape {shape})")
+    return int(shape[0]), int(shape[1])
+
+
+def _float32_tensor(x, what: str):
+    """x as a float32 torch tensor where it lies (TypeError for another dtype): nothing is moved yet"""
+    import torch
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what} must be float32, got {t.dtype}")
+    return t
+
+
+def components_workspace(rows: int, nfft: int) -> int:
+    """mdc_iq_spectrogram_components_workspace: bytes of scratch the labelling of a (rows, nfft) spectrogram needs (no GPU)."""
+    return _cabi.check(_cabi.lib().mdc_iq_spectrogram_components_workspace(int(rows), int(nfft)))
+
+
+def spectrogram_components(spec, thresh, reach_rows: int = 1, reach_bins: int = 1, capacity: int = 65536, device=None):
+    """Connected components of a thresholded spectrogram on the device (mdc_iq_spectrogram_components, include/mdc.h).  spec: the
+    (rows, nfft) float32 tensor of spectrogram (a host tensor or array is moved to the device); thresh: nfft float32 values in
+    natural DFT order (detection_threshold).  Cell (r, k) is on iff spec[r, k] > thresh[k]; on-cells at most reach_rows rows and
+    reach_bins CENTRED columns apart are linked (centred column c = (k + nfft/2) mod nfft: the band is not circular at +-0.5,
+    and natural bins nfft-1 and 0 are neighbours); a component is a connected set, numbered by its first cell in (row, centred
+    column) order.  Returns (labels, records, count): labels, the (rows, nfft) int32 device tensor of component numbers in natural
+    positions, -1 where off; records, a numpy array of _cabi.IQ_COMPONENT (box in rows and centred columns, half-open; cells;
+    peak and where it is) trimmed to min(count, capacity); count, the number of components, which may exceed capacity -- the
+    labels are complete regardless.  Reading count and the records back is the call's one synchronisation; the workspace is
+    allocated here.  ValueError / TypeError -- before anything touches a device -- for a shape that is not (rows, nfft) with
+    nfft a power of two in 64..4096, no rows, more than 2^31 - 1 cells, a thresh that does not hold nfft values, a reach
+    outside 0..4, or a negative capacity."""
+    import torch
+    rows, nfft = _check_spectrogram_shape(spec)
+    if rows < 1:
+        raise ValueError("the spectrogram has no rows")
+    if rows * nfft > _cabi.COMPONENTS_MAX_CELLS:
+        raise ValueError(f"at most {_cabi.COMPONENTS_MAX_CELLS} cells (got {rows} x {nfft})")
+    tshape = tuple(thresh.shape) if hasattr(thresh, "shape") else (len(thresh),)
+    if tshape != (nfft,):
+        raise ValueError(f"thresh must hold nfft = {nfft} values (got shape {tshape})")
+    a, b, cap = int(reach_rows), int(reach_bins), int(capacity)
+    if not (0 <= a <= _cabi.COMPONENTS_MAX_REACH and 0 <= b <= _cabi.COMPONENTS_MAX_REACH):
+        raise ValueError(f"reach_rows and reach_bins must be in 0..{_cabi.COMPONENTS_MAX_REACH} (got {reach_rows!r}, {reach_bins!r})")
+    if cap < 0:
+        raise ValueError(f"capacity must be >= 0 (got {capacity!r})")
+    t, th = _float32_tensor(spec, "spec"), _float32_tensor(thresh, "thresh")
+    if not t.is_cuda:
+        t = t.to(device if device is not None else "cuda:0")
+    t, th = t.contiguous(), th.to(t.device).contiguous()
+    lib = _cabi.lib()
+    labels = torch.empty((rows, nfft), dtype=torch.int32, device=t.device)
+    comps = torch.empty((cap, 4), dtype=torch.int64, device=t.device)      # 32-byte records, 8-byte aligned
+    count = torch.empty((1,), dtype=torch.int64, device=t.device)
+    work = torch.empty((_cabi.check(lib.mdc_iq_spectrogram_components_workspace(rows, nfft)) // 8 + 2,), dtype=torch.int64, device=t.device)
+    ws = work.data_ptr() + (-work.data_ptr()) % 16
+    with torch.cuda.device(t.device):
+        _cabi.check(lib.mdc_iq_spectrogram_components(t.data_ptr(), rows, nfft, th.data_ptr(), a, b, labels.data_ptr(),
+                                                      comps.data_ptr() if cap else None, cap, count.data_ptr(), ws,
+                                                      torch.cuda.current_stream(t.device).cuda_stream))
+    n = int(count.item())
+    records = comps[:min(n, cap)].cpu().numpy().view(_cabi.IQ_COMPONENT).reshape(-1)
+    return labels, records, n
+
+
+def detection_threshold(spec, threshold_db: float = 6.0, dc_guard: int = 1, floor: str = "flat"):
+    """The per-bin threshold of a time-frequency detection: an (nfft,) float32 device tensor in natural DFT order.  Q0 =
+    spectrum_quantiles(spec, 0.5) is every bin's median over time, which bursts do not lift.  floor="flat": the median over the
+    bins of Q0, one level for the whole band -- an element of Q0, the LOWER median sort(Q0)[(nfft - 1) // 2], taken on the device in
+    float32; scan_iq(bursts=True)'s noise is numpy's float64 median of the same Q0, the mean of the two middle values, so the
+    two agree to within the spacing of Q0's middle values, not bit for bit; "per-bin": Q0
+    itself, for a coloured front-end -- whatever is on in more than half the rows is then floor, not signal.  The floor times
+    10^(threshold_db / 10), in float32; bins within dc_guard of bin 0 (both sides; dc_guard < 0: none) are +inf, which switches
+    them off.  A floor that is not > 0 gives +inf (nothing is detected there; "flat": anywhere)."""
+    import torch
+    if floor not in ("flat", "per-bin"):
+        raise ValueError(f"floor must be 'flat' or 'per-bin' (got {floor!r})")
+    factor = float(np.float32(10.0 ** (float(threshold_db) / 10.0)))
+    if not np.isfinite(factor):
+        raise ValueError(f"threshold_db must be finite (got {threshold_db!r})")
+    q0 = spectrum_quantiles(spec, 0.5)
+    nfft = q0.shape[0]
+    level = q0 if floor == "per-bin" else torch.sort(q0).values[(nfft - 1) // 2].expand(nfft)
+    inf = torch.full((nfft,), float("inf"), dtype=torch.float32, device=q0.device)
+    thresh = torch.where(level > 0, level * factor, inf)
+    if int(dc_guard) >= 0:
+        thresh[torch.arange(-int(dc_guard), int(dc_guard) + 1, device=q0.device) % nfft] = float("inf")
+    return thresh
+
+
+def detections_from_components(spec, thresh, records, count: int, min_rows: int = 3, min_bins: int = 3, nfft_hop=None, avg: int = 1):
+    """The host half of find_detections: spectrogram_components' records -> a list of Detection(first_row, stop_row, first_bin,
+    stop_bin, cells, centre, bandwidth, peak_db, snr_db, first_pair, stop_pair), ordered by (first_pair, centre); float64.
+    Components whose box spans fewer than min_rows rows or min_bins bins are dropped.  first_bin / stop_bin are the box's CENTRED
+    columns (half-open; column c is the frequency (c - nfft/2) / nfft), bandwidth its width / nfft.  centre: the box's columns
+    are averaged over the box's rows, every column's mean is taken above thresh at that bin (below it: 0; the threshold is the
+    floor of a detection) and centre is the centroid of that excess in cycles per sample -- find_emitters' centroid on the box;
+    a box without excess gets its middle.  peak_db = 10 log10(peak); snr_db, the peak over the threshold AT ITS BIN in dB (add
+    threshold_db for the ratio to the noise floor).  first_pair / stop_pair: burst_pairs(first_row, stop_row, nfft, nfft_hop, avg)
+    -- nfft_hop (default nfft // 2) and avg are the spectrogram's.  spec, thresh: device or host; only the boxes are read."""
+    from collections import namedtuple
+    Detection = namedtuple("Detection", "first_row stop_row first_bin stop_bin cells centre bandwidth peak_db snr_db first_pair stop_pair")
+    rows, nfft = _check_spectrogram_shape(spec)
+    hop = nfft // 2 if nfft_hop is None else int(nfft_hop)
+    th = np.asarray(thresh.cpu().numpy() if hasattr(thresh, "cpu") else thresh, dtype=np.float64).reshape(-1)
+    if th.size != nfft:
+        raise ValueError(f"thresh must hold nfft = {nfft} values (got {th.size})")
+    found = []
+    for rec in records[:min(int(count), len(records))]:
+        r0, r1, c0, c1 = int(rec["row_first"]), int(rec["row_stop"]), int(rec["bin_first"]), int(rec["bin_stop"])
+        if r1 - r0 < int(min_rows) or c1 - c0 < int(min_bins):
+            continue
+        cols = (np.arange(c0, c1) + nfft // 2) % nfft
+        box = spec[r0:r1]
+        box = box[:, cols] if not hasattr(box, "cpu") else box[:, cols.tolist()].cpu().numpy()
+        mean = np.asarray(box, np.float64).mean(axis=0)
+        with np.errstate(invalid="ignore"):
+            excess = np.where(mean > th[cols], mean - th[cols], 0.0)
+        f = (np.arange(c0, c1) - nfft // 2) / float(nfft)
+        total = float(excess.sum())
+        centre = float((excess * f).sum() / total) if total > 0.0 else float(f[0] + f[-1]) / 2.0
+        peak = float(rec["peak"])
+        at = th[(int(rec["peak_bin"]) + nfft // 2) % nfft]
+        a, z = burst_pairs(r0, r1, nfft, hop, avg)
+        with np.errstate(divide="ignore"):
+            found.append(Detection(r0, r1, c0, c1, int(rec["cells"]), centre, float(c1 - c0) / nfft, float(10.0 * np.log10(peak)),
+                                   float(10.0 * np.log10(peak / at)), a, z))
+    found.sort(key=lambda d: (d.first_pair, d.centre))
+    return found
+
+
+def find_detections(spec, thresh, reach_rows: int = 2, reach_bins: int = 3, min_rows: int = 3, min_bins: int = 3, capacity: int = 65536,
+                    nfft_hop=None, avg: int = 1):
+    """Every emitter's every appearance in a spectrogram, as boxes in time and frequency: spectrogram_components(spec, thresh,
+    reach_rows, reach_bins, capacity) on the device, then detections_from_components(spec, thresh, records, count, min_rows,
+    min_bins, nfft_hop, avg) on the host.  A reach of g + 1 joins on-cells across g off cells, as merge_bins / merge_rows do in
+    one dimension.  A hopper gives one Detection per dwell, two emitters that share bins at different times stay two, a single
+    packet is one box.  ValueError if the spectrogram holds more components than capacity (both numbers are named): raise
+    capacity, or the threshold."""
+    _, records, count = spectrogram_components(spec, thresh, reach_rows, reach_bins, capacity)
+    if count > int(capacity):
+        raise ValueError(f"the spectrogram holds {count} components, capacity is {int(capacity)}: raise capacity or the threshold")
+    return detections_from_components(spec, thresh, records, count, min_rows, min_bins, nfft_hop, avg)

@@ -1069,6 +1069,67 @@ class VTCNN2:
                             labels=labels, probs=probs, window_dbfs=dbfs, label=label, **extra))
         return out
 
+    def detect_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_db: float = 6.0, floor: str = "flat", reach_rows: int = 2,
+                  reach_bins: int = 3, min_rows: int = 3, min_bins: int = 3, hop: int = 128, level: float = 7.8e-3,
+                  squelch_dbfs: Optional[float] = None, dc_guard: int = 1):
+        """A wideband capture in, "what transmitted when, where, and what modulation" out: the scan in two dimensions, for
+        frequency hoppers, emitters that share bins at different times and single packets, which scan_iq's one-dimensional
+        searches miss or mangle.  The capture's spectrogram (frontend.spectrogram, as scan_iq builds it: nfft bins, segments nfft //
+        2 apart, `avg` per row) is thresholded per cell at frontend.detection_threshold(spec, threshold_db, dc_guard, floor) and
+        frontend.find_detections(spec, thresh, reach_rows, reach_bins, min_rows, min_bins, avg=avg) joins the on-cells into boxes
+        in time and frequency, all on the device.  Per detection, frontend.channel_plan(centre, bandwidth) and frontend.plan_taps
+        give (shift, L, D) and the filter, and ONLY the pairs [first_pair, stop_pair) of the capture go through frontend.ddc (L ==
+        1) or frontend.resample; the result is cut into windows `hop` output pairs apart (hop == 128: trimmed to whole frames)
+        and classified with predict_iq(..., "ci16", normalize="rms", level=, squelch_dbfs=, return_power=True).  Returns one dict
+        per detection, ordered by (first_pair, centre): the Detection's fields (first_row, stop_row, first_bin, stop_bin, cells,
+        centre, bandwidth, peak_db, snr_db, first_pair, stop_pair) plus shift, interpolate, decimate, probs, labels, window_dbfs
+        (device tensors, or numpy arrays for a numpy capture), windows, their number, and label, the most frequent label among the
+        windows the squelch let through (the smallest on a tie; -1 if there are none).  A detection whose pairs are too few for
+        one window gives windows = 0, label = -1 and empty results.  The default dc_guard of 1 switches bins -1, 0, +1 off, a gap
+        of three that reach_bins = 3 does not bridge: an emitter ON bin 0 comes out as two boxes, one each side of the guard.  A
+        capture without a DC spike takes dc_guard=0 (only bin 0 off) and gets it as one."""
+        torch = _torch()
+        from . import frontend as F
+        fmt = F.sample_format_id(sample_format)
+        as_numpy = not isinstance(iq, torch.Tensor)
+        dev = F._device_samples(iq, fmt, f"cuda:{self.device_index}")
+        spec = F.spectrogram(dev, fmt, nfft=nfft, avg=avg)
+        if spec.shape[0] == 0:
+            raise ValueError(f"the capture is too short for one row of {avg} segments of {nfft} pairs")
+        thresh = F.detection_threshold(spec, threshold_db, dc_guard, floor)
+        per_pair = _cabi.IQ_PAIR_BYTES[fmt] // dev.element_size()      # elements of `dev` per (I,Q) pair
+        Cn = self.topology.classes
+        out = []
+        for d in F.find_detections(spec, thresh, reach_rows, reach_bins, min_rows, min_bins, avg=avg):
+            shift, L, D, _ = F.channel_plan(d.centre, d.bandwidth)
+            taps = F.plan_taps(L, D)
+            part = dev[d.first_pair * per_pair:d.stop_pair * per_pair]
+            if L == 1:
+                n_out = F.ddc_out_count(d.stop_pair - d.first_pair, taps.size, D)
+            else:
+                n_out = F.resample_out_count(d.stop_pair - d.first_pair, taps.size, L, D)
+            if n_out < 128:
+                probs = torch.empty((0, Cn), dtype=torch.float32, device=dev.device)
+                labels = torch.empty((0,), dtype=torch.int32, device=dev.device)
+                dbfs = torch.empty((0,), dtype=torch.float64, device=dev.device)
+            else:
+                if L == 1:
+                    down = F.ddc(part, fmt, shift=shift, decimate=D, taps=taps)
+                else:
+                    down = F.resample(part, fmt, shift=shift, interpolate=L, decimate=D, taps=taps)
+                if hop == 128:
+                    down = down[:down.shape[0] // 128 * 128]
+                probs, labels, dbfs = self.predict_iq(down.reshape(-1), _cabi.IQ_CI16, hop=hop, normalize="rms", level=level,
+                                                      squelch_dbfs=squelch_dbfs, return_power=True)
+            open_ = labels[labels >= 0]
+            label = int(torch.bincount(open_).argmax()) if open_.numel() else -1
+            windows = int(labels.shape[0])
+            if as_numpy:
+                probs, labels, dbfs = probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy()
+            out.append(dict(d._asdict(), shift=shift, interpolate=L, decimate=D, probs=probs, labels=labels, window_dbfs=dbfs, windows=windows,
+                            label=label))
+        return out
+
     def predict_channels(self, iq, sample_format, channels: int, decimate: Optional[int] = None, taps=None, tap_shift: Optional[int] = None,
                          hop: int = 128, level: float = 7.8e-3, squelch_dbfs: Optional[float] = None, batch_size: int = 0):
         """A band with a channel raster in, "what is on every channel" out.  The capture is split into M = channels evenly spaced
