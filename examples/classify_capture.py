@@ -42,6 +42,9 @@ line per dwell), two emitters that use the same bins at different times (two lin
 
     python examples/classify_capture.py capture.bin --format ci16 --detections --threshold 6
 
+Add --batched for a busy band: all boxes are then extracted in one launch and classified in one forward (the same lines, bit for
+bit; frontend.extract, detect_iq(batched=True)) instead of a few launches and one synchronisation per box.
+
 A band with a channel raster -- PMR / LMR, GSM, FM broadcast, ISM sub-bands -- is split into all its M evenly spaced channels in
 one pass instead (frontend.channelize, a polyphase filter bank on the device; VTCNN2.predict_channels), one line per channel:
 
@@ -165,11 +168,12 @@ def synthetic_hopper(fmt="ci16", seed=1, pairs=1 << 19):
     return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * full), lo, hi).astype(DTYPES[fmt]).reshape(-1)
 
 
-def detections(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0):
+def detections(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0, batched=False):
     """Print one line per detection of the capture (VTCNN2.detect_iq: boxes in time and frequency) and return the records: the
     box's span in input pairs, centre and width (Hz with rate, else cycles per sample), the peak over the threshold, the plan and
-    the label."""
-    found = model.detect_iq(iq[:iq.size // 2 * 2], fmt, nfft=nfft, threshold_db=threshold_db, hop=hop, level=level, squelch_dbfs=squelch)
+    the label.  batched: all boxes in one extraction launch and one forward (needs hop == 128); the same records."""
+    found = model.detect_iq(iq[:iq.size // 2 * 2], fmt, nfft=nfft, threshold_db=threshold_db, hop=hop, level=level, squelch_dbfs=squelch,
+                            batched=batched)
     k, unit = (rate, "Hz") if rate else (1.0, "cyc/sample")
     print(f"{len(found)} detections ({unit})")
     print(f"{'first pair':>12s} {'stop pair':>12s} {'centre':>12s} {'bandwidth':>12s} {'peak dB':>8s} {'L/D':>7s} {'windows':>8s} {'open':>6s} {'label':>6s}")
@@ -278,6 +282,8 @@ def main():
     ap.add_argument("--detections", action="store_true",
                     help="search the spectrogram in two dimensions (hoppers, emitters sharing bins, single packets): one line per box in "
                          "time and frequency; uses --nfft and --threshold")
+    ap.add_argument("--batched", action="store_true",
+                    help="with --detections: extract all boxes in one launch and classify them in one forward (the same lines; needs --hop 128)")
     a = ap.parse_args()
     if a.detections:
         iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_hopper(a.format)
@@ -286,7 +292,7 @@ def main():
         else:
             model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
         detections(model, iq, a.format, nfft=a.nfft, threshold_db=a.threshold, rate=a.rate if a.rate != 1.0 else None, hop=a.hop, level=a.level,
-                   squelch=a.squelch)
+                   squelch=a.squelch, batched=a.batched)
         return
     if a.channels:
         iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_raster(a.format, a.channels)

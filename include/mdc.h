@@ -60,7 +60,9 @@ extern "C" {
                                   spectral lines at the symbol rate and at 2 / 4 times the carrier offset);
                                   mdc_iq_spectrum_quantiles (order statistics of a spectrogram along time, per bin);
                                   mdc_iq_spectrogram_components / mdc_iq_spectrogram_components_workspace, mdc_iq_component
-                                  (connected components of a thresholded spectrogram: boxes in time and frequency) */
+                                  (connected components of a thresholded spectrogram: boxes in time and frequency);
+                                  mdc_iq_extract / mdc_iq_extract_plan / mdc_iq_extract_plan_bytes, mdc_iq_extract_job,
+                                  mdc_iq_extract_filter (K stretches of a capture through mdc_iq_resample's chain in one launch) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -425,6 +427,54 @@ MDC_API int mdc_iq_ddc(const void* iq_dev, int format, int64_t pairs_in, uint32_
 MDC_API int64_t mdc_iq_resample_out_count(int64_t pairs_in, int ntaps, int interpolate, int decimate);
 MDC_API int mdc_iq_resample(const void* iq_dev, int format, int64_t pairs_in, uint32_t phase0, uint32_t phase_step, int interpolate,
                             int decimate, const int16_t* taps_host, int ntaps, int16_t* out_dev, int64_t n_out, void* hip_stream);
+
+/* ---- batched extraction: K stretches of one capture, each tuned, filtered and resampled, in one launch (additive in ABI 5) ----
+ * A search over a capture (mdc_iq_spectrogram_components) returns hundreds to thousands of boxes; K calls of mdc_iq_resample on
+ * K slices are K launches, each with its taps.  mdc_iq_extract does all of them in one: a JOB is a stretch of the capture with
+ * its own oscillator and filter, and its outputs go to a range of one output buffer.  Normatively, for job j of the plan:
+ *     out_dev[out_first .. out_first + n_out)  =  the first n_out output pairs of
+ *     mdc_iq_resample(iq_dev + first_pair pairs, format, pairs, phase0, phase_step, L, D, taps, ...)
+ * bit for bit, (L, D, taps) being filters[job.filter]: the oscillator counts from the job's own first pair, and pairs at or
+ * beyond first_pair + pairs read as zero even where the capture goes on -- the semantics of a call on the slice.  For L = 1 it
+ * is mdc_iq_ddc's result.  0 <= n_out <= mdc_iq_resample_out_count(pairs, ntaps, L, D): a caller may trim each job, to whole
+ * frames of 128 pairs for instance, and pack the jobs back to back.  Pairs of out_dev that no job names are not written.
+ *   filters    filters_host[f] = (interpolate, decimate, ntaps, first_tap): the filter's taps are taps_host[first_tap ..
+ *              first_tap + ntaps), int16, under mdc_iq_resample's limits (L <= 32, D <= 256, T <= 1024, per branch
+ *              sum |h| <= 65535).  Filters may share or overlap stretches of taps_host.
+ *   jobs       jobs_host[j]: 0 <= first_pair, 0 <= pairs, first_pair + pairs <= pairs_in; 0 <= filter < nfilters; reserved = 0;
+ *              the output ranges [out_first, out_first + n_out) lie inside [0, out_pairs] and are pairwise disjoint (ranges that
+ *              merely touch are disjoint; empty ranges overlap nothing).  Jobs may read overlapping input.
+ *   plan       mdc_iq_extract_plan validates all of that and writes a position-independent blob of exactly
+ *              mdc_iq_extract_plan_bytes(...) bytes into plan_host: a header, the job records, per filter the tiling and the
+ *              branch-major tap image the kernel reads, and the list of (job, tile) work items, ordered so that the tiles of one
+ *              filter are adjacent.  Both calls are host code and need no device; the same inputs give the same bytes.
+ *              mdc_iq_extract_plan_bytes checks what it can see (the filters' limits, each job's filter index, reserved, pairs
+ *              and n_out) and returns the size, or a negative MDC_EINVAL.  Every failure is MDC_EINVAL with a message that names
+ *              the job (or the filter).
+ *   run        the caller moves the blob to the device as it likes (plan_dev: the same plan_bytes bytes, 8-byte aligned) and
+ *              calls mdc_iq_extract with BOTH copies: launch sizes and the sanity checks (magic, size, and that format, pairs_in
+ *              and out_pairs are the plan's) come from plan_host, the kernel reads plan_dev.  The call only enqueues on
+ *              hip_stream -- no allocation, no copy, no synchronisation: capturable in a hipGraph -- and runs on the current
+ *              device; plan_host may be freed on return, plan_dev must live until the launch has run.  A plan without tiles is
+ *              MDC_OK without a launch.  iq_dev is aligned to one pair, out_dev to 4 bytes, as in mdc_iq_resample.
+ * A plan may be run any number of times, on any capture of the same format and length. */
+typedef struct mdc_iq_extract_filter {
+    int32_t interpolate, decimate, ntaps;
+    int32_t first_tap;                   /* index of the filter's first tap in taps_host */
+} mdc_iq_extract_filter;
+typedef struct mdc_iq_extract_job {
+    int64_t first_pair, pairs;           /* the stretch [first_pair, first_pair + pairs) of the capture */
+    int64_t out_first, n_out;            /* its outputs: pairs [out_first, out_first + n_out) of out_dev */
+    uint32_t phase0, phase_step;         /* the oscillator, counted from first_pair */
+    int32_t filter, reserved;            /* index into filters_host; 0 */
+} mdc_iq_extract_job;
+MDC_API int64_t mdc_iq_extract_plan_bytes(int64_t njobs, int32_t nfilters, const mdc_iq_extract_job* jobs_host,
+                                          const mdc_iq_extract_filter* filters_host);
+MDC_API int mdc_iq_extract_plan(int format, int64_t pairs_in, const mdc_iq_extract_job* jobs_host, int64_t njobs,
+                                const mdc_iq_extract_filter* filters_host, int32_t nfilters, const int16_t* taps_host, int64_t ntaps_total,
+                                int64_t out_pairs, void* plan_host, int64_t plan_bytes);
+MDC_API int mdc_iq_extract(const void* iq_dev, int format, int64_t pairs_in, const void* plan_host, const void* plan_dev, int64_t plan_bytes,
+                           int16_t* out_dev, int64_t out_pairs, void* hip_stream);
 
 /* ---- power spectrogram: windowed FFTs of a raw capture, averaged (additive in ABI 5) ----------------------------------------
  * mdc_iq_ddc and mdc_iq_resample want to be told where the signal is and how wide; mdc_iq_spectrogram is what finds out: the

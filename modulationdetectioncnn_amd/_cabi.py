@@ -36,6 +36,7 @@ EXPORTS = [
     "mdc_iq_windows", "mdc_iq_windows_norm", "mdc_predict_host_iq", "mdc_predict_host_iq_norm",
     "mdc_iq_ddc", "mdc_iq_ddc_out_count", "mdc_iq_ddc_nco_table",
     "mdc_iq_resample", "mdc_iq_resample_out_count",
+    "mdc_iq_extract", "mdc_iq_extract_plan", "mdc_iq_extract_plan_bytes",
     "mdc_iq_spectrogram", "mdc_iq_spectrogram_rows", "mdc_iq_line_spectrum",
     "mdc_iq_channelizer", "mdc_iq_channelizer_out_count",
     "mdc_iq_spectrum_quantiles",
@@ -62,6 +63,11 @@ DDC_TILE_PAIRS, DDC_GRID_CAP = 8192, 1024
 # tiling (csrc/iq_resample.hip): a tile is ((RESAMPLE_TILE_PAIRS - ceil(T / L)) // D) * L outputs, RESAMPLE_GRID_CAP work-groups
 RESAMPLE_MAX_INTERPOLATE, RESAMPLE_MAX_DECIMATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BRANCH_ABS_SUM = 32, 256, 1024, 65535
 RESAMPLE_TILE_PAIRS, RESAMPLE_GRID_CAP = 8192, 1024
+# mdc_iq_extract: the records of include/mdc.h (mdc_iq_extract_filter, 16 B; mdc_iq_extract_job, 48 B).  Limits and tiling are the
+# resampler's, per filter; the kernel strides over the plan's (job, tile) list with at most RESAMPLE_GRID_CAP work-groups
+IQ_EXTRACT_FILTER = np.dtype([("interpolate", np.int32), ("decimate", np.int32), ("ntaps", np.int32), ("first_tap", np.int32)])
+IQ_EXTRACT_JOB = np.dtype([("first_pair", np.int64), ("pairs", np.int64), ("out_first", np.int64), ("n_out", np.int64),
+                           ("phase0", np.uint32), ("phase_step", np.uint32), ("filter", np.int32), ("reserved", np.int32)])
 # mdc_iq_spectrogram: limits of include/mdc.h, and the kernel's grid (csrc/iq_spectrogram.hip: kSpecGridCap): one work-group per
 # row, at most SPECTROGRAM_GRID_CAP of them; more rows are walked in passes
 SPECTROGRAM_MIN_NFFT, SPECTROGRAM_MAX_NFFT, SPECTROGRAM_MAX_AVG = 64, 4096, 4096
@@ -171,6 +177,8 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_iq_ddc_nco_table", [vp]),
                        ("mdc_iq_ddc", [vp, i32, i64, C.c_uint32, C.c_uint32, i32, vp, i32, vp, i64, vp]),
                        ("mdc_iq_resample", [vp, i32, i64, C.c_uint32, C.c_uint32, i32, i32, vp, i32, vp, i64, vp]),
+                       ("mdc_iq_extract_plan", [i32, i64, vp, i64, vp, C.c_int32, vp, i64, i64, vp, i64]),
+                       ("mdc_iq_extract", [vp, i32, i64, vp, vp, i64, vp, i64, vp]),
                        ("mdc_iq_spectrogram", [vp, i32, i64, i32, i64, i32, vp, C.c_float, vp, i64, vp]),
                        ("mdc_iq_line_spectrum", [vp, i32, i64, i32, i32, i64, i32, vp, C.c_float, vp, i64, vp]),
                        ("mdc_iq_channelizer", [vp, i32, i64, i64, i32, i32, vp, i32, i32, vp, i64, vp]),
@@ -183,6 +191,8 @@ def lib(variant: str = "product") -> C.CDLL:
         L.mdc_iq_ddc_out_count.argtypes, L.mdc_iq_ddc_out_count.restype = [i64, i32, i32], i64
     if getattr(L, "mdc_iq_resample_out_count", None) is not None:
         L.mdc_iq_resample_out_count.argtypes, L.mdc_iq_resample_out_count.restype = [i64, i32, i32, i32], i64
+    if getattr(L, "mdc_iq_extract_plan_bytes", None) is not None:
+        L.mdc_iq_extract_plan_bytes.argtypes, L.mdc_iq_extract_plan_bytes.restype = [i64, C.c_int32, vp, vp], i64
     if getattr(L, "mdc_iq_spectrogram_rows", None) is not None:
         L.mdc_iq_spectrogram_rows.argtypes, L.mdc_iq_spectrogram_rows.restype = [i64, i32, i64, i32], i64
     if getattr(L, "mdc_iq_channelizer_out_count", None) is not None:

@@ -1,7 +1,8 @@
 // The stages of mdc_iq_ddc (iq_ddc.hip) and mdc_iq_resample (iq_resample.hip) -- the "widening", "oscillator", "mixer" and
 // "filter" of include/mdc.h.  Both kernels use the loads, the table and the LDS geometry below; the DDC calls mix_tile and
 // fir_output, the resampler carries its own copies of those two for a measured reason (see its file head): what is said of the
-// stages here holds for both.
+// stages here holds for both.  mdc_iq_extract (iq_extract.hip) calls both as well, once per (job, tile): a job's slice is the base
+// pointer and the bound it hands mix_tile.
 //
 //   loads     the quad loads of the three sample formats (load_quad) and the oscillator table.
 //   mix       mix_tile: each thread takes four adjacent pairs at a time (one unaligned 8- or 16-byte vector load; the capture's

@@ -23,24 +23,11 @@
 // copies, line for line the same: with either call in its place rows of tools/resample_probe.py measured up to 6 % slower on the
 // MI355X, outside the spread of this code against itself (the rows: DESIGN.md 5.16, profiles/iq_frontend_ab.txt).  A change to
 // either stage is made in both places; tests/test_iq_resample_gpu.py::test_one_branch_is_the_ddc holds them to the same bits.
-#include "iq_mix.h"
+#include "iq_resample_plan.h"      // limits, tiling and the tap image, shared with mdc_iq_extract
 
 namespace mdc {
 
 namespace {
-
-constexpr int kResThreads = kIqMixThreads;
-constexpr long kResGridCap = 1024;       // work-groups; beyond it the kernel strides (_cabi.RESAMPLE_GRID_CAP)
-constexpr int kResMaxTaps = 1024, kResMaxDecimate = 256, kResMaxInterpolate = 32;
-constexpr int kResTapGroup = 4;          // tap dwords per step of the filter loop
-constexpr int kResTapDwords = 768;       // the branch-major image: L * stride <= 651 dwords over all 1 <= L <= 32, T <= 1024
-
-struct ResTaps { unsigned pk[kResTapDwords]; };
-
-struct ResPlan {
-    int L, D, ngroups, stride, tapdw, tile_out, tile_in;
-    bool odd;
-};
 
 template <int FMT, bool ODD>
 __global__ __launch_bounds__(kResThreads) void iq_resample_kernel(const unsigned char* __restrict__ iq, long pairs, unsigned phase0, unsigned step,
@@ -133,44 +120,6 @@ int resample_launch(const unsigned char* iq, int64_t pairs, uint32_t phase0, uin
     return MDC_OK;
 }
 
-int64_t resample_out_count(int64_t pairs, int ntaps, int L, int D) {
-    if (pairs < 1) return 0;
-    const int64_t lv = (pairs - 1) * L + 1;      // the zero-stuffed length; pairs <= 2^58 is checked
-    return lv >= ntaps ? (lv - ntaps) / D + 1 : 0;
-}
-
-int resample_shape_check(const char* who, int64_t pairs, int ntaps, int L, int D) {
-    if (L < 1 || L > kResMaxInterpolate) { set_error("%s: interpolate must be in 1..%d (got %d)", who, kResMaxInterpolate, L); return MDC_EINVAL; }
-    if (D < 1 || D > kResMaxDecimate) { set_error("%s: decimate must be in 1..%d (got %d)", who, kResMaxDecimate, D); return MDC_EINVAL; }
-    if (ntaps < 1 || ntaps > kResMaxTaps) { set_error("%s: ntaps must be in 1..%d (got %d)", who, kResMaxTaps, ntaps); return MDC_EINVAL; }
-    if (pairs < 0) { set_error("%s: negative pair count", who); return MDC_EINVAL; }
-    if (pairs > ((int64_t)1 << 58)) { set_error("%s: pair count beyond 2^58", who); return MDC_EINVAL; }
-    return MDC_OK;
-}
-
-int gcd(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
-
-// the tiling and the branch-major tap image for (L, D, taps); false if the image does not fit (it always does: see kResTapDwords)
-bool resample_plan(int L, int D, const int16_t* h, int ntaps, ResPlan& p, ResTaps& taps) {
-    const int longest = (ntaps + L - 1) / L;                                     // taps of branch 0, the longest branch
-    p.L = L;
-    p.D = D;
-    p.ngroups = ((longest + 1) / 2 + kResTapGroup - 1) / kResTapGroup;
-    p.stride = (kResTapGroup * p.ngroups) | 1;
-    p.tapdw = L * p.stride;
-    if (p.tapdw > kResTapDwords) return false;
-    const int q = (kIqTilePairs - longest) / D;                                  // >= (8192 - 1024) / 256
-    p.tile_out = q * L;
-    p.tile_in = q * D;
-    // an output of the class c (mod L / g) of a tile starts at the local sample ceil(c D / L) + k D / g
-    const int g = gcd(L, D);
-    p.odd = ((D / g) & 1) != 0;
-    for (int c = 0; c < L / g && !p.odd; ++c) p.odd = (((c * D + L - 1) / L) & 1) != 0;
-    for (int r = 0; r < L; ++r)
-        for (int i = 0; r + i * L < ntaps; ++i) taps.pk[r * p.stride + (i >> 1)] |= (unsigned)(uint16_t)h[r + i * L] << (16 * (i & 1));
-    return true;
-}
-
 }  // namespace
 
 }  // namespace mdc
@@ -208,7 +157,7 @@ int mdc_iq_resample(const void* iq_dev, int format, int64_t pairs_in, uint32_t p
     if (!iq_dev || !out_dev) { set_error("mdc_iq_resample: null buffer"); return MDC_EINVAL; }
     ResTaps taps{};
     ResPlan plan{};
-    if (!resample_plan(interpolate, decimate, taps_host, ntaps, plan, taps)) {
+    if (!resample_plan(interpolate, decimate, taps_host, ntaps, plan, taps.pk)) {
         set_error("mdc_iq_resample: internal: the branch-major tap image of %d taps in %d branches exceeds %d dwords", ntaps, interpolate, kResTapDwords);
         return MDC_EINVAL;
     }

@@ -450,6 +450,138 @@ def resample(iq, sample_format, shift: float = 0.0, interpolate: int = 1, decima
     return out
 
 
+# ---- batched extraction (mdc_iq_extract): K stretches of a capture, each through the resampler's chain, in one launch ---------
+def _int16_taps(taps) -> np.ndarray:
+    h = np.asarray(taps)
+    if h.dtype.kind != "i" or h.ndim != 1:
+        raise TypeError("taps must be a one-dimensional integer array (int16)")
+    if h.size and (h.min() < -32768 or h.max() > 32767):
+        raise ValueError("taps must fit int16")
+    return np.ascontiguousarray(h.astype(np.int16))
+
+
+def extract_plan(jobs, filters, sample_format, pairs_in: int, out_pairs=None):
+    """The plan of one mdc_iq_extract launch (include/mdc.h, "batched extraction"; host code, no GPU).  filters: a sequence of
+    (interpolate, decimate, taps); equal ones -- the same L, D and tap bytes -- are stored once.  jobs: a numpy array of
+    _cabi.IQ_EXTRACT_JOB records whose `filter` indexes `filters` and whose out_first / n_out are used as given (out_pairs: the
+    output's length, default the end of the last range), or a sequence of (first_pair, pairs, phase0, phase_step, filter, n_out),
+    which are packed back to back in the order given.  Returns (blob, out_pairs): the plan as a numpy uint8 array -- the same
+    inputs give the same bytes -- and the output's length in pairs.  Everything mdc_iq_extract_plan rejects is a _cabi.MdcError
+    that names the job."""
+    fmt = sample_format_id(sample_format)
+    unique, index, taps_all, recs = {}, [], [], []
+    for L, D, taps in filters:
+        h = _int16_taps(taps)
+        key = (int(L), int(D), h.tobytes())
+        if key not in unique:
+            unique[key] = len(recs)
+            recs.append((int(L), int(D), h.size, sum(t.size for t in taps_all)))
+            taps_all.append(h)
+        index.append(unique[key])
+    frec = np.array(recs, dtype=_cabi.IQ_EXTRACT_FILTER).reshape(-1)
+    h_all = np.ascontiguousarray(np.concatenate(taps_all)) if taps_all else np.zeros(0, np.int16)
+    if isinstance(jobs, np.ndarray) and jobs.dtype == _cabi.IQ_EXTRACT_JOB:
+        jrec = np.ascontiguousarray(jobs).reshape(-1).copy()
+        if out_pairs is None:
+            out_pairs = int((jrec["out_first"] + jrec["n_out"]).max()) if jrec.size else 0
+    else:
+        rows = [tuple(int(v) for v in j) for j in jobs]
+        jrec = np.zeros(len(rows), _cabi.IQ_EXTRACT_JOB)
+        at = 0
+        for k, (first, pairs, phase0, step, f, n_out) in enumerate(rows):
+            jrec[k] = (first, pairs, at, n_out, phase0 % (1 << 32), step % (1 << 32), f, 0)
+            at += max(n_out, 0)
+        if out_pairs is None:
+            out_pairs = at
+    known = (jrec["filter"] >= 0) & (jrec["filter"] < len(index))      # an unknown index stays one: the planner names the job
+    jrec["filter"][known] = np.asarray(index, np.int32)[jrec["filter"][known]] if len(index) else 0
+    jrec["filter"][~known] = -1
+    lib = _cabi.lib()
+    nbytes = _cabi.check(lib.mdc_iq_extract_plan_bytes(jrec.size, frec.size, jrec.ctypes.data, frec.ctypes.data))
+    blob = np.empty(nbytes, np.uint8)
+    _cabi.check(lib.mdc_iq_extract_plan(fmt, int(pairs_in), jrec.ctypes.data, jrec.size, frec.ctypes.data, frec.size, h_all.ctypes.data, h_all.size,
+                                        int(out_pairs), blob.ctypes.data, nbytes))
+    return blob, int(out_pairs)
+
+
+def extract_run(iq, sample_format, blob, out_pairs: int, out=None, device=None):
+    """One mdc_iq_extract launch of a plan of extract_plan on a capture (iq: as frames_from_iq).  Returns the (out_pairs, 2)
+    int16 device tensor; `out`, a tensor of that shape, is filled instead of a new one (pairs that no job names keep what they
+    held; a new tensor holds zeros there).  Enqueues on torch's current stream; the plan's device copy is an ordinary torch
+    transfer."""
+    import torch
+    fmt = sample_format_id(sample_format)
+    t = _device_samples(iq, fmt, device)
+    pairs = t.numel() * t.element_size() // _cabi.IQ_PAIR_BYTES[fmt]
+    if pairs * _cabi.IQ_PAIR_BYTES[fmt] != t.numel() * t.element_size():
+        raise ValueError("the capture is not a whole number of (I,Q) pairs")
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    if out is None:
+        out = torch.zeros((int(out_pairs), 2), dtype=torch.int16, device=t.device)
+    elif out.dtype != torch.int16 or tuple(out.shape) != (int(out_pairs), 2) or not out.is_contiguous() or out.device != t.device:
+        raise ValueError(f"out must be a contiguous ({int(out_pairs)}, 2) int16 tensor on the capture's device")
+    plan_dev = torch.from_numpy(blob).to(t.device)
+    with torch.cuda.device(t.device):
+        _cabi.check(_cabi.lib().mdc_iq_extract(t.data_ptr() if pairs else None, fmt, pairs, blob.ctypes.data, plan_dev.data_ptr(), blob.size,
+                                               out.data_ptr() if out_pairs else None, int(out_pairs), torch.cuda.current_stream(t.device).cuda_stream))
+    return out
+
+
+def extract(iq, sample_format, stretches, device=None, whole_frames: bool = True):
+    """Tune, low-pass and resample K stretches of one capture in ONE launch (mdc_iq_extract).  stretches: a sequence of
+    (first_pair, stop_pair, shift, interpolate, decimate, taps); stretch k gives what resample(iq[first_pair:stop_pair], ...,
+    shift, interpolate, decimate, taps) gives (for interpolate == 1: ddc), bit for bit -- the oscillator starts at phase 0 on
+    the stretch's first pair.  Returns (block, offsets): the (N, 2) int16 device tensor of all stretches' outputs back to back
+    and an int64 numpy array of K + 1 offsets, stretch k being block[offsets[k]:offsets[k + 1]].  whole_frames: every stretch
+    is trimmed to a multiple of 128 outputs, so that the block is whole frames and no window of predict_iq(block, "ci16")
+    straddles two stretches (a stretch of fewer than 128 outputs is empty)."""
+    import torch
+    fmt = sample_format_id(sample_format)
+    t = _device_samples(iq, fmt, device)
+    pairs_in = t.numel() * t.element_size() // _cabi.IQ_PAIR_BYTES[fmt]
+    lib = _cabi.lib()
+    jobs, filters, slot = [], [], {}
+    for first, stop, shift, L, D, taps in stretches:
+        (L, D), h = _check_resample_factors(L, D), np.asarray(taps)
+        key = (L, D, id(taps))      # the same array object again: no need to compare its bytes (extract_plan dedupes the rest)
+        if key not in slot:
+            slot[key] = len(filters)
+            filters.append((L, D, taps))
+        first, stop = int(first), int(stop)
+        if not 0 <= first <= stop <= pairs_in:
+            raise ValueError(f"stretch [{first}, {stop}) does not lie inside the capture's {pairs_in} pairs")
+        n = _cabi.check(lib.mdc_iq_resample_out_count(stop - first, h.size, L, D))
+        jobs.append((first, stop - first, 0, phase_step(shift), slot[key], n // HOP_FRAME * HOP_FRAME if whole_frames else n))
+    blob, out_pairs = extract_plan(jobs, filters, fmt, pairs_in)
+    offsets = np.zeros(len(jobs) + 1, np.int64)
+    np.cumsum([j[5] for j in jobs], out=offsets[1:])
+    block = torch.empty((out_pairs, 2), dtype=torch.int16, device=t.device)      # packed back to back: every pair is written
+    return extract_run(t, fmt, blob, out_pairs, out=block), offsets
+
+
+def segment_votes(labels, offsets, classes: int):
+    """Per segment k = labels[offsets[k]:offsets[k + 1]] the most frequent label among those >= 0 (the smallest on a tie; -1 when
+    there is none): VTCNN2.scan_iq's rule for all segments at once.  labels: an integer tensor of class indices < classes, -1
+    for "no label" (a squelched window); offsets: K + 1 non-decreasing window offsets, offsets[-1] <= len(labels).  Returns a (K,)
+    int64 tensor on labels' device; torch operations only, nothing synchronises."""
+    import torch
+    C = int(classes)
+    off = torch.as_tensor(np.asarray(offsets, np.int64) if not isinstance(offsets, torch.Tensor) else offsets, dtype=torch.int64).to(labels.device)
+    K = off.numel() - 1
+    if K < 0:
+        raise ValueError("offsets must hold at least one value")
+    lab = labels.reshape(-1).to(torch.int64)
+    at = torch.arange(lab.numel(), dtype=torch.int64, device=lab.device)
+    seg = torch.bucketize(at, off[1:], right=True)      # the segment of window i: how many segments end at or before it
+    counted = (lab >= 0) & (lab < C) & (at >= off[0]) & (seg < K)
+    counts = torch.zeros(max(K, 1) * C, dtype=torch.int64, device=lab.device)
+    counts.scatter_add_(0, torch.where(counted, seg * C + lab, torch.zeros_like(lab)), counted.to(torch.int64))
+    counts = counts.view(max(K, 1), C)[:K]
+    # the largest count, and among equals the smallest class: one key per class, no two equal
+    key = counts * C + torch.arange(C - 1, -1, -1, dtype=torch.int64, device=lab.device)
+    return torch.where(counts.sum(1) > 0, key.argmax(1), torch.full((K,), -1, dtype=torch.int64, device=lab.device))
+
+
 # ---- power spectrogram (mdc_iq_spectrogram) and the emitter scan: where the signals are, and how wide ------------------------
 def spectrogram_rows(pairs: int, nfft: int, hop: int, avg: int) -> int:
     """mdc_iq_spectrogram_rows: rows of a capture of `pairs` pairs -- ((pairs - nfft) // hop + 1) // avg, or 0 when pairs < nfft;
@@ -838,6 +970,21 @@ def channel_plan(centre: float, bandwidth: float, fill: float = DEFAULT_FILL, ma
         raise ValueError(f"no L / D with L <= {Lmax}, D <= {Dmax} comes within 1 % of {float(target):.6g} "
                          f"(fill {fill:g} of the output rate for a bandwidth of {bandwidth:g}); closest {f.numerator}/{f.denominator}")
     return -centre, f.numerator, f.denominator, bandwidth * f.denominator / f.numerator
+
+
+def channel_plans(emitters, fill: float = DEFAULT_FILL):
+    """channel_plan(centre, bandwidth, fill) for a sequence of (centre, bandwidth): the same tuples, with the search for L / D made
+    once per distinct bandwidth -- the boxes of a spectrogram have few widths (a number of bins over nfft), and the search, exact
+    rationals over every L, is most of what a plan costs."""
+    ratios, out = {}, []
+    for centre, bandwidth in emitters:
+        centre, bandwidth = float(centre), float(bandwidth)
+        if bandwidth not in ratios:
+            ratios[bandwidth] = channel_plan(centre, bandwidth, fill)[1:]
+        elif not (np.isfinite(centre) and -0.5 <= centre <= 0.5):
+            raise ValueError(f"centre must lie in [-0.5, 0.5] cycles per sample (got {centre!r})")
+        out.append((-centre,) + ratios[bandwidth])
+    return out
 
 
 def plan_taps(interpolate: int, decimate: int) -> np.ndarray:

@@ -1071,7 +1071,7 @@ class VTCNN2:
 
     def detect_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_db: float = 6.0, floor: str = "flat", reach_rows: int = 2,
                   reach_bins: int = 3, min_rows: int = 3, min_bins: int = 3, hop: int = 128, level: float = 7.8e-3,
-                  squelch_dbfs: Optional[float] = None, dc_guard: int = 1):
+                  squelch_dbfs: Optional[float] = None, dc_guard: int = 1, batched: bool = False):
         """A wideband capture in, "what transmitted when, where, and what modulation" out: the scan in two dimensions, for
         frequency hoppers, emitters that share bins at different times and single packets, which scan_iq's one-dimensional
         searches miss or mangle.  The capture's spectrogram (frontend.spectrogram, as scan_iq builds it: nfft bins, segments nfft //
@@ -1087,16 +1087,26 @@ class VTCNN2:
         windows the squelch let through (the smallest on a tie; -1 if there are none).  A detection whose pairs are too few for
         one window gives windows = 0, label = -1 and empty results.  The default dc_guard of 1 switches bins -1, 0, +1 off, a gap
         of three that reach_bins = 3 does not bridge: an emitter ON bin 0 comes out as two boxes, one each side of the guard.  A
-        capture without a DC spike takes dc_guard=0 (only bin 0 off) and gets it as one."""
+        capture without a DC spike takes dc_guard=0 (only bin 0 off) and gets it as one.
+        batched=True gives the same records, key for key and bit for bit, without the loop over detections: one
+        frontend.extract launch tunes, filters and resamples every detection's pairs into one block of whole frames, one
+        predict_iq classifies the block, frontend.segment_votes takes every detection's vote on the device, and the labels come to
+        the host in one transfer; probs, labels and window_dbfs are then slices of the block's results.  It needs hop == 128 (with
+        another hop windows would straddle detections: ValueError)."""
         torch = _torch()
         from . import frontend as F
         fmt = F.sample_format_id(sample_format)
+        if batched and hop != 128:
+            raise ValueError(f"batched=True needs hop == 128 (got {hop}): windows at another hop would straddle two detections")
         as_numpy = not isinstance(iq, torch.Tensor)
         dev = F._device_samples(iq, fmt, f"cuda:{self.device_index}")
         spec = F.spectrogram(dev, fmt, nfft=nfft, avg=avg)
         if spec.shape[0] == 0:
             raise ValueError(f"the capture is too short for one row of {avg} segments of {nfft} pairs")
         thresh = F.detection_threshold(spec, threshold_db, dc_guard, floor)
+        if batched:
+            found = F.find_detections(spec, thresh, reach_rows, reach_bins, min_rows, min_bins, avg=avg)
+            return self._classify_detections(dev, fmt, found, level, squelch_dbfs, as_numpy)
         per_pair = _cabi.IQ_PAIR_BYTES[fmt] // dev.element_size()      # elements of `dev` per (I,Q) pair
         Cn = self.topology.classes
         out = []
@@ -1128,6 +1138,37 @@ class VTCNN2:
                 probs, labels, dbfs = probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy()
             out.append(dict(d._asdict(), shift=shift, interpolate=L, decimate=D, probs=probs, labels=labels, window_dbfs=dbfs, windows=windows,
                             label=label))
+        return out
+
+    def _classify_detections(self, dev, fmt, found, level, squelch_dbfs, as_numpy):
+        """detect_iq(batched=True) behind the search: the records of `found` (frontend.find_detections) on the device capture dev"""
+        torch = _torch()
+        from . import frontend as F
+        if not found:
+            return []
+        Cn = self.topology.classes
+        taps, plans = {}, [p[:3] for p in F.channel_plans([(d.centre, d.bandwidth) for d in found])]
+        for _, L, D in plans:
+            if (L, D) not in taps:
+                taps[L, D] = F.plan_taps(L, D)
+        block, offsets = F.extract(dev, fmt, [(d.first_pair, d.stop_pair, shift, L, D, taps[L, D]) for d, (shift, L, D) in zip(found, plans)],
+                                   whole_frames=True)
+        first = (offsets // 128).tolist()      # in windows
+        if block.shape[0]:
+            probs, labels, dbfs = self.predict_iq(block.reshape(-1), _cabi.IQ_CI16, normalize="rms", level=level, squelch_dbfs=squelch_dbfs,
+                                                  return_power=True)
+        else:
+            probs = torch.empty((0, Cn), dtype=torch.float32, device=dev.device)
+            labels = torch.empty((0,), dtype=torch.int32, device=dev.device)
+            dbfs = torch.empty((0,), dtype=torch.float64, device=dev.device)
+        label = F.segment_votes(labels, offsets // 128, Cn).cpu().tolist()      # the one transfer of the K labels
+        if as_numpy:
+            probs, labels, dbfs = probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy()
+        out = []
+        for k, (d, (shift, L, D)) in enumerate(zip(found, plans)):
+            a, z = first[k], first[k + 1]
+            out.append(dict(d._asdict(), shift=shift, interpolate=L, decimate=D, probs=probs[a:z], labels=labels[a:z], window_dbfs=dbfs[a:z],
+                            windows=z - a, label=label[k]))
         return out
 
     def predict_channels(self, iq, sample_format, channels: int, decimate: Optional[int] = None, taps=None, tap_shift: Optional[int] = None,
