@@ -85,8 +85,9 @@ static int layer_layout(mdc_model* m) {
             m->slots = {{"mdc_vt_conv"}, {"mdc_vt_dense1"}, {"mdc_vt_head"}};
             return MDC_OK;
         case MDC_KIND_CNNPY:
-            if (t.filters < 1 || t.filters > 10 || t.hidden < 1 || t.hidden > 16 || t.classes < 2 || t.classes > 16) {
-                set_error("cnnpy: need filters 1..10, hidden 1..16, classes 2..16 (got %d,%d,%d)", t.filters, t.hidden, t.classes);
+            if (t.filters < 1 || t.filters > 10 || t.hidden < 1 || t.hidden > 16 || t.classes < 1 || t.classes > 16) {
+                // (classes = 1 is Keras' Dense(1) + softmax: a row of 1.0 and label 0 -- the narrowest shape dense_chain serves)
+                set_error("cnnpy: need filters 1..10, hidden 1..16, classes 1..16 (got %d,%d,%d)", t.filters, t.hidden, t.classes);
                 return MDC_ENOTSUP;
             }
             m->nlayers = 3;

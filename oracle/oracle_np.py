@@ -21,6 +21,9 @@ What it restates (all file:line are into /root/reference):
   TensorFlow backend ``Reshape([1,2,128])`` is H=1, W=2, C=128.
 * ``argmax_first``      -- ``int(np.argmax(row))`` of cnn.py:209 (first max wins).
 
+Each forward is a chain of per-layer functions (``deployed_conv``, ``vtcnn2_conv1``, ``vtcnn2_conv2``, ``cnnpy_conv``,
+``dense``) that can be called one by one: tests/exact_fixtures.py puts a precision mode's narrowing conversions between them.
+
 The arithmetic itself lives in TensorFlow 2.4.0 / Keras 2.4.0 (versions from
 the .h5 attributes), which are not vendored and not installed here; the Keras
 layer semantics restated are: ZeroPadding2D((0,p)) pads W only; Conv2D is
@@ -61,6 +64,25 @@ def _as(x, dtype):
 # ---------------------------------------------------------------------------
 # T1 / T2: deployed single-conv nets  (CNN.ipynb cell 6)
 # ---------------------------------------------------------------------------
+def dense(x, kernel, bias, relu: bool, dtype=np.float32) -> np.ndarray:
+    """Keras Dense: x @ W + b, then ReLU if the layer has one.  One layer of every net below."""
+    z = _as(x, dtype) @ _as(kernel, dtype) + _as(bias, dtype)
+    return np.maximum(z, dtype(0)) if relu else z
+
+
+def deployed_conv(x, conv_kernel, conv_bias, dtype=np.float32) -> np.ndarray:
+    """ZeroPadding2D((0,1)) + Conv2D(F,(1,2),relu) of the deployed nets: x (N,2,128) -> (N,2,129,F) channels_last."""
+    x = _as(x, dtype)
+    k = _as(conv_kernel, dtype).reshape(2, -1)           # [kw][f]
+    b = _as(conv_bias, dtype)
+    n = x.shape[0]
+    xp = np.zeros((n, 2, 130), dtype)                    # ZeroPadding2D((0,1)): W only
+    xp[:, :, 1:129] = x
+    # y[n,h,w,f] = relu(b[f] + K[0,0,0,f]*xp[w] + K[0,1,0,f]*xp[w+1]),  w = 0..128
+    y = xp[:, :, 0:129, None] * k[0] + xp[:, :, 1:130, None] * k[1] + b
+    return np.maximum(y, dtype(0))
+
+
 def forward_deployed(x, conv_kernel, conv_bias, dense_kernel, dense_bias, dtype=np.float32) -> Dict[str, np.ndarray]:
     """x (N,2,128); conv_kernel HWIO (1,2,1,F); dense_kernel (258F, C).
 
@@ -68,26 +90,49 @@ def forward_deployed(x, conv_kernel, conv_bias, dense_kernel, dense_bias, dtype=
     'flat' (N,258F) = model3, 'dense' (N,C) post-ReLU pre-softmax = model2,
     'probs' = model5 / model.predict, 'labels' = first-max argmax.
     """
-    x = _as(x, dtype)
-    k = _as(conv_kernel, dtype).reshape(2, -1)           # [kw][f]
-    b = _as(conv_bias, dtype)
-    wd = _as(dense_kernel, dtype)
-    bd = _as(dense_bias, dtype)
-    n = x.shape[0]
-    xp = np.zeros((n, 2, 130), dtype)                    # ZeroPadding2D((0,1)): W only
-    xp[:, :, 1:129] = x
-    # y[n,h,w,f] = relu(b[f] + K[0,0,0,f]*xp[w] + K[0,1,0,f]*xp[w+1]),  w = 0..128
-    y = xp[:, :, 0:129, None] * k[0] + xp[:, :, 1:130, None] * k[1] + b
-    y = np.maximum(y, dtype(0))
-    flat = y.reshape(n, 258 * k.shape[1])                # channels_last: h*129F + w*F + f
-    dense = np.maximum(flat @ wd + bd, dtype(0))         # Dense(C, activation='relu')
-    probs = softmax(dense)
-    return {"conv": y, "flat": flat, "dense": dense, "probs": probs, "labels": argmax_first(probs)}
+    y = deployed_conv(x, conv_kernel, conv_bias, dtype)
+    flat = y.reshape(y.shape[0], 258 * y.shape[3])      # channels_last: h*129F + w*F + f
+    d = dense(flat, dense_kernel, dense_bias, True, dtype)   # Dense(C, activation='relu')
+    probs = softmax(d)
+    return {"conv": y, "flat": flat, "dense": d, "probs": probs, "labels": argmax_first(probs)}
 
 
 # ---------------------------------------------------------------------------
 # T3: canonical VT-CNN2  (RML2016.10a_VTCNN2_example.ipynb:229-243)
 # ---------------------------------------------------------------------------
+def vtcnn2_conv1(x, conv1_kernel, conv1_bias, dtype=np.float32) -> np.ndarray:
+    """ZeroPadding2D((0,2)) + Conv2D(256,(1,3),relu), channels_first: x (m,2,128) -> (m,256,2,130)."""
+    x = _as(x, dtype)
+    k1 = _as(conv1_kernel, dtype).reshape(conv1_kernel.shape[0], 3)        # [c][j]
+    b1 = _as(conv1_bias, dtype)
+    m = x.shape[0]
+    xp = np.zeros((m, 2, 132), dtype)                    # ZeroPadding2D((0,2))
+    xp[:, :, 2:130] = x
+    # conv1 (1x3), 256 filters: y1[m,c,h,w], w = 0..129
+    y1 = (k1[None, :, None, None, 0] * xp[:, None, :, 0:130]
+          + k1[None, :, None, None, 1] * xp[:, None, :, 1:131]
+          + k1[None, :, None, None, 2] * xp[:, None, :, 2:132]
+          + b1[None, :, None, None])
+    return np.maximum(y1, dtype(0))
+
+
+def vtcnn2_conv2(y1, conv2_kernel, conv2_bias, dtype=np.float32) -> np.ndarray:
+    """ZeroPadding2D((0,2)) + Conv2D(80,(2,3),relu), channels_first: y1 (m,256,2,130) -> (m,80,132)."""
+    y1 = _as(y1, dtype)
+    k2 = _as(conv2_kernel, dtype)                                           # [o][c][h][j]
+    co, ci = k2.shape[0], k2.shape[1]
+    k2m = np.ascontiguousarray(k2.transpose(1, 2, 3, 0)).reshape(ci * 6, co)   # rows (c,h,j)
+    b2 = _as(conv2_bias, dtype)
+    m = y1.shape[0]
+    y1p = np.zeros((m, ci, 2, 134), dtype)               # ZeroPadding2D((0,2))
+    y1p[:, :, :, 2:132] = y1
+    # conv2 (2x3) over 256 channels, 80 filters: im2col rows (c,h,j) -> matmul
+    win = np.lib.stride_tricks.sliding_window_view(y1p, 3, axis=3)     # (m,c,2,132,3)
+    a = np.ascontiguousarray(win.transpose(0, 3, 1, 2, 4)).reshape(m * 132, ci * 6)
+    y2 = np.maximum(a @ k2m + b2, dtype(0)).reshape(m, 132, co)
+    return np.ascontiguousarray(y2.transpose(0, 2, 1))                 # (m,80,132) channels_first
+
+
 def forward_vtcnn2(x, conv1_kernel, conv1_bias, conv2_kernel, conv2_bias,
                    dense1_kernel, dense1_bias, dense2_kernel, dense2_bias,
                    dtype=np.float32, chunk: int = 64, taps: bool = False) -> Dict[str, np.ndarray]:
@@ -96,12 +141,8 @@ def forward_vtcnn2(x, conv1_kernel, conv1_bias, conv2_kernel, conv2_bias,
     Dropout layers are identity at inference.
     """
     x = _as(x, dtype)
-    k1 = _as(conv1_kernel, dtype).reshape(conv1_kernel.shape[0], 3)        # [c][j]
-    b1 = _as(conv1_bias, dtype)
-    k2 = _as(conv2_kernel, dtype)                                           # [o][c][h][j]
-    co, ci = k2.shape[0], k2.shape[1]
-    k2m = np.ascontiguousarray(k2.transpose(1, 2, 3, 0)).reshape(ci * 6, co)   # rows (c,h,j)
-    b2 = _as(conv2_bias, dtype)
+    k1, b1 = _as(conv1_kernel, dtype), _as(conv1_bias, dtype)
+    k2, b2 = _as(conv2_kernel, dtype), _as(conv2_bias, dtype)
     w1, bb1 = _as(dense1_kernel, dtype), _as(dense1_bias, dtype)
     w2, bb2 = _as(dense2_kernel, dtype), _as(dense2_bias, dtype)
     n = x.shape[0]
@@ -110,26 +151,11 @@ def forward_vtcnn2(x, conv1_kernel, conv1_bias, conv2_kernel, conv2_bias,
         out["conv1"] = []
         out["conv2"] = []
     for s in range(0, n, chunk):
-        xb = x[s:s + chunk]
-        m = xb.shape[0]
-        xp = np.zeros((m, 2, 132), dtype)                # ZeroPadding2D((0,2))
-        xp[:, :, 2:130] = xb
-        # conv1 (1x3), 256 filters: y1[m,c,h,w], w = 0..129
-        y1 = (k1[None, :, None, None, 0] * xp[:, None, :, 0:130]
-              + k1[None, :, None, None, 1] * xp[:, None, :, 1:131]
-              + k1[None, :, None, None, 2] * xp[:, None, :, 2:132]
-              + b1[None, :, None, None])
-        y1 = np.maximum(y1, dtype(0))
-        y1p = np.zeros((m, ci, 2, 134), dtype)           # ZeroPadding2D((0,2))
-        y1p[:, :, :, 2:132] = y1
-        # conv2 (2x3) over 256 channels, 80 filters: im2col rows (c,h,j) -> matmul
-        win = np.lib.stride_tricks.sliding_window_view(y1p, 3, axis=3)     # (m,c,2,132,3)
-        a = np.ascontiguousarray(win.transpose(0, 3, 1, 2, 4)).reshape(m * 132, ci * 6)
-        y2 = np.maximum(a @ k2m + b2, dtype(0)).reshape(m, 132, co)
-        y2 = np.ascontiguousarray(y2.transpose(0, 2, 1))                   # (m,80,132) channels_first
-        flat = y2.reshape(m, co * 132)                                     # idx o*132 + w
-        d1 = np.maximum(flat @ w1 + bb1, dtype(0))
-        lg = d1 @ w2 + bb2
+        y1 = vtcnn2_conv1(x[s:s + chunk], k1, b1, dtype)
+        y2 = vtcnn2_conv2(y1, k2, b2, dtype)
+        flat = y2.reshape(y2.shape[0], y2.shape[1] * 132)                        # idx o*132 + w
+        d1 = dense(flat, w1, bb1, True, dtype)
+        lg = dense(d1, w2, bb2, False, dtype)
         out["flat"].append(flat)
         out["dense1"].append(d1)
         out["logits"].append(lg)
@@ -145,21 +171,26 @@ def forward_vtcnn2(x, conv1_kernel, conv1_bias, conv2_kernel, conv2_bias,
 # ---------------------------------------------------------------------------
 # T4: the literal cnn.py model  (cnn.py:104-115)
 # ---------------------------------------------------------------------------
-def forward_cnnpy(x, conv_kernel, conv_bias, dense1_kernel, dense1_bias,
-                  dense2_kernel, dense2_bias, dtype=np.float32) -> Dict[str, np.ndarray]:
-    """x (N,2,128) -> Reshape([1,2,128]) = (H=1, W=2, C=128) under channels_last;
-    ZeroPadding2D((0,1)) -> W=4; Conv2D(10,(1,2)) HWIO (1,2,128,F) -> (1,3,F);
-    Flatten (w,f); Dense(10,relu); Dense(5); softmax."""
+def cnnpy_conv(x, conv_kernel, conv_bias, dtype=np.float32) -> np.ndarray:
+    """Reshape([1,2,128]) = (H=1, W=2, C=128) + ZeroPadding2D((0,1)) + Conv2D(F,(1,2),relu): x (N,2,128) -> (N,3,F)."""
     x = _as(x, dtype)
     k = _as(conv_kernel, dtype).reshape(2, 128, -1)       # [kw][c][f]
     n = x.shape[0]
     xp = np.zeros((n, 4, 128), dtype)                    # [w][c]
     xp[:, 1:3, :] = x
     y = np.stack([xp[:, w, :] @ k[0] + xp[:, w + 1, :] @ k[1] for w in range(3)], axis=1)
-    y = np.maximum(y + _as(conv_bias, dtype), dtype(0))  # (n,3,F)
-    flat = y.reshape(n, -1)
-    d1 = np.maximum(flat @ _as(dense1_kernel, dtype) + _as(dense1_bias, dtype), dtype(0))
-    lg = d1 @ _as(dense2_kernel, dtype) + _as(dense2_bias, dtype)
+    return np.maximum(y + _as(conv_bias, dtype), dtype(0))  # (n,3,F)
+
+
+def forward_cnnpy(x, conv_kernel, conv_bias, dense1_kernel, dense1_bias,
+                  dense2_kernel, dense2_bias, dtype=np.float32) -> Dict[str, np.ndarray]:
+    """x (N,2,128) -> Reshape([1,2,128]) = (H=1, W=2, C=128) under channels_last;
+    ZeroPadding2D((0,1)) -> W=4; Conv2D(10,(1,2)) HWIO (1,2,128,F) -> (1,3,F);
+    Flatten (w,f); Dense(10,relu); Dense(5); softmax."""
+    y = cnnpy_conv(x, conv_kernel, conv_bias, dtype)
+    flat = y.reshape(y.shape[0], 3 * y.shape[2])
+    d1 = dense(flat, dense1_kernel, dense1_bias, True, dtype)
+    lg = dense(d1, dense2_kernel, dense2_bias, False, dtype)
     probs = softmax(lg)
     return {"conv": y, "flat": flat, "dense1": d1, "logits": lg, "probs": probs, "labels": argmax_first(probs)}
 

@@ -3,7 +3,8 @@
 Tolerances: Dense+ReLU tap 5e-6 abs for the Keras known answer (BASELINE.md section 2);
 2e-6 * scale abs for f32 vs the f64 oracle elsewhere; probabilities 2e-6 abs.  Labels must be
 bit-exact wherever the f64 oracle's top-2 margin exceeds 1e-5 (relative to the largest
-output); exact ties ([0,0,0] after ReLU) must resolve to the FIRST maximum."""
+output); exact ties ([0,0,0] after ReLU) must resolve to the FIRST maximum.
+Faults too small for these bars are caught in tests/test_exact_fixtures_gpu.py (integer fixtures, bit-for-bit against the oracle)."""
 import json
 import os
 

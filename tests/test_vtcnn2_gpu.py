@@ -13,7 +13,8 @@ homogeneous in its input scale):
                      round 4: E4M3 features between conv2 and dense1 as well -- the 'flat' / 'conv' taps carry that rounding, v/16)
 i.e. about twice (fp8: 1.25 x) what is measured -- round 2's 2e-2 / 8e-2 would have passed a kernel three times as wrong.
 Probabilities: half the logit bar (softmax contracts).  Labels: bit-exact wherever the oracle's top-2 logit margin
-exceeds 4x the tolerance; every frame counts in tests/test_label_agreement_gpu.py."""
+exceeds 4x the tolerance; every frame counts in tests/test_label_agreement_gpu.py.
+Faults too small for these bars are caught in tests/test_exact_fixtures_gpu.py (integer fixtures, bit-for-bit against the oracle)."""
 import ctypes
 
 import numpy as np
