@@ -6,8 +6,10 @@
 so that `model.fit(..., callbacks=[...])` reads here as it reads there.  They are descriptions -- `Trainer.fit` runs the loop
 and consults the two small state machines below, which restate Keras 2.4's rules (tensorflow/python/keras/callbacks.py):
   ModelCheckpoint   on_epoch_end: save when `current < best` (save_best_only) or always; `best` starts at +inf.
-  EarlyStopping     on_epoch_end: `current - min_delta < best` resets `wait` (and remembers the weights if
-                    restore_best_weights), otherwise `wait += 1` and training stops once `wait >= patience`.
+  EarlyStopping     on_epoch_end: `current + |min_delta| < best` resets `wait` (and remembers the weights if
+                    restore_best_weights), otherwise `wait += 1` and training stops once `wait >= patience`.  (Keras
+                    writes `np.less(current - min_delta, best)` after `min_delta *= -1` for a minimised monitor: only
+                    a value at least |min_delta| BELOW the best counts as an improvement.)
 Only what a loss needs is built: monitor 'val_loss' (or 'loss'), mode 'auto' / 'min'."""
 from __future__ import annotations
 
@@ -68,7 +70,7 @@ class EarlyStopping:
         """-> (improved, stop) for this epoch's monitored value."""
         if current is None:
             return False, False
-        if current - self.min_delta < self.best:
+        if current + self.min_delta < self.best:
             self.best = current
             self.wait = 0
             return True, False
