@@ -399,6 +399,15 @@ def _lsb_log2(a) -> int:
 def check_preconditions(fx: Fixture, mode: str = "f32", fp8_bf16_features: bool = False, verbose: bool = False, frames=None) -> Dict[str, float]:
     """Asserts, on the oracle alone, that the GPU must reproduce `expected()` bit for bit, and returns the bounds it found.
     frames: other frames than the fixture's own (the same preconditions, checked on them)."""
+    return _check(fx, mode, fp8_bf16_features, verbose, frames)[0]
+
+
+def checked_expected(fx: Fixture, mode: str = "f32", fp8_bf16_features: bool = False, frames=None) -> Dict[str, np.ndarray]:
+    """`expected()`'s arrays, handed out only after the preconditions held on them (one oracle pass for both)."""
+    return _check(fx, mode, fp8_bf16_features, False, frames)[1]
+
+
+def _check(fx: Fixture, mode: str, fp8_bf16_features: bool, verbose: bool, frames):
     out, t = expected(fx, mode, fp8_bf16_features, frames=frames)
     tag = f"{fx.kind}{fx.shape} {fx.flavour} {mode}{'+bf16feat' if fp8_bf16_features else ''}"
     bounds: Dict[str, float] = {}
@@ -455,7 +464,7 @@ def check_preconditions(fx: Fixture, mode: str = "f32", fp8_bf16_features: bool 
         print(f"[exact fixture] {tag}")
         for k, v in bounds.items():
             print(f"    {k}: {v:.6g}")
-    return bounds
+    return bounds, out
 
 
 def batch_indices(n: int, nframes: int, seed: int) -> np.ndarray:
@@ -463,3 +472,65 @@ def batch_indices(n: int, nframes: int, seed: int) -> np.ndarray:
     rng = np.random.default_rng([seed, n])
     idx = np.concatenate([np.arange(nframes)] * (n // nframes) + [rng.choice(nframes, size=n % nframes, replace=False)])
     return rng.permutation(idx)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# raw uint8 I/Q captures that stand for exact frames
+# ----------------------------------------------------------------------------------------------------------------------
+# (byte - 127.5) 2^-6 = (2 byte - 255) U: an odd number of units, exact in f32 (127.5 and 2^-6 are f32 numbers, the difference
+# has at most 9 significant bits).  Bytes 127 / 128 are +-U, VT-CNN2's amp = 1 range without its zeros; bytes 126..129 are +-U
+# and +-3U, the deployed nets' amp = 3 range.  The fixtures' weights, scales and fp8_input_absmax = U serve unchanged.
+RAW_SCALE = 2.0 ** -6
+RAW_BYTES = {"vtcnn2": (127, 128), "deployed": (126, 127, 128, 129)}
+RAW_FRAMES = 64                                   # raw fixture frames of the hop-128 layout, as many as Fixture.frames
+RAW_PERIOD = {64: 64 * 128, 3: 384}               # pairs per period of the periodic layouts: 128 distinct windows each
+
+
+def raw_fixture_frames(kind: str, seed: int) -> np.ndarray:
+    """The RAW_FRAMES raw fixture frames: (64, 256) uint8, 128 (I, Q) byte pairs each, seeded draws from RAW_BYTES[kind]."""
+    rng = np.random.default_rng([seed, len(RAW_BYTES[kind]), 128])
+    return rng.choice(np.array(RAW_BYTES[kind], np.uint8), size=(RAW_FRAMES, 256))
+
+
+def raw_capture(kind: str, hop: int, seed: int, idx=None, windows: Optional[int] = None) -> np.ndarray:
+    """The uint8 stream I0, Q0, I1, Q1, ... of a capture whose windows (128 pairs, `hop` pairs apart) are exact fixture frames.
+    hop 128: window i is raw fixture frame idx[i] (idx from batch_indices); the oracle runs on the 64 raw frames
+             (idx = arange(RAW_FRAMES)) and the expectation is want[idx].
+    hop 64, 3: `windows` windows of a periodic stream, period RAW_PERIOD[hop] pairs = 128 hops: window i is window i mod 128;
+             the oracle runs on raw_capture(..., windows=128) and the expectation is want[arange(windows) % 128]."""
+    if hop == 128:
+        assert idx is not None and windows is None
+        return np.ascontiguousarray(raw_fixture_frames(kind, seed)[np.asarray(idx)]).reshape(-1)
+    assert idx is None and windows is not None and windows >= 1
+    period = RAW_PERIOD[hop]
+    assert period % hop == 0
+    rng = np.random.default_rng([seed, len(RAW_BYTES[kind]), hop])
+    one = rng.choice(np.array(RAW_BYTES[kind], np.uint8), size=2 * period)
+    pairs = (windows - 1) * hop + 128
+    return np.ascontiguousarray(np.tile(one, -(-pairs // period))[:2 * pairs])
+
+
+def raw_period_windows(hop: int) -> int:
+    """Distinct windows of the periodic layout at this hop."""
+    return RAW_PERIOD[hop] // hop
+
+
+def raw_windows(stream, hop: int, scale: float = RAW_SCALE, first_pair: int = 0, swap_iq: bool = False) -> np.ndarray:
+    """The library's windowing and conversion (mdc_iq_u8_windows, include/mdc.h) restated in numpy f32: window i is pairs
+    [i hop, i hop + 128), row 0 = (I - 127.5) scale from the even bytes, row 1 = (Q - 127.5) scale from the odd ones.
+    first_pair / swap_iq: the sensitivity check's faults (window i taken from pair i hop + first_pair; I and Q exchanged)."""
+    pairs = np.asarray(stream, np.uint8).reshape(-1, 2)
+    n = 0 if len(pairs) < 128 + first_pair else (len(pairs) - 128 - first_pair) // hop + 1
+    at = np.arange(n)[:, None] * hop + first_pair + np.arange(128)[None, :]
+    w = pairs[at].astype(np.float32)                       # (n, 128, 2)
+    if swap_iq:
+        w = w[:, :, ::-1]
+    sc = np.float32(scale)
+    return np.ascontiguousarray(np.stack([(w[:, :, 0] - np.float32(127.5)) * sc, (w[:, :, 1] - np.float32(127.5)) * sc], axis=1))
+
+
+def raw_oracle_frames(kind: str, hop: int, seed: int) -> np.ndarray:
+    """The distinct windows of a layout, as frames: what the oracle is run on (64 at hop 128, 128 at the periodic hops)."""
+    if hop == 128:
+        return raw_windows(raw_capture(kind, 128, seed, idx=np.arange(RAW_FRAMES)), 128)
+    return raw_windows(raw_capture(kind, hop, seed, windows=raw_period_windows(hop)), hop)

@@ -188,3 +188,85 @@ def test_sensitivity_to_a_truncating_conversion(kind, shape, mode):
     good = X.expected(fx, mode)[0]
     point = "conv2.out" if kind == "vtcnn2" else "conv.out"
     assert _detected(kind, mode, good, X.expected(fx, mode, corrupt=("trunc", point))[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# raw uint8 I/Q captures (exact_fixtures.raw_capture / raw_windows): the byte streams tests/test_exact_walks_gpu.py feeds to
+# predict_iq_u8 stand for exact frames, the preconditions hold on them, and a window taken one pair off changes the expectation
+# ---------------------------------------------------------------------------------------------------------------
+RAW_SEED = 0            # (the GPU file's seed; the preconditions below are what qualifies it)
+RAW_HOPS = (128, 64, 3)
+RAW_CASES = [c for c in CASES if c[0] != "cnnpy"]      # cnn.py's net converts first and forwards frames: no raw-byte kernel
+RAW_IDS = [i for i, c in zip(IDS, CASES) if c[0] != "cnnpy"]
+
+
+@pytest.mark.parametrize("kind", ["vtcnn2", "deployed"])
+def test_raw_captures_stand_for_odd_multiples_of_the_unit(kind):
+    units = {"vtcnn2": {-1, 1}, "deployed": {-3, -1, 1, 3}}[kind]
+    raw = X.raw_fixture_frames(kind, RAW_SEED)
+    assert raw.shape == (64, 256) and raw.dtype == np.uint8 and set(np.unique(raw)) == set(X.RAW_BYTES[kind])
+    # hop 128: window i is raw fixture frame idx[i]: I from the even bytes, Q from the odd ones, (2 byte - 255) U exactly
+    idx = X.batch_indices(257, 64, seed=257)
+    stream = X.raw_capture(kind, 128, RAW_SEED, idx=idx)
+    assert stream.dtype == np.uint8 and stream.shape == (257 * 256,)
+    fr = X.raw_windows(stream, 128)
+    assert fr.dtype == np.float32 and fr.shape == (257, 2, 128)
+    want = (2 * raw[idx].astype(np.int64).reshape(257, 128, 2).transpose(0, 2, 1) - 255) * X.U      # integers times 2^-7: exact in f64
+    assert np.array_equal(fr.astype(np.float64), want)
+    assert set(np.unique(fr.astype(np.float64) / X.U)) == units
+    assert np.array_equal(X.raw_oracle_frames(kind, 128, RAW_SEED)[idx], fr)
+    # the periodic layouts: 128 distinct windows, window i = window i mod 128, however long the stream is
+    for hop in (64, 3):
+        assert X.raw_period_windows(hop) == 128
+        n = 128 * 2 + 37
+        stream = X.raw_capture(kind, hop, RAW_SEED, windows=n)
+        assert stream.shape == (2 * ((n - 1) * hop + 128),)
+        fr = X.raw_windows(stream, hop)
+        one = X.raw_oracle_frames(kind, hop, RAW_SEED)
+        assert fr.shape == (n, 2, 128) and one.shape == (128, 2, 128)
+        assert np.array_equal(fr, one[np.arange(n) % 128])
+        assert set(np.unique(fr.astype(np.float64) / X.U)) == units
+        assert len(np.unique(one.reshape(128, -1), axis=0)) == 128                # ... and they ARE distinct
+        pairs = stream.reshape(-1, 2)
+        assert np.array_equal(fr[5, 0], (2.0 * pairs[5 * hop:5 * hop + 128, 0] - 255) * X.U)      # I: even bytes, from pair i hop
+        assert np.array_equal(fr[5, 1], (2.0 * pairs[5 * hop:5 * hop + 128, 1] - 255) * X.U)
+
+
+@pytest.mark.parametrize("kind,shape,flavour,mode,bf", RAW_CASES, ids=RAW_IDS)
+def test_preconditions_hold_on_the_raw_byte_frames(kind, shape, flavour, mode, bf):
+    """The fixtures' weights, scales and fp8_input_absmax = U serve the raw-byte frames unchanged, at every hop (prints the
+    bounds: pytest -s).  A failure is an error of the fixture, as above."""
+    fx = _fx(kind, shape, flavour)
+    for hop in RAW_HOPS:
+        fr = X.raw_oracle_frames(kind, hop, RAW_SEED)
+        assert float(np.abs(fr).max()) <= fx.fp8_input_absmax                     # the range the fp8 mode was told to represent
+        bounds = X.check_preconditions(fx, mode, bf, verbose=True, frames=fr)
+        assert all(v < X.EXACT_F32 for k, v in bounds.items() if "sum|term|" in k)
+        if kind == "vtcnn2":
+            assert bounds["distinct labels"] >= 4 and bounds["frames whose maximum is the tied pair"] >= 1
+
+
+def _raw_faults(kind, hop):
+    """(name, frames) of the three faults on the first 16 windows of a capture (the oracle's cost is per window; a fault that
+    moves every window shows on 16), cut from a stream a few windows longer so that every faulty window exists."""
+    n = 16
+    stream = X.raw_capture(kind, 128, RAW_SEED, idx=np.arange(n + 1) % 64) if hop == 128 else X.raw_capture(kind, hop, RAW_SEED, windows=n + 128 // hop + 1)
+    good = X.raw_windows(stream, hop)[:n]
+    yield "good", good
+    yield "stream shifted by one pair", X.raw_windows(stream[2:], hop)[:n]
+    yield "I and Q exchanged", X.raw_windows(stream, hop, swap_iq=True)[:n]
+    yield "window i from pair i hop + 1", X.raw_windows(stream, hop, first_pair=1)[:n]
+
+
+@pytest.mark.parametrize("hop", RAW_HOPS)
+@pytest.mark.parametrize("kind,shape,flavour,mode,bf", [c for c in RAW_CASES if c[1] in (11, 3, 10)], ids=[i for i, c in zip(RAW_IDS, RAW_CASES) if c[1] in (11, 3, 10)])
+def test_sensitivity_of_the_raw_byte_expectation(kind, shape, flavour, mode, bf, hop):
+    """A capture read one pair late, with I and Q exchanged, or with each window taken from pair i hop + 1 changes the expected
+    `dense` array, and with it an array the GPU tests assert (the deployed nets' reduced modes: probabilities and labels only)."""
+    fx = _fx(kind, shape, flavour)
+    runs = {name: X.expected(fx, mode, bf, frames=fr)[0] for name, fr in _raw_faults(kind, hop)}
+    good = runs.pop("good")
+    for name, bad in runs.items():
+        assert not np.array_equal(good["dense"], bad["dense"]), name
+        assert (good["dense"] != bad["dense"]).any(axis=1).mean() > 0.5, name          # not one lucky window: most of them
+        assert _detected(kind, mode, good, bad), name
