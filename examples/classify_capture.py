@@ -43,7 +43,10 @@ line per dwell), two emitters that use the same bins at different times (two lin
     python examples/classify_capture.py capture.bin --format ci16 --detections --threshold 6
 
 Add --batched for a busy band: all boxes are then extracted in one launch and classified in one forward (the same lines, bit for
-bit; frontend.extract, detect_iq(batched=True)) instead of a few launches and one synchronisation per box.
+bit; frontend.extract, detect_iq(batched=True)) instead of a few launches and one synchronisation per box.  Add --refine to
+take each box's symbol rate and carrier from its spectral lines instead of its width and centroid (detect_iq(refine=True);
+with --batched all boxes' line spectra come from one frontend.line_spectra and one frontend.find_lines); two more columns, as
+with --scan --refine.
 
 A band with a channel raster -- PMR / LMR, GSM, FM broadcast, ISM sub-bands -- is split into all its M evenly spaced channels in
 one pass instead (frontend.channelize, a polyphase filter bank on the device; VTCNN2.predict_channels), one line per channel:
@@ -168,19 +171,27 @@ def synthetic_hopper(fmt="ci16", seed=1, pairs=1 << 19):
     return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * full), lo, hi).astype(DTYPES[fmt]).reshape(-1)
 
 
-def detections(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0, batched=False):
+def detections(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0, batched=False, refine=False):
     """Print one line per detection of the capture (VTCNN2.detect_iq: boxes in time and frequency) and return the records: the
     box's span in input pairs, centre and width (Hz with rate, else cycles per sample), the peak over the threshold, the plan and
-    the label.  batched: all boxes in one extraction launch and one forward (needs hop == 128); the same records."""
+    the label.  batched: all boxes in one extraction launch and one forward (needs hop == 128); the same records.  refine: symbol
+    rate and carrier from each box's spectral lines (detect_iq's refine=True), as two more columns -- the symbol rate ("-" where no
+    line was found) and the refined centre."""
+    more = dict(refine=True) if refine else {}
     found = model.detect_iq(iq[:iq.size // 2 * 2], fmt, nfft=nfft, threshold_db=threshold_db, hop=hop, level=level, squelch_dbfs=squelch,
-                            batched=batched)
+                            batched=batched, **more)
     k, unit = (rate, "Hz") if rate else (1.0, "cyc/sample")
     print(f"{len(found)} detections ({unit})")
-    print(f"{'first pair':>12s} {'stop pair':>12s} {'centre':>12s} {'bandwidth':>12s} {'peak dB':>8s} {'L/D':>7s} {'windows':>8s} {'open':>6s} {'label':>6s}")
+    print(f"{'first pair':>12s} {'stop pair':>12s} {'centre':>12s} {'bandwidth':>12s} {'peak dB':>8s} {'L/D':>7s} {'windows':>8s} {'open':>6s} {'label':>6s}"
+          + (f" {'symbol rate':>12s} {'refined':>12s}" if refine else ""))
     for d in found:
         labels = np.asarray(d["labels"])
+        more = ""
+        if refine:
+            symbol = "-" if d["symbol_rate"] is None else f"{d['symbol_rate'] * k:.6g}"
+            more = f" {symbol:>12s} {(d['centre'] + d['carrier_offset']) * k:12.8g}"
         print(f"{d['first_pair']:12d} {d['stop_pair']:12d} {d['centre'] * k:12.6g} {d['bandwidth'] * k:12.6g} {d['snr_db']:8.1f} "
-              f"{str(d['interpolate']) + '/' + str(d['decimate']):>7s} {d['windows']:8d} {int((labels >= 0).sum()):6d} {d['label']:6d}")
+              f"{str(d['interpolate']) + '/' + str(d['decimate']):>7s} {d['windows']:8d} {int((labels >= 0).sum()):6d} {d['label']:6d}{more}")
     return found
 
 
@@ -273,7 +284,7 @@ def main():
     ap.add_argument("--nfft", type=int, default=1024, help="with --scan: bins of the spectrum (a power of two in 64..4096)")
     ap.add_argument("--threshold", type=float, default=6.0, help="with --scan: dB above the noise floor at which a bin belongs to an emitter")
     ap.add_argument("--refine", action="store_true",
-                    help="with --scan: symbol rate and carrier of each emitter from its spectral lines; two more columns")
+                    help="with --scan or --detections: symbol rate and carrier of each emitter from its spectral lines; two more columns")
     ap.add_argument("--bursts", action="store_true",
                     help="with --scan: find intermittent emitters too and classify only inside their bursts; two more columns")
     ap.add_argument("--hold", type=float, default=0.98, help="with --bursts: the quantile over time of each bin that the emitters are searched in")
@@ -292,7 +303,7 @@ def main():
         else:
             model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
         detections(model, iq, a.format, nfft=a.nfft, threshold_db=a.threshold, rate=a.rate if a.rate != 1.0 else None, hop=a.hop, level=a.level,
-                   squelch=a.squelch, batched=a.batched)
+                   squelch=a.squelch, batched=a.batched, refine=a.refine)
         return
     if a.channels:
         iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_raster(a.format, a.channels)

@@ -62,7 +62,10 @@ extern "C" {
                                   mdc_iq_spectrogram_components / mdc_iq_spectrogram_components_workspace, mdc_iq_component
                                   (connected components of a thresholded spectrogram: boxes in time and frequency);
                                   mdc_iq_extract / mdc_iq_extract_plan / mdc_iq_extract_plan_bytes, mdc_iq_extract_job,
-                                  mdc_iq_extract_filter (K stretches of a capture through mdc_iq_resample's chain in one launch) */
+                                  mdc_iq_extract_filter (K stretches of a capture through mdc_iq_resample's chain in one launch);
+                                  mdc_iq_line_spectra / mdc_iq_line_spectra_rows, mdc_iq_line_job (the line spectra of K stretches
+                                  at several orders, and their float64 means, in one call); mdc_iq_find_lines, mdc_iq_line_band,
+                                  mdc_iq_line_record (the line search of S spectra on the device) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -530,6 +533,73 @@ MDC_API int mdc_iq_spectrogram(const void* iq_dev, int format, int64_t pairs_in,
 #define MDC_IQ_LINE_ENVELOPE 0
 MDC_API int mdc_iq_line_spectrum(const void* iq_dev, int format, int64_t pairs_in, int order, int nfft, int64_t hop, int avg,
                                  const int16_t* window_dev, float scale, float* power_dev, int64_t rows, void* hip_stream);
+
+/* ---- batched line spectra: the line spectra of K stretches, and their means, in one call (additive in ABI 5) ----------------
+ * A search returns hundreds of boxes, and each box's symbol rate and carrier offset are read from the lines of its own isolated
+ * stream (mdc_iq_extract puts all of those streams into one MDC_IQ_CI16 block).  One mdc_iq_line_spectrum per (box, order) is
+ * three launches per box; mdc_iq_line_spectra does all boxes and all orders in one call.  A JOB is a stretch
+ * [first_pair, first_pair + pairs) of the capture at iq_dev; jobs may overlap, be empty, and start on any pair.
+ *   rows fn    mdc_iq_line_spectra_rows (host code, no device) checks 0 <= first_pair, 0 <= pairs, first_pair + pairs <= pairs_in
+ *              for every job and FILLS each job's rows = mdc_iq_spectrogram_rows(pairs, nfft, hop, avg) and first_row, the sum of
+ *              the rows of the jobs before it; it returns the total number of rows, or a negative MDC_EINVAL whose message names
+ *              the job.
+ *   rows       rows_dev holds norders planes of total_rows rows of nfft floats: [order index][global row][nfft].  For job j and
+ *              orders_host[i] = o, rows first_row .. first_row + rows - 1 of plane i equal, bit for bit, what
+ *              mdc_iq_line_spectrum(iq_dev + first_pair pairs, format, pairs, o, nfft, hop, avg, window_dev, scale, ...) writes
+ *              (the same kernel computes them).  No pair outside the job is read.
+ *   means      mean_dev holds njobs * norders * nfft doubles, [job][order index][nfft]: mean_dev[j][i][k] is
+ *              acc = 0.0; for r = first_row .. first_row + rows - 1 in that order: acc += (double)row[r][k]; acc / (double)rows
+ *              in IEEE float64 -- the bits of that loop.  A job with rows == 0 gets 0.0 in all its bins.
+ *   orders     orders_host: 1 <= norders <= 4 DISTINCT values of 0 (MDC_IQ_LINE_ENVELOPE), 1, 2, 4, in any order; a HOST array
+ *              that travels with the launch.
+ *   launches   norders + 1 per call, at most five, however many jobs there are -- mdc_iq_line_spectrum's own kernel once per order
+ *              over all jobs' rows, then the means -- on hip_stream; the row launches are skipped when total_rows == 0, all
+ *              when njobs == 0.  Work-groups look their row's job up in the table; the grid is capped and strides.  No work-group waits for another, nothing is atomic: the same inputs give the same bits on every run,
+ *              and a job's rows and means depend on neither the other jobs nor their order.
+ * The caller passes the job table twice, as mdc_iq_extract takes its plan: launch sizes and every check come from jobs_host
+ * (whose first_row / rows must be what mdc_iq_line_spectra_rows fills, and total_rows what it returns), the kernels read jobs_dev,
+ * the same njobs records on the device, 8-byte aligned; jobs_host may be freed on return.  The limits on nfft, hop, avg and scale
+ * and the alignment of iq_dev, window_dev and rows_dev are mdc_iq_line_spectrum's; mean_dev is 8-byte aligned.  Every argument
+ * error is MDC_EINVAL with a message, before any device call.  The call only enqueues (no allocation, no copy, no
+ * synchronisation: capturable in a hipGraph) and runs on the current device.  njobs <= 2^24. */
+typedef struct mdc_iq_line_job {
+    int64_t first_pair, pairs;           /* the stretch [first_pair, first_pair + pairs) of the capture */
+    int64_t first_row, rows;             /* its rows in every plane of rows_dev: filled by mdc_iq_line_spectra_rows */
+} mdc_iq_line_job;
+MDC_API int64_t mdc_iq_line_spectra_rows(mdc_iq_line_job* jobs_host, int64_t njobs, int64_t pairs_in, int nfft, int64_t hop, int avg);
+MDC_API int mdc_iq_line_spectra(const void* iq_dev, int format, int64_t pairs_in, const mdc_iq_line_job* jobs_host,
+                                const mdc_iq_line_job* jobs_dev, int64_t njobs, const int* orders_host, int norders, int nfft, int64_t hop,
+                                int avg, const int16_t* window_dev, float scale, float* rows_dev, int64_t total_rows, double* mean_dev,
+                                void* hip_stream);
+
+/* ---- line search: the strongest line of S power spectra within a band each, on the device (additive in ABI 5) ----------------
+ * What a host does with a line spectrum -- an argmax inside a band, the band's median, the peak's two neighbours -- needs the
+ * whole spectrum on the host: nfft doubles per spectrum.  mdc_iq_find_lines does the search where the spectra are and leaves
+ * one record of 48 bytes per spectrum.  Normatively, for spectrum s, the nfft doubles at spectra_dev + s * nfft in natural DFT
+ * order (what mdc_iq_line_spectra writes to mean_dev), and its band (lo, hi, two_sided):
+ *   searched   the bins k with lo <= g <= hi, g = f or, when two_sided != 0, |f|;  f = k / nfft for k < nfft / 2, else
+ *              (k - nfft) / nfft, formed and compared in float64.
+ *   count      the number of searched bins.
+ *   bin        the searched bin that holds the largest value; among equal values the smallest k.
+ *   peak       that value; left and right are the values of bins k - 1 and k + 1 modulo nfft, searched or not.
+ *   medians    median_lo and median_hi are the order statistics (count - 1) / 2 and count / 2 (0-based, integer division) of the
+ *              searched values sorted ascending: equal for an odd count; their mean is the median.
+ * All five doubles are elements of the spectrum, bit for bit.  A spectrum that holds, in any bin, a NaN, an infinity or a value
+ * below zero gets count = -1 and the other fields are unspecified (-0.0 counts as zero).  A band without a bin is MDC_EINVAL, found on the
+ * host from bands_host before any device call, with a message that names the spectrum; reserved must be 0.  bands_host is
+ * read for the checks, the kernel reads bands_dev (the same records on the device); all three device buffers are 8-byte
+ * aligned.  nfft: a power of two in 64..4096.  nspectra == 0 is MDC_OK without a launch.  One launch, one work-group per
+ * spectrum (the grid is capped and strides); the call only enqueues and is capturable in a hipGraph. */
+typedef struct mdc_iq_line_band {
+    double lo, hi;                       /* cycles per sample */
+    int32_t two_sided, reserved;         /* != 0: the band is on |f|; 0 */
+} mdc_iq_line_band;
+typedef struct mdc_iq_line_record {
+    int32_t bin, count;
+    double peak, left, right, median_lo, median_hi;
+} mdc_iq_line_record;
+MDC_API int mdc_iq_find_lines(const double* spectra_dev, int64_t nspectra, int nfft, const mdc_iq_line_band* bands_host,
+                              const mdc_iq_line_band* bands_dev, mdc_iq_line_record* records_dev, void* hip_stream);
 
 /* ---- spectrum quantiles: per-bin order statistics of a spectrogram along time (additive in ABI 5) ---------------------------
  * The mean over a spectrogram's rows dilutes an emitter that is on for 3 % of the capture by 15 dB.  A high quantile over time

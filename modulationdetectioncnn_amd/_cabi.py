@@ -41,6 +41,7 @@ EXPORTS = [
     "mdc_iq_channelizer", "mdc_iq_channelizer_out_count",
     "mdc_iq_spectrum_quantiles",
     "mdc_iq_spectrogram_components", "mdc_iq_spectrogram_components_workspace",
+    "mdc_iq_line_spectra", "mdc_iq_line_spectra_rows", "mdc_iq_find_lines",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
@@ -75,6 +76,14 @@ SPECTROGRAM_GRID_CAP = 2048
 # mdc_iq_line_spectrum: the same kernel and limits; `order` is 0 (MDC_IQ_LINE_ENVELOPE: I^2 + Q^2), 1 (the spectrogram), 2 or 4
 IQ_LINE_ENVELOPE = 0
 LINE_SPECTRUM_ORDERS = (0, 1, 2, 4)
+# mdc_iq_line_spectra: the job record of include/mdc.h (mdc_iq_line_job, 32 B), up to LINE_SPECTRA_MAX_ORDERS distinct orders per
+# call; the row kernel is the spectrogram's (one work-group per (order, row), SPECTROGRAM_GRID_CAP of them at most)
+IQ_LINE_JOB = np.dtype([("first_pair", np.int64), ("pairs", np.int64), ("first_row", np.int64), ("rows", np.int64)])
+LINE_SPECTRA_MAX_ORDERS = 4
+# mdc_iq_find_lines: the band and the record of include/mdc.h (mdc_iq_line_band, 24 B; mdc_iq_line_record, 48 B)
+IQ_LINE_BAND = np.dtype([("lo", np.float64), ("hi", np.float64), ("two_sided", np.int32), ("reserved", np.int32)])
+IQ_LINE_RECORD = np.dtype([("bin", np.int32), ("count", np.int32), ("peak", np.float64), ("left", np.float64), ("right", np.float64),
+                           ("median_lo", np.float64), ("median_hi", np.float64)])
 # mdc_iq_spectrum_quantiles: limits of include/mdc.h, and the kernel's tile (csrc/iq_quantiles.hip: kQuantTile): one work-group
 # per QUANTILES_TILE adjacent columns
 QUANTILES_MAX_RANKS, QUANTILES_MAX_ROWS = 8, 2 ** 31 - 1
@@ -183,7 +192,9 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_iq_line_spectrum", [vp, i32, i64, i32, i32, i64, i32, vp, C.c_float, vp, i64, vp]),
                        ("mdc_iq_channelizer", [vp, i32, i64, i64, i32, i32, vp, i32, i32, vp, i64, vp]),
                        ("mdc_iq_spectrum_quantiles", [vp, i64, i32, vp, i32, vp, vp]),
-                       ("mdc_iq_spectrogram_components", [vp, i64, i32, vp, i32, i32, vp, vp, i64, vp, vp, vp])):
+                       ("mdc_iq_spectrogram_components", [vp, i64, i32, vp, i32, i32, vp, vp, i64, vp, vp, vp]),
+                       ("mdc_iq_line_spectra", [vp, i32, i64, vp, vp, i64, vp, i32, i32, i64, i32, vp, C.c_float, vp, i64, vp, vp]),
+                       ("mdc_iq_find_lines", [vp, i64, i32, vp, vp, vp, vp])):
         fn = getattr(L, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, i32
@@ -195,6 +206,8 @@ def lib(variant: str = "product") -> C.CDLL:
         L.mdc_iq_extract_plan_bytes.argtypes, L.mdc_iq_extract_plan_bytes.restype = [i64, C.c_int32, vp, vp], i64
     if getattr(L, "mdc_iq_spectrogram_rows", None) is not None:
         L.mdc_iq_spectrogram_rows.argtypes, L.mdc_iq_spectrogram_rows.restype = [i64, i32, i64, i32], i64
+    if getattr(L, "mdc_iq_line_spectra_rows", None) is not None:
+        L.mdc_iq_line_spectra_rows.argtypes, L.mdc_iq_line_spectra_rows.restype = [vp, i64, i64, i32, i64, i32], i64
     if getattr(L, "mdc_iq_channelizer_out_count", None) is not None:
         L.mdc_iq_channelizer_out_count.argtypes, L.mdc_iq_channelizer_out_count.restype = [i64, i32, i32, i32], i64
     if getattr(L, "mdc_iq_spectrogram_components_workspace", None) is not None:

@@ -24,6 +24,11 @@
 //             34 KiB of image + 24 KiB of twiddles, two work-groups per CU.
 // mdc_iq_line_spectrum is the same kernel with ORDER != 1: the staging alone differs (spec_stage; include/mdc.h, "line spectrum";
 // tests/iq_line_ref.py), everything from the image on is shared -- DESIGN.md 5.19.
+// mdc_iq_line_spectra (iq_line_spectra.hip) is the same kernel again, handed a JOB TABLE: its rows are then the jobs' rows back to
+// back, and a work-group looks its row's job up (a binary search of the table's first_row column, uniform over the work-group)
+// and runs the row on the job's slice -- base pointer iq + first_pair, bound `pairs`, the row counted from the job's first.  The
+// very instructions that serve a call on the slice compute the row, so its bits are that call's by construction, and no pair
+// outside the job is read: every segment of a row the rows function counts lies inside the bound.
 // The call only enqueues; vector memory for every store.
 #include "iq_mix.h"
 
@@ -83,7 +88,8 @@ __device__ __forceinline__ float2 spec_stage(int I, int Q, int w) {
 template <int FMT, int LOG2N, int ORDER>
 __global__ __launch_bounds__(spec_threads(LOG2N)) void iq_spectrogram_kernel(const unsigned char* __restrict__ iq, long pairs, long hop, int avg,
                                                                             const short* __restrict__ window, float gain,
-                                                                            float* __restrict__ power, long rows) {
+                                                                            float* __restrict__ power, long rows,
+                                                                            const mdc_iq_line_job* __restrict__ jobs, long njobs) {
     constexpr int N = 1 << LOG2N, NB = N / 4, T = spec_threads(LOG2N);
     constexpr int B = (NB + T - 1) / T;              // radix-4 butterflies (and staged quads) per thread
     constexpr bool kWhole = NB % T == 0;             // false only for nfft 64 and 128: fewer butterflies than lanes
@@ -100,7 +106,19 @@ __global__ __launch_bounds__(spec_threads(LOG2N)) void iq_spectrogram_kernel(con
         tw[2 * NB + j] = spec_twiddle(3 * J);
     }
 
-    for (long row = blockIdx.x; row < rows; row += gridDim.x) {
+    for (long grow = blockIdx.x; grow < rows; grow += gridDim.x) {
+        const unsigned char* src = iq;      // the capture, or with a job table the row's job: all uniform over the work-group
+        long bound = pairs, row = grow;
+        if (jobs) {
+            long lo = 0, hi = njobs - 1;      // the last job whose first_row is <= grow owns the row (jobs without rows share their
+            while (lo < hi) {                 // first_row with the owner and come before it)
+                const long mid = (lo + hi + 1) >> 1;
+                if (jobs[mid].first_row <= grow) lo = mid; else hi = mid - 1;
+            }
+            src = iq + jobs[lo].first_pair * Quad<FMT>::kPairBytes;
+            bound = jobs[lo].pairs;
+            row = grow - jobs[lo].first_row;
+        }
         float acc[4 * B];
 #pragma unroll
         for (int i = 0; i < 4 * B; ++i) acc[i] = 0.f;
@@ -112,7 +130,7 @@ __global__ __launch_bounds__(spec_threads(LOG2N)) void iq_spectrogram_kernel(con
                 const int q = tid + i * T;
                 if (kWhole || q < NB) {
                     int I[4], Q[4];
-                    load_quad<FMT>(iq, start + 4 * q, pairs, I, Q);
+                    load_quad<FMT>(src, start + 4 * q, bound, I, Q);
                     short w[4];
                     __builtin_memcpy(w, window + 4 * q, sizeof(w));
 #pragma unroll
@@ -172,7 +190,7 @@ __global__ __launch_bounds__(spec_threads(LOG2N)) void iq_spectrogram_kernel(con
                 }
             }
         }
-        float* out = power + row * N;
+        float* out = power + grow * N;
         if (!kOdd) {
 #pragma unroll
             for (int i = 0; i < B; ++i) {
@@ -194,25 +212,26 @@ __global__ __launch_bounds__(spec_threads(LOG2N)) void iq_spectrogram_kernel(con
 }
 
 template <int FMT, int LOG2N, int ORDER>
-int spec_launch(const unsigned char* iq, int64_t pairs, int64_t hop, int avg, const int16_t* window, float gain, float* power, int64_t rows, hipStream_t s) {
+int spec_launch(const unsigned char* iq, int64_t pairs, int64_t hop, int avg, const int16_t* window, float gain, float* power, int64_t rows,
+                const mdc_iq_line_job* jobs, int64_t njobs, hipStream_t s) {
     const dim3 g((unsigned)(rows < kSpecGridCap ? rows : kSpecGridCap)), b(spec_threads(LOG2N));
     hipLaunchKernelGGL((iq_spectrogram_kernel<FMT, LOG2N, ORDER>), g, b, 0, s, iq, (long)pairs, (long)hop, avg, reinterpret_cast<const short*>(window), gain, power,
-                       (long)rows);
+                       (long)rows, jobs, (long)njobs);
     MDC_HIP(hipGetLastError());
     return MDC_OK;
 }
 
 template <int FMT, int ORDER>
 int spec_launch_fmt(int log2n, const unsigned char* iq, int64_t pairs, int64_t hop, int avg, const int16_t* window, float gain, float* power, int64_t rows,
-                    hipStream_t s) {
+                    const mdc_iq_line_job* jobs, int64_t njobs, hipStream_t s) {
     switch (log2n) {
-        case 6: return spec_launch<FMT, 6, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
-        case 7: return spec_launch<FMT, 7, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
-        case 8: return spec_launch<FMT, 8, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
-        case 9: return spec_launch<FMT, 9, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
-        case 10: return spec_launch<FMT, 10, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
-        case 11: return spec_launch<FMT, 11, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
-        default: return spec_launch<FMT, 12, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, s);
+        case 6: return spec_launch<FMT, 6, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+        case 7: return spec_launch<FMT, 7, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+        case 8: return spec_launch<FMT, 8, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+        case 9: return spec_launch<FMT, 9, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+        case 10: return spec_launch<FMT, 10, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+        case 11: return spec_launch<FMT, 11, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+        default: return spec_launch<FMT, 12, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
     }
 }
 
@@ -235,7 +254,29 @@ int64_t spec_rows(int64_t pairs, int nfft, int64_t hop, int avg) {
     return segs / avg;
 }
 
+// format and order as template arguments; jobs == nullptr: the rows of the capture itself
+int spec_dispatch(int format, int order, int log2n, const unsigned char* p, int64_t pairs, int64_t hop, int avg, const int16_t* window, float gain, float* power,
+                  int64_t rows, const mdc_iq_line_job* jobs, int64_t njobs, hipStream_t s) {
+    return with_format(format, [&](auto fmt) {
+        constexpr int F = decltype(fmt)::value;
+        switch (order) {
+            case 0: return spec_launch_fmt<F, 0>(log2n, p, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+            case 1: return spec_launch_fmt<F, 1>(log2n, p, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+            case 2: return spec_launch_fmt<F, 2>(log2n, p, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+            default: return spec_launch_fmt<F, 4>(log2n, p, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+        }
+    });
+}
+
 }  // namespace
+
+// what iq_line_spectra.hip needs of this file (mdc_internal.h)
+int iq_spec_shape_check(const char* who, int64_t pairs, int nfft, int64_t hop, int avg) { return spec_shape_check(who, pairs, nfft, hop, avg); }
+int64_t iq_spec_rows(int64_t pairs, int nfft, int64_t hop, int avg) { return spec_rows(pairs, nfft, hop, avg); }
+int iq_spec_jobs_launch(const void* iq, int format, int order, int nfft, int64_t hop, int avg, const int16_t* window, float gain, float* power, int64_t rows,
+                        const mdc_iq_line_job* jobs_dev, int64_t njobs, hipStream_t s) {
+    return spec_dispatch(format, order, spec_log2(nfft), static_cast<const unsigned char*>(iq), 0, hop, avg, window, gain, power, rows, jobs_dev, njobs, s);
+}
 
 }  // namespace mdc
 
@@ -267,17 +308,7 @@ static int spec_run(const char* who, const void* iq_dev, int format, int64_t pai
     const int log2n = spec_log2(nfft);
     const unsigned char* p = static_cast<const unsigned char*>(iq_dev);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    return guarded(who, [&]() -> int {
-        return with_format(format, [&](auto fmt) {
-            constexpr int F = decltype(fmt)::value;
-            switch (order) {
-                case 0: return spec_launch_fmt<F, 0>(log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, s);
-                case 1: return spec_launch_fmt<F, 1>(log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, s);
-                case 2: return spec_launch_fmt<F, 2>(log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, s);
-                default: return spec_launch_fmt<F, 4>(log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, s);
-            }
-        });
-    });
+    return guarded(who, [&]() -> int { return spec_dispatch(format, order, log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, nullptr, 0, s); });
 }
 
 int mdc_iq_spectrogram(const void* iq_dev, int format, int64_t pairs_in, int nfft, int64_t hop, int avg, const int16_t* window_dev, float scale,

@@ -241,6 +241,12 @@ int iq_pair_aligned(const char* who, const char* what, int format, const void* p
 int iq_format_check(const char* who, int format, int64_t hop);
 // the wave-per-window normaliser's MDC_IQ_CU8 instantiation with the record in 32-bit fields (n > 0; x or stats may be NULL)
 int iq_norm_wave_launch(const uint8_t* iq, int64_t n, int64_t hop, float level, int flags, float* x, mdc_iq_window_stats* stats, hipStream_t s);
+// iq_spectrogram.hip, for iq_line_spectra.hip: the spectrogram's shape check and row count, and iq_spectrogram_kernel at `order`
+// over a job table -- `rows` global rows (the jobs' rows back to back) into power, one plane; format, order and nfft are known good
+int iq_spec_shape_check(const char* who, int64_t pairs, int nfft, int64_t hop, int avg);
+int64_t iq_spec_rows(int64_t pairs, int nfft, int64_t hop, int avg);
+int iq_spec_jobs_launch(const void* iq, int format, int order, int nfft, int64_t hop, int avg, const int16_t* window, float gain, float* power, int64_t rows,
+                        const mdc_iq_line_job* jobs_dev, int64_t njobs, hipStream_t s);
 // fn(std::integral_constant<int, MDC_IQ_*>) for a format that iq_format_known has passed: the runtime format as a template argument
 template <class Fn>
 inline int with_format(int format, Fn&& fn) {

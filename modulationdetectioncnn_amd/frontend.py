@@ -6,6 +6,8 @@ An RTL-SDR delivers unsigned 8-bit interleaved (I, Q) samples; a frame of the cl
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 
 from . import _cabi
@@ -654,23 +656,7 @@ def _spectra(order, iq, sample_format, nfft, hop, avg, window, device, scale):
         raise ValueError("the capture is not a whole number of (I,Q) pairs")
     lib = _cabi.lib()
     rows = _cabi.check(lib.mdc_iq_spectrogram_rows(pairs, N, H, int(avg)))
-    if window is None:
-        w, default_scale = _default_window(N, t.device)
-    else:
-        if isinstance(window, torch.Tensor):
-            if window.dtype != torch.int16:
-                raise TypeError(f"window must be int16, got {window.dtype}")
-            w = window.to(t.device).contiguous().view(-1)
-        else:
-            h = np.asarray(window)
-            if h.dtype.kind not in "iu" or h.ndim != 1:
-                raise TypeError("window must be a one-dimensional integer array (int16)")
-            if h.size and (h.min() < -32768 or h.max() > 32767):
-                raise ValueError("window must fit int16")
-            w = torch.from_numpy(np.ascontiguousarray(h.astype(np.int16))).to(t.device)
-        default_scale = None
-    if w.numel() != N:
-        raise ValueError(f"the window has {w.numel()} values, nfft is {N}")
+    w, default_scale = _window_tensor(window, N, t.device)
     k = float(scale) if scale is not None else default_scale if default_scale is not None else window_scale(window)
     out = torch.empty((rows, N), dtype=torch.float32, device=t.device)
     with torch.cuda.device(t.device):
@@ -726,16 +712,146 @@ def find_line(psd, lo: float, hi: float, two_sided: bool = False):
     if band.size == 0:
         raise ValueError(f"no bin of the {n} lies in the band {lo:g} .. {hi:g} cycles per sample")
     k = int(band[np.argmax(p[band])])
-    peak, floor = float(p[k]), float(np.median(p[band]))
+    return _line_from_search(n, k, float(p[k]), float(p[(k - 1) % n]), float(p[(k + 1) % n]), float(np.median(p[band])))
+
+
+def _line_from_search(n: int, k: int, peak: float, left: float, right: float, floor: float):
+    """find_line and find_lines behind their searches: (frequency, prominence_db) from the strongest searched bin k of n, its
+    value, its circular neighbours' values and the median of the searched bins -- Python floats, float64 arithmetic"""
     prominence = 10.0 * np.log10(peak / floor) if floor > 0.0 and peak > 0.0 else (np.inf if peak > 0.0 else 0.0)
-    left, right = float(p[(k - 1) % n]), float(p[(k + 1) % n])
     delta = 0.0
     if left > 0.0 and peak > 0.0 and right > 0.0:
         a, b, c = np.log(left), np.log(peak), np.log(right)
         den = a - 2.0 * b + c
         if den < 0.0:
             delta = 0.5 * (a - c) / den
-    return float(f[k] + delta / n), float(prominence)
+    return float(np.fft.fftfreq(n)[k] + delta / n), float(prominence)
+
+
+def _window_tensor(window, N: int, device):
+    """(int16 device tensor of N values, its default scale or None): spectrogram's rules for `window`"""
+    import torch
+    if window is None:
+        return _default_window(N, device)
+    if isinstance(window, torch.Tensor):
+        if window.dtype != torch.int16:
+            raise TypeError(f"window must be int16, got {window.dtype}")
+        w = window.to(device).contiguous().view(-1)
+    else:
+        h = np.asarray(window)
+        if h.dtype.kind not in "iu" or h.ndim != 1:
+            raise TypeError("window must be a one-dimensional integer array (int16)")
+        if h.size and (h.min() < -32768 or h.max() > 32767):
+            raise ValueError("window must fit int16")
+        w = torch.from_numpy(np.ascontiguousarray(h.astype(np.int16))).to(device)
+    if w.numel() != N:
+        raise ValueError(f"the window has {w.numel()} values, nfft is {N}")
+    return w, None
+
+
+def line_spectra(iq, sample_format, jobs, orders=(0, 2, 4), nfft: int = 1024, hop=None, avg: int = 8, window=None, device=None, scale=None,
+                 return_rows: bool = False):
+    """The line spectra of K stretches of one capture at several orders, and their means over the rows, in one call
+    (mdc_iq_line_spectra, include/mdc.h: one launch per order and one for the means, whatever K).  iq: as frames_from_iq -- in
+    practice the "ci16" block of extract(..., whole_frames=False).  jobs: a sequence of (first_pair, stop_pair), or a
+    one-dimensional integer array of K + 1 non-decreasing offsets as extract returns them (job k is offsets[k]:offsets[k + 1]);
+    jobs may overlap, be empty and start on any pair.  orders: 1 to 4 distinct values of 0, 1, 2, 4.  nfft, hop, avg, window,
+    scale: as line_spectrum.  Returns (means, rows): the (K, len(orders), nfft) float64 device tensor -- means[k, i] is the
+    float64 mean, row by row from the first, of line_spectrum(iq[first:stop], ..., orders[i], nfft, hop, avg), bit for bit;
+    all zeros for a job too short for a row -- and an int64 numpy array of each job's row count.  With return_rows also the
+    (len(orders), total rows, nfft) float32 device tensor of the rows themselves and the int64 numpy array of K + 1 first rows
+    (job k owns rows first[k]:first[k + 1] of every plane).  Enqueues on torch's current stream; the job table goes to the
+    device as an ordinary torch transfer."""
+    import torch
+    fmt = sample_format_id(sample_format)
+    N = int(nfft)
+    H = N // 2 if hop is None else int(hop)
+    ords = [o for o in orders]
+    if not 1 <= len(ords) <= _cabi.LINE_SPECTRA_MAX_ORDERS or len(set(ords)) != len(ords) or \
+            any(isinstance(o, bool) or o not in _cabi.LINE_SPECTRUM_ORDERS for o in ords):
+        raise ValueError(f"orders must be 1..{_cabi.LINE_SPECTRA_MAX_ORDERS} distinct values of {_cabi.LINE_SPECTRUM_ORDERS} (got {orders!r})")
+    t = _device_samples(iq, fmt, device)
+    pairs = t.numel() * t.element_size() // _cabi.IQ_PAIR_BYTES[fmt]
+    if pairs * _cabi.IQ_PAIR_BYTES[fmt] != t.numel() * t.element_size():
+        raise ValueError("the capture is not a whole number of (I,Q) pairs")
+    if isinstance(jobs, np.ndarray) and jobs.ndim == 1:
+        if jobs.size < 1 or jobs.dtype.kind not in "iu":
+            raise ValueError("offsets must be a one-dimensional integer array of at least one value")
+        off = jobs.astype(np.int64)
+        spans = list(zip(off[:-1].tolist(), off[1:].tolist()))
+    else:
+        spans = [(int(a), int(z)) for a, z in jobs]
+    rec = np.zeros(len(spans), _cabi.IQ_LINE_JOB)
+    for k, (a, z) in enumerate(spans):
+        if not 0 <= a <= z <= pairs:
+            raise ValueError(f"job {k}: [{a}, {z}) does not lie inside the capture's {pairs} pairs")
+        rec[k] = (a, z - a, 0, 0)
+    lib = _cabi.lib()
+    total = _cabi.check(lib.mdc_iq_line_spectra_rows(rec.ctypes.data, rec.size, pairs, N, H, int(avg)))
+    w, default_scale = _window_tensor(window, N, t.device)
+    k = float(scale) if scale is not None else default_scale if default_scale is not None else window_scale(window)
+    K, no = rec.size, len(ords)
+    rows = torch.empty((no, total, N), dtype=torch.float32, device=t.device)
+    means = torch.empty((K, no, N), dtype=torch.float64, device=t.device)
+    if K:
+        jobs_dev = torch.from_numpy(rec.view(np.int64).reshape(K, 4)).to(t.device)
+        o = (C.c_int * no)(*[int(v) for v in ords])
+        with torch.cuda.device(t.device):
+            _cabi.check(lib.mdc_iq_line_spectra(t.data_ptr() if pairs else None, fmt, pairs, rec.ctypes.data, jobs_dev.data_ptr(), K, o, no, N, H, int(avg),
+                                                w.data_ptr(), k, rows.data_ptr() if total else None, total, means.data_ptr(),
+                                                torch.cuda.current_stream(t.device).cuda_stream))
+    counts = rec["rows"].astype(np.int64)
+    if return_rows:
+        return means, counts, rows, np.concatenate([rec["first_row"].astype(np.int64), np.array([total], np.int64)])
+    return means, counts
+
+
+def line_records(spectra, bands):
+    """mdc_iq_find_lines on S spectra (include/mdc.h, "line search"): spectra, an (S, nfft) float64 tensor (a host tensor or
+    array is moved to the device); bands, S tuples (lo, hi, two_sided).  Returns the S records as a numpy array of
+    _cabi.IQ_LINE_RECORD -- one transfer of 48 bytes per spectrum, which synchronises.  A band without a bin is a ValueError that
+    names the spectrum, before anything is launched."""
+    import torch
+    t = spectra if isinstance(spectra, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(spectra, dtype=np.float64)))
+    if t.dtype != torch.float64 or t.dim() != 2:
+        raise TypeError(f"spectra must be a two-dimensional float64 tensor, got {t.dtype} with {t.dim()} dimensions")
+    if not t.is_cuda:
+        t = t.to("cuda:0")
+    t = t.contiguous()
+    S, N = int(t.shape[0]), int(t.shape[1])
+    rec = np.zeros(S, _cabi.IQ_LINE_BAND)
+    bands = list(bands)
+    if len(bands) != S:
+        raise ValueError(f"{S} spectra, {len(bands)} bands")
+    for i, (lo, hi, two) in enumerate(bands):
+        rec[i] = (float(lo), float(hi), 1 if two else 0, 0)
+    out = torch.zeros((S, _cabi.IQ_LINE_RECORD.itemsize), dtype=torch.uint8, device=t.device)
+    if S:
+        bands_dev = torch.from_numpy(rec.view(np.uint8).reshape(S, -1)).to(t.device)
+        with torch.cuda.device(t.device):
+            rc = _cabi.lib().mdc_iq_find_lines(t.data_ptr(), S, N, rec.ctypes.data, bands_dev.data_ptr(), out.data_ptr(),
+                                               torch.cuda.current_stream(t.device).cuda_stream)
+        if rc == -22:
+            raise ValueError(_cabi.lib().mdc_last_error().decode("utf-8", "replace"))
+        _cabi.check(rc)
+    return out.cpu().numpy().view(_cabi.IQ_LINE_RECORD).reshape(-1)
+
+
+def find_lines(spectra, bands):
+    """find_line for S spectra at once, searched on the device (mdc_iq_find_lines): spectra, an (S, nfft) float64 tensor, nfft a
+    power of two in 64..4096; bands, S tuples (lo, hi, two_sided).  Returns a list of S (frequency, prominence_db), each equal
+    to find_line(spectra[s], lo, hi, two_sided) to the bit: the device finds the strongest searched bin, its neighbours and the
+    two middle order statistics of the band, the arithmetic after the search is find_line's own.  ValueError if a band holds no
+    bin or a spectrum holds a non-finite or negative value."""
+    rec = line_records(spectra, bands)
+    n = int(spectra.shape[1])
+    out = []
+    for s, r in enumerate(rec):
+        if r["count"] < 0:
+            raise ValueError(f"spectrum {s} holds a non-finite or negative value")
+        floor = float(r["median_lo"]) if r["count"] % 2 else float(np.median(np.array([r["median_lo"], r["median_hi"]], np.float64)))
+        out.append(_line_from_search(n, int(r["bin"]), float(r["peak"]), float(r["left"]), float(r["right"]), floor))
+    return out
 
 
 def _line_psd(iq, sample_format, order: int, nfft: int, avg: int):

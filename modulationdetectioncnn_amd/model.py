@@ -1071,7 +1071,8 @@ class VTCNN2:
 
     def detect_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_db: float = 6.0, floor: str = "flat", reach_rows: int = 2,
                   reach_bins: int = 3, min_rows: int = 3, min_bins: int = 3, hop: int = 128, level: float = 7.8e-3,
-                  squelch_dbfs: Optional[float] = None, dc_guard: int = 1, batched: bool = False):
+                  squelch_dbfs: Optional[float] = None, dc_guard: int = 1, batched: bool = False, refine: bool = False, min_line_db: float = 8.0,
+                  line_nfft: int = 1024, line_avg: int = 8):
         """A wideband capture in, "what transmitted when, where, and what modulation" out: the scan in two dimensions, for
         frequency hoppers, emitters that share bins at different times and single packets, which scan_iq's one-dimensional
         searches miss or mangle.  The capture's spectrogram (frontend.spectrogram, as scan_iq builds it: nfft bins, segments nfft //
@@ -1092,7 +1093,24 @@ class VTCNN2:
         frontend.extract launch tunes, filters and resamples every detection's pairs into one block of whole frames, one
         predict_iq classifies the block, frontend.segment_votes takes every detection's vote on the device, and the labels come to
         the host in one transfer; probs, labels and window_dbfs are then slices of the block's results.  It needs hop == 128 (with
-        another hop windows would straddle detections: ValueError)."""
+        another hop windows would straddle detections: ValueError).
+        refine=True replaces the plan's two guesses per detection -- a symbol rate from the box's width, a carrier from its
+        centroid -- by the detection's spectral lines, scan_iq(refine=True)'s recipe on the detection's own pairs: D0 = clamp(floor(1
+        / (4 bandwidth)), 1, 256); iso = the pairs [first_pair, stop_pair) through frontend.ddc(shift=-centre, decimate=D0,
+        taps=frontend.plan_taps(1, D0)); b = bandwidth D0.  frontend.line_spectra(iso, "ci16", orders (0, 2, 4), nfft=line_nfft,
+        avg=line_avg) gives the three mean spectra, frontend.find_lines searches the envelope's in [b / 2.5, min(0.45, 1.25 b)] and,
+        with m = min(b / 8, 0.12), the square's in |f| <= 2 m and the fourth power's in |f| <= 4 m.  The symbol line counts from
+        min_line_db on (frontend.estimate_symbol_rate's rule); the carrier is order 2's line if it reaches min_line_db, else order
+        4's, else none (frontend.estimate_carrier_offset's rule).  shift = -(centre + offset / D0), folded into [-0.5, 0.5]; (L, D) =
+        frontend.resample_ratio(1.0, rate / D0, 8) when the symbol line was found and a ratio within its 1 % exists, else the plan's.
+        The record gains symbol_rate (cycles per input sample, or None), symbol_line_db, carrier_offset, carrier_order (2, 4, or 0)
+        and carrier_line_db; centre stays the centroid.  A detection too short for one row of line_avg segments of line_nfft
+        isolated pairs, or whose symbol band holds no bin at line_nfft, keeps the plan: symbol_rate None, symbol_line_db -inf,
+        carrier_offset 0.0, carrier_order 0, carrier_line_db -inf.  The loop does ddc, line_spectra (one job) and find_lines (three
+        bands) per detection; batched=True does ONE frontend.extract(..., whole_frames=False) for all isolations, ONE line_spectra
+        over the block, ONE find_lines whose 3 K records come to the host in one transfer, and then the extraction above with the
+        refined shifts and ratios: the same spectra from the same entries, so both forms agree bit for bit.  refine=False is the
+        plan alone, and its record has none of the five keys."""
         torch = _torch()
         from . import frontend as F
         fmt = F.sample_format_id(sample_format)
@@ -1106,14 +1124,27 @@ class VTCNN2:
         thresh = F.detection_threshold(spec, threshold_db, dc_guard, floor)
         if batched:
             found = F.find_detections(spec, thresh, reach_rows, reach_bins, min_rows, min_bins, avg=avg)
-            return self._classify_detections(dev, fmt, found, level, squelch_dbfs, as_numpy)
+            if not refine:
+                return self._classify_detections(dev, fmt, found, level, squelch_dbfs, as_numpy)
+            plans, extras = self._refine_detections(dev, fmt, found, min_line_db, line_nfft, line_avg)
+            return self._classify_detections(dev, fmt, found, level, squelch_dbfs, as_numpy, plans, extras)
         per_pair = _cabi.IQ_PAIR_BYTES[fmt] // dev.element_size()      # elements of `dev` per (I,Q) pair
         Cn = self.topology.classes
         out = []
         for d in F.find_detections(spec, thresh, reach_rows, reach_bins, min_rows, min_bins, avg=avg):
             shift, L, D, _ = F.channel_plan(d.centre, d.bandwidth)
-            taps = F.plan_taps(L, D)
             part = dev[d.first_pair * per_pair:d.stop_pair * per_pair]
+            extra = {}
+            if refine:
+                D0, bands = self._line_bands(d.bandwidth, line_nfft)
+                lines = None
+                if bands is not None:
+                    iso = F.ddc(part, fmt, shift=-d.centre, decimate=D0, taps=F.plan_taps(1, D0))
+                    means, rows = F.line_spectra(iso.reshape(-1), _cabi.IQ_CI16, [(0, iso.shape[0])], orders=(0, 2, 4), nfft=line_nfft, avg=line_avg)
+                    if rows[0] > 0:
+                        lines = F.find_lines(means[0], bands)
+                (shift, L, D), extra = self._refined_plan(d.centre, D0, (shift, L, D), lines, min_line_db)
+            taps = F.plan_taps(L, D)
             if L == 1:
                 n_out = F.ddc_out_count(d.stop_pair - d.first_pair, taps.size, D)
             else:
@@ -1137,17 +1168,87 @@ class VTCNN2:
             if as_numpy:
                 probs, labels, dbfs = probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy()
             out.append(dict(d._asdict(), shift=shift, interpolate=L, decimate=D, probs=probs, labels=labels, window_dbfs=dbfs, windows=windows,
-                            label=label))
+                            label=label, **extra))
         return out
 
-    def _classify_detections(self, dev, fmt, found, level, squelch_dbfs, as_numpy):
-        """detect_iq(batched=True) behind the search: the records of `found` (frontend.find_detections) on the device capture dev"""
+    @staticmethod
+    def _line_bands(bandwidth, line_nfft):
+        """detect_iq(refine=True): (D0, bands) of a detection of that bandwidth -- the isolating decimation and the three bands of
+        frontend.find_lines (envelope, square, fourth power) at its isolated rate; bands is None when the envelope's band holds
+        no bin of line_nfft"""
+        D0 = min(max(int(1.0 / (4.0 * bandwidth)), 1), 256)
+        b = bandwidth * D0
+        lo, hi = b / 2.5, min(0.45, 1.25 * b)
+        f = np.fft.fftfreq(int(line_nfft))
+        if not np.any((f >= lo) & (f <= hi)):
+            return D0, None
+        m = min(b / 8.0, 0.12)
+        return D0, [(lo, hi, False), (0.0, 2.0 * m, True), (0.0, 4.0 * m, True)]
+
+    @staticmethod
+    def _refined_plan(centre, D0, plan, lines, min_line_db):
+        """detect_iq(refine=True): ((shift, L, D), the record's five extra keys) from find_lines' three results at orders 0, 2, 4
+        of the detection isolated at decimation D0 (lines None: no spectrum, the plan stands) -- the decisions of
+        frontend.estimate_symbol_rate and frontend.estimate_carrier_offset, and scan_iq(refine=True)'s use of them"""
+        from . import frontend as F
+        if lines is None:
+            return plan, dict(symbol_rate=None, symbol_line_db=float("-inf"), carrier_offset=0.0, carrier_order=0, carrier_line_db=float("-inf"))
+        shift, L, D = plan
+        (rate, rate_db), (f2, db2), (f4, db4) = lines
+        if rate_db < float(min_line_db):
+            rate = None
+        if db2 >= float(min_line_db):
+            offset, order, offset_db = f2 / 2, 2, db2
+        elif db4 >= float(min_line_db):
+            offset, order, offset_db = f4 / 4, 4, db4
+        else:
+            offset, order, offset_db = 0.0, 0, max(db2, db4)
+        shift = -(centre + offset / D0)
+        if abs(shift) > 0.5:      # a detection at the band's edge: the same frequency, one turn on
+            shift -= round(shift)
+        if rate is not None:
+            try:
+                L, D, _ = F.resample_ratio(1.0, rate / D0, 8)
+            except ValueError:      # nothing within 1 %: the plan's ratio stands
+                pass
+        return (shift, L, D), dict(symbol_rate=None if rate is None else rate / D0, symbol_line_db=rate_db, carrier_offset=offset / D0,
+                                   carrier_order=order, carrier_line_db=offset_db)
+
+    def _refine_detections(self, dev, fmt, found, min_line_db, line_nfft, line_avg):
+        """detect_iq(batched=True, refine=True) before the extraction: (plans, extras) of all detections from one frontend.extract
+        of their isolations, one frontend.line_spectra over that block and one frontend.find_lines"""
+        from . import frontend as F
+        plans = [p[:3] for p in F.channel_plans([(d.centre, d.bandwidth) for d in found])]
+        if not found:
+            return plans, []
+        geo = [self._line_bands(d.bandwidth, line_nfft) for d in found]
+        taps = {}
+        for D0, _ in geo:
+            if D0 not in taps:
+                taps[D0] = F.plan_taps(1, D0)
+        block, offsets = F.extract(dev, fmt, [(d.first_pair, d.stop_pair, -d.centre, 1, D0, taps[D0]) for d, (D0, _) in zip(found, geo)],
+                                   whole_frames=False)
+        means, rows = F.line_spectra(block.reshape(-1), _cabi.IQ_CI16, offsets, orders=(0, 2, 4), nfft=line_nfft, avg=line_avg)
+        live = [k for k, (_, bands) in enumerate(geo) if bands is not None and rows[k] > 0]
+        lines = {}
+        if live:
+            at = _torch().as_tensor(live, dtype=_torch().int64, device=means.device)
+            got = F.find_lines(means[at].reshape(-1, means.shape[2]), [band for k in live for band in geo[k][1]])
+            lines = {k: got[3 * i:3 * i + 3] for i, k in enumerate(live)}
+        out = [self._refined_plan(d.centre, D0, plan, lines.get(k), min_line_db) for k, (d, (D0, _), plan) in enumerate(zip(found, geo, plans))]
+        return [p for p, _ in out], [e for _, e in out]
+
+    def _classify_detections(self, dev, fmt, found, level, squelch_dbfs, as_numpy, plans=None, extras=None):
+        """detect_iq(batched=True) behind the search: the records of `found` (frontend.find_detections) on the device capture dev;
+        plans: (shift, L, D) per detection, None = frontend.channel_plans'; extras: per detection, further keys of its record"""
         torch = _torch()
         from . import frontend as F
         if not found:
             return []
         Cn = self.topology.classes
-        taps, plans = {}, [p[:3] for p in F.channel_plans([(d.centre, d.bandwidth) for d in found])]
+        if plans is None:
+            plans = [p[:3] for p in F.channel_plans([(d.centre, d.bandwidth) for d in found])]
+        taps = {}
         for _, L, D in plans:
             if (L, D) not in taps:
                 taps[L, D] = F.plan_taps(L, D)
@@ -1168,7 +1269,7 @@ class VTCNN2:
         for k, (d, (shift, L, D)) in enumerate(zip(found, plans)):
             a, z = first[k], first[k + 1]
             out.append(dict(d._asdict(), shift=shift, interpolate=L, decimate=D, probs=probs[a:z], labels=labels[a:z], window_dbfs=dbfs[a:z],
-                            windows=z - a, label=label[k]))
+                            windows=z - a, label=label[k], **(extras[k] if extras else {})))
         return out
 
     def predict_channels(self, iq, sample_format, channels: int, decimate: Optional[int] = None, taps=None, tap_shift: Optional[int] = None,
