@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -57,6 +57,22 @@ IQ_PAIR_BYTES = {IQ_CU8: 2, IQ_CI8: 2, IQ_CI16: 4}
 IQ_SAMPLE_DTYPE = {IQ_CU8: np.dtype(np.uint8), IQ_CI8: np.dtype(np.int8), IQ_CI16: np.dtype("<i2")}
 # mdc_iq_window_stats64 (32 B): the same four exact integers for any format (s: include/mdc.h)
 IQ_WINDOW_STATS64 = np.dtype([("sum_i", np.int64), ("sum_q", np.int64), ("sum_sq", np.uint64), ("energy", np.uint64)])
+
+
+class IqWindowEntries(NamedTuple):
+    """What differs between the two families of window entries: the names, whether they take an MDC_IQ_* format, and the record"""
+    frames: str
+    frames_norm: str
+    host: str
+    host_norm: str
+    takes_format: bool
+    stats: np.dtype
+
+
+# unsigned bytes through their own kernels and the 16-byte record; any format (unsigned bytes too) through the 32-byte record's
+IQ_U8_ENTRIES = IqWindowEntries("mdc_iq_u8_windows", "mdc_iq_u8_windows_norm", "mdc_predict_host_iq_u8", "mdc_predict_host_iq_u8_norm", False,
+                                IQ_WINDOW_STATS)
+IQ_ENTRIES = IqWindowEntries("mdc_iq_windows", "mdc_iq_windows_norm", "mdc_predict_host_iq", "mdc_predict_host_iq_norm", True, IQ_WINDOW_STATS64)
 # mdc_iq_ddc: limits of include/mdc.h, and the kernel's tiling (csrc/iq_ddc.hip: kDdcTilePairs, kDdcGridCap) for tests and tools
 DDC_MAX_DECIMATE, DDC_MAX_TAPS, DDC_MAX_TAPS_ABS_SUM, DDC_NCO_ENTRIES = 256, 1024, 65535, 4096
 DDC_TILE_PAIRS, DDC_GRID_CAP = 8192, 1024

@@ -437,47 +437,14 @@ int predict_host_iq_u8(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t 
         });
 }
 
-// mdc_predict_host_iq_u8 with mdc_iq_u8_windows_norm into the slot's frame buffer + mdc_forward in the compute step, and one
-// more result copy (the statistics).  Through frames, so cnn.py's literal model is served too.
-int predict_host_iq_u8_norm(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t hop, float level, int flags, float* probs_host,
-                            int32_t* labels_host, mdc_iq_window_stats* stats_host, int64_t chunk_frames) {
-    int rc = iq_norm_check("mdc_predict_host_iq_u8_norm", hop, level, flags);
-    if (rc != MDC_OK) return rc;
-    if ((rc = check_common("mdc_predict_host_iq_u8_norm", m, iq_host, n, chunk_frames)) != MDC_OK) return rc;
-    if (n == 0) return MDC_OK;
-    std::lock_guard<std::mutex> g(m->host_mu);
-    DeviceScope dev(m->device);
-    if (!dev.ok) { set_error("mdc_predict_host_iq_u8_norm: cannot select device %d", m->device); return MDC_EIO; }
-    int64_t chunk = std::min<int64_t>(chunk_frames > 0 ? chunk_frames : default_chunk(n), n);
-    if (chunk_frames <= 0) {      // default: a slot's frames are within 64 MiB already (default_chunk); so are its bytes, however large the hop
-        const int64_t fit = ((kDefaultChunkFrames * kFrameFloats * 4) - 256) / (2 * hop) + 1;
-        chunk = std::max<int64_t>(1, std::min(chunk, fit));
-    }
-    const size_t in_bytes = (size_t)(2 * hop) * (size_t)(chunk - 1) + 256;
-    if ((rc = ctx_prepare(m, in_bytes, chunk)) != MDC_OK) return rc;
-    if ((rc = ctx_prepare_norm(m, chunk)) != MDC_OK) return rc;
-    return run_pipeline(
-        m, reinterpret_cast<const char*>(iq_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr, stats_host, sizeof(mdc_iq_window_stats),
-        [hop](int64_t start, int64_t count, size_t* off, size_t* bytes) {
-            *off = (size_t)(2 * hop) * (size_t)start;
-            *bytes = (size_t)(2 * hop) * (size_t)(count - 1) + 256;
-        },
-        [m, hop, level, flags, stats_host](Slot& s, int64_t count, HostCtx* c) {
-            int r = mdc_iq_u8_windows_norm(reinterpret_cast<const uint8_t*>(s.d_in), count, hop, level, flags, s.d_x,
-                                           stats_host ? reinterpret_cast<mdc_iq_window_stats*>(s.d_stats) : nullptr,
-                                           c->comp_s);
-            if (r != MDC_OK) return r;
-            return mdc_forward(m, s.d_x, count, s.d_probs, s.d_labels, nullptr, MDC_TAP_NONE, c->ws, c->ws_bytes, c->comp_s);
-        });
-}
-
-// mdc_predict_host_iq / mdc_predict_host_iq_norm: the two drivers above for any MDC_IQ_* format, the slots sized in bytes per
-// pair.  Both go through frames (mdc_iq_windows / mdc_iq_windows_norm into the slot's frame buffer, then mdc_forward): every
-// kind is served.  norm = false: `gain` is the scale, flags and stats_host are unused.
+// The drivers through frames, for any MDC_IQ_* format, the slots sized in bytes per pair: mdc_iq_windows or a normaliser into the
+// slot's frame buffer + mdc_forward in the compute step (so cnn.py's literal model is served too), and with statistics one more
+// result copy.  norm = false: `gain` is the scale, flags and stats_host are unused.  stats_bytes is the record asked for: 16
+// (mdc_iq_window_stats, unsigned bytes only) goes through mdc_iq_u8_windows_norm, 32 (mdc_iq_window_stats64) through mdc_iq_windows_norm.
 namespace {
 
 int predict_host_iq_frames(const char* who, bool norm, mdc_model* m, const void* iq_host, int format, int64_t n, int64_t hop, float gain, int flags,
-                           float* probs_host, int32_t* labels_host, mdc_iq_window_stats64* stats_host, int64_t chunk_frames) {
+                           float* probs_host, int32_t* labels_host, void* stats_host, size_t stats_bytes, int64_t chunk_frames) {
     int rc = iq_format_check(who, format, hop);
     if (rc != MDC_OK) return rc;
     if (norm && (rc = iq_norm_check(who, hop, gain, flags)) != MDC_OK) return rc;
@@ -496,16 +463,18 @@ int predict_host_iq_frames(const char* who, bool norm, mdc_model* m, const void*
     if ((rc = ctx_prepare(m, in_bytes, chunk)) != MDC_OK) return rc;
     if ((rc = ctx_prepare_norm(m, chunk)) != MDC_OK) return rc;
     return run_pipeline(
-        m, static_cast<const char*>(iq_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr, stats_host,
-        sizeof(mdc_iq_window_stats64),
+        m, static_cast<const char*>(iq_host), n, chunk, chunk_frames <= 0 && n >= 4 * chunk, probs_host, labels_host, nullptr, stats_host, stats_bytes,
         [hop, pair](int64_t start, int64_t count, size_t* off, size_t* bytes) {
             *off = pair * (size_t)hop * (size_t)start;
             *bytes = pair * (size_t)hop * (size_t)(count - 1) + 128 * pair;
         },
-        [m, norm, format, hop, gain, flags, stats_host](Slot& s, int64_t count, HostCtx* c) {
-            int r = norm ? mdc_iq_windows_norm(s.d_in, format, count, hop, gain, flags, s.d_x,
-                                               stats_host ? reinterpret_cast<mdc_iq_window_stats64*>(s.d_stats) : nullptr, c->comp_s)
-                         : mdc_iq_windows(s.d_in, format, count, hop, gain, s.d_x, c->comp_s);
+        [m, norm, format, hop, gain, flags, stats_host, stats_bytes](Slot& s, int64_t count, HostCtx* c) {
+            char* stats = stats_host ? s.d_stats : nullptr;
+            int r = !norm ? mdc_iq_windows(s.d_in, format, count, hop, gain, s.d_x, c->comp_s)
+                    : stats_bytes == sizeof(mdc_iq_window_stats)
+                        ? mdc_iq_u8_windows_norm(reinterpret_cast<const uint8_t*>(s.d_in), count, hop, gain, flags, s.d_x,
+                                                 reinterpret_cast<mdc_iq_window_stats*>(stats), c->comp_s)
+                        : mdc_iq_windows_norm(s.d_in, format, count, hop, gain, flags, s.d_x, reinterpret_cast<mdc_iq_window_stats64*>(stats), c->comp_s);
             if (r != MDC_OK) return r;
             return mdc_forward(m, s.d_x, count, s.d_probs, s.d_labels, nullptr, MDC_TAP_NONE, c->ws, c->ws_bytes, c->comp_s);
         });
@@ -513,19 +482,25 @@ int predict_host_iq_frames(const char* who, bool norm, mdc_model* m, const void*
 
 }  // namespace
 
+int predict_host_iq_u8_norm(mdc_model* m, const uint8_t* iq_host, int64_t n, int64_t hop, float level, int flags, float* probs_host,
+                            int32_t* labels_host, mdc_iq_window_stats* stats_host, int64_t chunk_frames) {
+    return predict_host_iq_frames("mdc_predict_host_iq_u8_norm", true, m, iq_host, MDC_IQ_CU8, n, hop, level, flags, probs_host, labels_host, stats_host,
+                                  sizeof(mdc_iq_window_stats), chunk_frames);
+}
+
 int predict_host_iq(mdc_model* m, const void* iq_host, int format, int64_t n, int64_t hop, float scale, float* probs_host, int32_t* labels_host,
                     int64_t chunk_frames) {
     // unsigned bytes where the forward kernels read them themselves: the same results (mdc_forward_iq_u8 is bit-identical to
     // mdc_iq_u8_windows + mdc_forward) without the frame buffer
     if (format == MDC_IQ_CU8 && m && m->topo.kind != MDC_KIND_CNNPY)
         return predict_host_iq_u8(m, static_cast<const uint8_t*>(iq_host), n, hop, scale, probs_host, labels_host, chunk_frames);
-    return predict_host_iq_frames("mdc_predict_host_iq", false, m, iq_host, format, n, hop, scale, 0, probs_host, labels_host, nullptr, chunk_frames);
+    return predict_host_iq_frames("mdc_predict_host_iq", false, m, iq_host, format, n, hop, scale, 0, probs_host, labels_host, nullptr, 0, chunk_frames);
 }
 
 int predict_host_iq_norm(mdc_model* m, const void* iq_host, int format, int64_t n, int64_t hop, float level, int flags, float* probs_host,
                          int32_t* labels_host, mdc_iq_window_stats64* stats_host, int64_t chunk_frames) {
     return predict_host_iq_frames("mdc_predict_host_iq_norm", true, m, iq_host, format, n, hop, level, flags, probs_host, labels_host, stats_host,
-                                  chunk_frames);
+                                  sizeof(mdc_iq_window_stats64), chunk_frames);
 }
 
 }  // namespace mdc

@@ -37,21 +37,7 @@ def frames_from_iq_u8(iq, scale: float = DEFAULT_SCALE, device=None, hop: int = 
     """iq: uint8 tensor/array of interleaved bytes (I0,Q0,I1,Q1,...).  Returns float32 (n,2,128) on the device:
     row 0 = (I - 127.5)*scale, row 1 = (Q - 127.5)*scale; window i starts at pair i*hop (hop = 128: disjoint
     256-byte frames, a trailing partial frame is an error; smaller hops: overlapping windows, mdc_iq_u8_windows)."""
-    import torch
-    t = iq if isinstance(iq, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(iq, dtype=np.uint8)))
-    if t.dtype != torch.uint8:
-        raise TypeError(f"iq must be uint8, got {t.dtype}")
-    if not t.is_cuda:
-        t = t.to(device if device is not None else "cuda:0")
-    t = t.contiguous().view(-1)
-    if t.data_ptr() % 2:
-        t = t.clone()       # a view starting at an odd byte of a larger buffer: the ABI wants whole (I,Q) pairs
-    n = window_count(t.numel(), hop)
-    x = torch.empty((n, 2, 128), dtype=torch.float32, device=t.device)
-    with torch.cuda.device(t.device):
-        _cabi.check(_cabi.lib().mdc_iq_u8_windows(t.data_ptr() if n else None, n, int(hop), float(scale), x.data_ptr() if n else None,
-                                                  torch.cuda.current_stream(t.device).cuda_stream))
-    return x
+    return _windows(_as_bytes(iq), _cabi.IQ_U8_ENTRIES, _cabi.IQ_CU8, hop, scale, None, True, False, device)[0]
 
 
 # ---- level-normalised windows (mdc_iq_u8_windows_norm): DC removal, fixed complex rms, per-window power ------------------
@@ -59,17 +45,10 @@ DEFAULT_LEVEL = 7.8e-3      # the complex rms of the bundled frames, and of Radi
 FULL_SCALE_ENERGY = float((128 * 255) ** 2)      # E of a full-scale constant-envelope window: 0 dBFS
 
 
-def _device_bytes(iq, device=None):
+def _as_bytes(iq):
+    """what the _u8 names take: a uint8 tensor as it is, anything else (a list, a wider integer array) as numpy makes it uint8"""
     import torch
-    t = iq if isinstance(iq, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(iq, dtype=np.uint8)))
-    if t.dtype != torch.uint8:
-        raise TypeError(f"iq must be uint8, got {t.dtype}")
-    if not t.is_cuda:
-        t = t.to(device if device is not None else "cuda:0")
-    t = t.contiguous().view(-1)
-    if t.data_ptr() % 2:
-        t = t.clone()       # a view starting at an odd byte of a larger buffer: the ABI wants whole (I,Q) pairs
-    return t
+    return iq if isinstance(iq, torch.Tensor) else np.asarray(iq, dtype=np.uint8)
 
 
 def stats_tensor_to_numpy(stats):
@@ -83,30 +62,15 @@ def normalized_frames_from_iq_u8(iq, level: float = DEFAULT_LEVEL, remove_dc: bo
     removing each channel's mean if remove_dc (include/mdc.h, mdc_iq_u8_windows_norm).  A constant window becomes all zeros.
     Returns float32 (n,2,128) on the device; with return_stats also the windows' statistics as an (n,4) int32 device tensor
     (columns sum_i, sum_q, sum_sq, energy -- the last two are unsigned 32-bit values; stats_tensor_to_numpy names them)."""
-    import torch
-    t = _device_bytes(iq, device)
-    n = window_count(t.numel(), hop)
-    x = torch.empty((n, 2, 128), dtype=torch.float32, device=t.device)
-    stats = torch.empty((n, 4), dtype=torch.int32, device=t.device) if return_stats else None
-    with torch.cuda.device(t.device):
-        _cabi.check(_cabi.lib().mdc_iq_u8_windows_norm(t.data_ptr() if n else None, n, int(hop), float(level),
-                                                       _cabi.IQ_REMOVE_DC if remove_dc else 0, x.data_ptr() if n else None,
-                                                       stats.data_ptr() if return_stats and n else None,
-                                                       torch.cuda.current_stream(t.device).cuda_stream))
+    flags = _cabi.IQ_REMOVE_DC if remove_dc else 0
+    x, stats = _windows(_as_bytes(iq), _cabi.IQ_U8_ENTRIES, _cabi.IQ_CU8, hop, level, flags, True, return_stats, device)
     return (x, stats) if return_stats else x
 
 
 def window_stats_iq_u8(iq, hop: int = HOP_FRAME, remove_dc: bool = True, device=None):
     """The statistics alone (no frames are written): a numpy array of _cabi.IQ_WINDOW_STATS records, one per window."""
-    import torch
-    t = _device_bytes(iq, device)
-    n = window_count(t.numel(), hop)
-    stats = torch.empty((n, 4), dtype=torch.int32, device=t.device)
-    if n:
-        with torch.cuda.device(t.device):
-            _cabi.check(_cabi.lib().mdc_iq_u8_windows_norm(t.data_ptr(), n, int(hop), 1.0, _cabi.IQ_REMOVE_DC if remove_dc else 0, None,
-                                                           stats.data_ptr(), torch.cuda.current_stream(t.device).cuda_stream))
-    return stats_tensor_to_numpy(stats)
+    flags = _cabi.IQ_REMOVE_DC if remove_dc else 0
+    return stats_tensor_to_numpy(_windows(_as_bytes(iq), _cabi.IQ_U8_ENTRIES, _cabi.IQ_CU8, hop, 1.0, flags, False, True, device)[1])
 
 
 def window_power_dbfs(stats, sample_format="cu8") -> np.ndarray:
@@ -195,6 +159,35 @@ def _device_samples(iq, fmt: int, device=None):
     return t
 
 
+def _pair_count(t, fmt: int) -> int:
+    """(I,Q) pairs of the flat device capture t"""
+    nbytes = t.numel() * t.element_size()
+    if nbytes % _cabi.IQ_PAIR_BYTES[fmt]:
+        raise ValueError("the capture is not a whole number of (I,Q) pairs")
+    return nbytes // _cabi.IQ_PAIR_BYTES[fmt]
+
+
+def _windows(iq, entries, fmt: int, hop, gain, flags, want_frames: bool, want_stats: bool, device):
+    """The six functions of this file that cut a capture into windows: (frames or None, statistics or None) through one row of
+    _cabi's entry table.  flags None: the plain entry, gain is the scale; else the normalising one, gain is the level.  The
+    statistics are the (n,4) device tensor of the row's record, int32 or int64 columns."""
+    import torch
+    t = _device_samples(iq, fmt, device)
+    n = window_count(t.numel() * t.element_size(), hop, _cabi.IQ_PAIR_BYTES[fmt])
+    x = torch.empty((n, 2, 128), dtype=torch.float32, device=t.device) if want_frames else None
+    stats = torch.empty((n, 4), dtype=torch.int32 if entries.stats.itemsize == 16 else torch.int64, device=t.device) if want_stats else None
+    head = (t.data_ptr() if n else None,) + ((fmt,) if entries.takes_format else ())
+    if n or want_frames:      # (the statistics alone of no window: nothing is asked of the library)
+        with torch.cuda.device(t.device):
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+            if flags is None:
+                _cabi.check(getattr(_cabi.lib(), entries.frames)(*head, n, int(hop), float(gain), x.data_ptr() if n else None, stream))
+            else:
+                _cabi.check(getattr(_cabi.lib(), entries.frames_norm)(*head, n, int(hop), float(gain), flags, x.data_ptr() if want_frames and n else None,
+                                                                      stats.data_ptr() if want_stats and n else None, stream))
+    return x, stats
+
+
 def stats64_tensor_to_numpy(stats):
     """The (n,4) int64 device tensor the calls below fill -> a numpy array of _cabi.IQ_WINDOW_STATS64 records."""
     return stats.cpu().numpy().view(_cabi.IQ_WINDOW_STATS64).reshape(-1)
@@ -204,47 +197,23 @@ def frames_from_iq(iq, sample_format, scale=None, device=None, hop: int = HOP_FR
     """frames_from_iq_u8 for any sample format: iq holds interleaved samples of the format's dtype (uint8 / int8 / int16).
     Returns float32 (n,2,128) on the device, sample * scale ("cu8": (byte - 127.5) * scale); default scale 1/127.5, 1/128,
     1/32768 (mdc_iq_windows)."""
-    import torch
     fmt = sample_format_id(sample_format)
-    t = _device_samples(iq, fmt, device)
-    n = window_count(t.numel() * t.element_size(), hop, _cabi.IQ_PAIR_BYTES[fmt])
-    x = torch.empty((n, 2, 128), dtype=torch.float32, device=t.device)
-    with torch.cuda.device(t.device):
-        _cabi.check(_cabi.lib().mdc_iq_windows(t.data_ptr() if n else None, fmt, n, int(hop), float(DEFAULT_SCALES[fmt] if scale is None else scale),
-                                               x.data_ptr() if n else None, torch.cuda.current_stream(t.device).cuda_stream))
-    return x
+    return _windows(iq, _cabi.IQ_ENTRIES, fmt, hop, DEFAULT_SCALES[fmt] if scale is None else scale, None, True, False, device)[0]
 
 
 def normalized_frames_from_iq(iq, sample_format, level: float = DEFAULT_LEVEL, remove_dc: bool = True, hop: int = HOP_FRAME, device=None,
                               return_stats: bool = False):
     """normalized_frames_from_iq_u8 for any sample format (mdc_iq_windows_norm).  With return_stats also the windows' statistics
     as an (n,4) int64 device tensor (columns sum_i, sum_q, sum_sq, energy; stats64_tensor_to_numpy names them)."""
-    import torch
-    fmt = sample_format_id(sample_format)
-    t = _device_samples(iq, fmt, device)
-    n = window_count(t.numel() * t.element_size(), hop, _cabi.IQ_PAIR_BYTES[fmt])
-    x = torch.empty((n, 2, 128), dtype=torch.float32, device=t.device)
-    stats = torch.empty((n, 4), dtype=torch.int64, device=t.device) if return_stats else None
-    with torch.cuda.device(t.device):
-        _cabi.check(_cabi.lib().mdc_iq_windows_norm(t.data_ptr() if n else None, fmt, n, int(hop), float(level),
-                                                    _cabi.IQ_REMOVE_DC if remove_dc else 0, x.data_ptr() if n else None,
-                                                    stats.data_ptr() if return_stats and n else None,
-                                                    torch.cuda.current_stream(t.device).cuda_stream))
+    flags = _cabi.IQ_REMOVE_DC if remove_dc else 0
+    x, stats = _windows(iq, _cabi.IQ_ENTRIES, sample_format_id(sample_format), hop, level, flags, True, return_stats, device)
     return (x, stats) if return_stats else x
 
 
 def window_stats_iq(iq, sample_format, hop: int = HOP_FRAME, remove_dc: bool = True, device=None):
     """The statistics alone (no frames are written): a numpy array of _cabi.IQ_WINDOW_STATS64 records, one per window."""
-    import torch
-    fmt = sample_format_id(sample_format)
-    t = _device_samples(iq, fmt, device)
-    n = window_count(t.numel() * t.element_size(), hop, _cabi.IQ_PAIR_BYTES[fmt])
-    stats = torch.empty((n, 4), dtype=torch.int64, device=t.device)
-    if n:
-        with torch.cuda.device(t.device):
-            _cabi.check(_cabi.lib().mdc_iq_windows_norm(t.data_ptr(), fmt, n, int(hop), 1.0, _cabi.IQ_REMOVE_DC if remove_dc else 0, None,
-                                                        stats.data_ptr(), torch.cuda.current_stream(t.device).cuda_stream))
-    return stats64_tensor_to_numpy(stats)
+    flags = _cabi.IQ_REMOVE_DC if remove_dc else 0
+    return stats64_tensor_to_numpy(_windows(iq, _cabi.IQ_ENTRIES, sample_format_id(sample_format), hop, 1.0, flags, False, True, device)[1])
 
 
 # ---- digital down-converter (mdc_iq_ddc): frequency shift, low-pass, decimate -- exact integers, on the device -------------
@@ -300,6 +269,15 @@ def nco_table() -> np.ndarray:
     return t
 
 
+def _int16_taps(taps) -> np.ndarray:
+    h = np.asarray(taps)
+    if h.dtype.kind != "i" or h.ndim != 1:
+        raise TypeError("taps must be a one-dimensional integer array (int16)")
+    if h.size and (h.min() < -32768 or h.max() > 32767):
+        raise ValueError("taps must fit int16")
+    return np.ascontiguousarray(h.astype(np.int16))
+
+
 def ddc(iq, sample_format, shift: float = 0.0, decimate: int = 1, taps=None, phase0: int = 0, device=None):
     """Tune, low-pass and decimate a capture on the device (mdc_iq_ddc, include/mdc.h: exact integer arithmetic).  iq: as
     frames_from_iq; shift: the frequency added to the capture, cycles per input sample (phase_step); taps: int16 Q15, applied as
@@ -314,16 +292,9 @@ def ddc(iq, sample_format, shift: float = 0.0, decimate: int = 1, taps=None, pha
         if D == 1:
             raise ValueError("decimate == 1 needs explicit taps (design_lowpass designs anti-alias filters for decimate >= 2)")
         taps = design_lowpass(D)
-    h = np.asarray(taps)
-    if h.dtype.kind != "i" or h.ndim != 1:
-        raise TypeError("taps must be a one-dimensional integer array (int16 Q15)")
-    if h.size and (h.min() < -32768 or h.max() > 32767):
-        raise ValueError("taps must fit int16")
-    h = np.ascontiguousarray(h.astype(np.int16))
+    h = _int16_taps(taps)
     t = _device_samples(iq, fmt, device)
-    pairs = t.numel() * t.element_size() // _cabi.IQ_PAIR_BYTES[fmt]
-    if pairs * _cabi.IQ_PAIR_BYTES[fmt] != t.numel() * t.element_size():
-        raise ValueError("the capture is not a whole number of (I,Q) pairs")
+    pairs = _pair_count(t, fmt)
     L = _cabi.lib()
     n_out = _cabi.check(L.mdc_iq_ddc_out_count(pairs, h.size, D))
     out = torch.empty((n_out, 2), dtype=torch.int16, device=t.device)
@@ -433,16 +404,9 @@ def resample(iq, sample_format, shift: float = 0.0, interpolate: int = 1, decima
         if L == 1 and D == 1:
             raise ValueError("interpolate == decimate needs explicit taps (design_resampler designs filters for a change of rate)")
         taps = design_resampler(L, D)
-    h = np.asarray(taps)
-    if h.dtype.kind != "i" or h.ndim != 1:
-        raise TypeError("taps must be a one-dimensional integer array (int16)")
-    if h.size and (h.min() < -32768 or h.max() > 32767):
-        raise ValueError("taps must fit int16")
-    h = np.ascontiguousarray(h.astype(np.int16))
+    h = _int16_taps(taps)
     t = _device_samples(iq, fmt, device)
-    pairs = t.numel() * t.element_size() // _cabi.IQ_PAIR_BYTES[fmt]
-    if pairs * _cabi.IQ_PAIR_BYTES[fmt] != t.numel() * t.element_size():
-        raise ValueError("the capture is not a whole number of (I,Q) pairs")
+    pairs = _pair_count(t, fmt)
     lib = _cabi.lib()
     n_out = _cabi.check(lib.mdc_iq_resample_out_count(pairs, h.size, L, D))
     out = torch.empty((n_out, 2), dtype=torch.int16, device=t.device)
@@ -453,15 +417,6 @@ def resample(iq, sample_format, shift: float = 0.0, interpolate: int = 1, decima
 
 
 # ---- batched extraction (mdc_iq_extract): K stretches of a capture, each through the resampler's chain, in one launch ---------
-def _int16_taps(taps) -> np.ndarray:
-    h = np.asarray(taps)
-    if h.dtype.kind != "i" or h.ndim != 1:
-        raise TypeError("taps must be a one-dimensional integer array (int16)")
-    if h.size and (h.min() < -32768 or h.max() > 32767):
-        raise ValueError("taps must fit int16")
-    return np.ascontiguousarray(h.astype(np.int16))
-
-
 def extract_plan(jobs, filters, sample_format, pairs_in: int, out_pairs=None):
     """The plan of one mdc_iq_extract launch (include/mdc.h, "batched extraction"; host code, no GPU).  filters: a sequence of
     (interpolate, decimate, taps); equal ones -- the same L, D and tap bytes -- are stored once.  jobs: a numpy array of
@@ -514,9 +469,7 @@ def extract_run(iq, sample_format, blob, out_pairs: int, out=None, device=None):
     import torch
     fmt = sample_format_id(sample_format)
     t = _device_samples(iq, fmt, device)
-    pairs = t.numel() * t.element_size() // _cabi.IQ_PAIR_BYTES[fmt]
-    if pairs * _cabi.IQ_PAIR_BYTES[fmt] != t.numel() * t.element_size():
-        raise ValueError("the capture is not a whole number of (I,Q) pairs")
+    pairs = _pair_count(t, fmt)
     blob = np.ascontiguousarray(blob, dtype=np.uint8)
     if out is None:
         out = torch.zeros((int(out_pairs), 2), dtype=torch.int16, device=t.device)
@@ -651,9 +604,7 @@ def _spectra(order, iq, sample_format, nfft, hop, avg, window, device, scale):
     N = int(nfft)
     H = N // 2 if hop is None else int(hop)
     t = _device_samples(iq, fmt, device)
-    pairs = t.numel() * t.element_size() // _cabi.IQ_PAIR_BYTES[fmt]
-    if pairs * _cabi.IQ_PAIR_BYTES[fmt] != t.numel() * t.element_size():
-        raise ValueError("the capture is not a whole number of (I,Q) pairs")
+    pairs = _pair_count(t, fmt)
     lib = _cabi.lib()
     rows = _cabi.check(lib.mdc_iq_spectrogram_rows(pairs, N, H, int(avg)))
     w, default_scale = _window_tensor(window, N, t.device)
@@ -771,9 +722,7 @@ def line_spectra(iq, sample_format, jobs, orders=(0, 2, 4), nfft: int = 1024, ho
             any(isinstance(o, bool) or o not in _cabi.LINE_SPECTRUM_ORDERS for o in ords):
         raise ValueError(f"orders must be 1..{_cabi.LINE_SPECTRA_MAX_ORDERS} distinct values of {_cabi.LINE_SPECTRUM_ORDERS} (got {orders!r})")
     t = _device_samples(iq, fmt, device)
-    pairs = t.numel() * t.element_size() // _cabi.IQ_PAIR_BYTES[fmt]
-    if pairs * _cabi.IQ_PAIR_BYTES[fmt] != t.numel() * t.element_size():
-        raise ValueError("the capture is not a whole number of (I,Q) pairs")
+    pairs = _pair_count(t, fmt)
     if isinstance(jobs, np.ndarray) and jobs.ndim == 1:
         if jobs.size < 1 or jobs.dtype.kind not in "iu":
             raise ValueError("offsets must be a one-dimensional integer array of at least one value")
@@ -1224,9 +1173,7 @@ def channelize(iq, sample_format, channels: int, decimate=None, taps=None, tap_s
     M = _check_channels(channels)
     D = M // 2 if decimate is None else int(decimate)
     t = _device_samples(iq, fmt, device)
-    pairs = t.numel() * t.element_size() // _cabi.IQ_PAIR_BYTES[fmt]
-    if pairs * _cabi.IQ_PAIR_BYTES[fmt] != t.numel() * t.element_size():
-        raise ValueError("the capture is not a whole number of (I,Q) pairs")
+    pairs = _pair_count(t, fmt)
     if int(first_index) < 0:
         raise ValueError("first_index must be >= 0")
     if taps is None:

@@ -25,7 +25,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from . import _cabi
+from . import _cabi, capture
 from .formats import q612
 from .formats.h5mini import load_keras_h5
 from .topology import Topology, synthetic_weights
@@ -69,6 +69,16 @@ def _nonfinite_policy(nonfinite: Optional[str], tap: Optional[str] = None) -> Op
 def _torch():
     import torch
     return torch
+
+
+_TENSOR_DTYPE: dict = {}      # MDC_IQ_* -> the torch dtype of such a capture (filled at the first use: torch is imported late)
+
+
+def _tensor_dtype(fmt: int):
+    if not _TENSOR_DTYPE:
+        torch = _torch()
+        _TENSOR_DTYPE.update({_cabi.IQ_CU8: torch.uint8, _cabi.IQ_CI8: torch.int8, _cabi.IQ_CI16: torch.int16})
+    return _TENSOR_DTYPE[fmt]
 
 
 class VTCNN2:
@@ -765,100 +775,93 @@ class VTCNN2:
         mdc_predict_host_iq_u8_norm; every kind of net.  squelch_dbfs (needs normalize="rms"): windows whose power
         (frontend.window_power_dbfs: 0 dBFS = a full-scale constant envelope) lies below it get label -1, their
         probabilities stay as computed.  return_power=True appends the per-window dBFS vector (float64) to the result."""
+        return self._predict_windows(iq, _cabi.IQ_CU8, scale, batch_size, hop, normalize, level, remove_dc, squelch_dbfs, return_power)
+
+    def _predict_windows(self, iq, fmt, scale, batch_size, hop, normalize, level, remove_dc, squelch_dbfs, return_power):
+        """predict_iq_u8 and predict_iq behind their own input checks: iq is a tensor, or anything numpy turns into the format's
+        dtype.  _cabi's entry table says what differs between unsigned bytes (their own entries, the 16-byte record) and the other
+        formats.  Plain unsigned bytes need no frames: the forward kernels read them (cnn.py's literal net converts first)."""
         torch = _torch()
-        from .frontend import DEFAULT_SCALE, frames_from_iq_u8, window_count
-        if normalize is not None:
+        from . import frontend as F
+        norm = normalize is not None
+        want_stats = False
+        if norm:
             if normalize != "rms":
                 raise ValueError(f"normalize must be None or 'rms'; got {normalize!r}")
             if scale is not None:
                 raise ValueError("scale= and normalize='rms' cannot be combined: the normalised path scales each window itself")
-            return self._predict_iq_u8_norm(iq, batch_size, hop, float(level), bool(remove_dc), squelch_dbfs, bool(return_power))
-        if squelch_dbfs is not None or return_power:
-            raise ValueError("squelch_dbfs and return_power need normalize='rms' (the plain path computes no window power)")
-        scale = DEFAULT_SCALE if scale is None else float(scale)
-        as_numpy = not isinstance(iq, torch.Tensor)
-        if as_numpy and self.topology.kind != "cnnpy":      # host bytes: the library's streaming driver (mdc_predict_host_iq_u8)
-            b = np.ascontiguousarray(np.asarray(iq, dtype=np.uint8)).reshape(-1)
-            n, Cn = window_count(b.size, hop), self.topology.classes
-            probs, labels = np.empty((n, Cn), np.float32), np.empty((n,), np.int32)
-            self._check(self._lib().mdc_predict_host_iq_u8(self._engine(), b.ctypes.data, n, int(hop), scale, probs.ctypes.data,
-                                                           labels.ctypes.data, self._host_chunk(batch_size)))
-            return probs, labels
-        t = torch.from_numpy(np.ascontiguousarray(np.asarray(iq, dtype=np.uint8))) if as_numpy else iq
-        if t.dtype != torch.uint8:
-            raise TypeError(f"iq must be uint8, got {t.dtype}")
-        t = t.to(f"cuda:{self.device_index}").contiguous().view(-1)
-        n, Cn = window_count(t.numel(), hop), self.topology.classes
-        if t.data_ptr() % 2:
-            t = t.clone()       # a view into a larger buffer starting at an odd byte: the ABI wants whole (I,Q) pairs
-        probs = torch.empty((n, Cn), dtype=torch.float32, device=t.device)
-        labels = torch.empty((n,), dtype=torch.int32, device=t.device)
-        if n == 0:
-            return (probs.cpu().numpy(), labels.cpu().numpy()) if as_numpy else (probs, labels)
-        if self.topology.kind == "cnnpy":
-            x = frames_from_iq_u8(t, scale, hop=hop)
-            self.forward_device(x, probs, labels, batch_size=batch_size or None)
+            gain = float(level)
+            if not (gain > 0.0 and np.isfinite(gain)):
+                raise ValueError("level must be finite and > 0")
+            flags = _cabi.IQ_REMOVE_DC if remove_dc else 0
+            want_stats = squelch_dbfs is not None or return_power
+            floor = F.squelch_energy_threshold(squelch_dbfs, fmt) if squelch_dbfs is not None else 0
         else:
-            L, h = self._lib(), self._engine()
-            chunk = max(1, min(int(batch_size) if batch_size else self.default_chunk, n))
-            with torch.cuda.device(t.device):
-                stream = torch.cuda.current_stream(t.device).cuda_stream
-                ws, ws_bytes = self._workspace(chunk, stream)
-                for s0 in range(0, n, chunk):
-                    m = min(chunk, n - s0)
-                    self._check(L.mdc_forward_iq_u8(h, t.data_ptr() + 2 * hop * s0, m, hop, scale,
-                                                    probs.data_ptr() + s0 * Cn * 4, labels.data_ptr() + s0 * 4,
-                                                    ws.data_ptr() if ws is not None else None, ws_bytes, stream))
-        return (probs.cpu().numpy(), labels.cpu().numpy()) if as_numpy else (probs, labels)
-
-    def _predict_iq_u8_norm(self, iq, batch_size, hop, level, remove_dc, squelch_dbfs, return_power):
-        torch = _torch()
-        from .frontend import FULL_SCALE_ENERGY, squelch_energy_threshold, window_count, window_power_dbfs
-        if not (level > 0.0 and np.isfinite(level)):
-            raise ValueError("level must be finite and > 0")
-        flags = _cabi.IQ_REMOVE_DC if remove_dc else 0
-        want_stats = squelch_dbfs is not None or return_power
-        floor = squelch_energy_threshold(squelch_dbfs) if squelch_dbfs is not None else 0
-        Cn = self.topology.classes
-        if not isinstance(iq, torch.Tensor):      # host bytes: the library's streaming driver
-            b = np.ascontiguousarray(np.asarray(iq, dtype=np.uint8)).reshape(-1)
-            n = window_count(b.size, hop)
+            if squelch_dbfs is not None or return_power:
+                raise ValueError("squelch_dbfs and return_power need normalize='rms' (the plain path computes no window power)")
+            gain = F.DEFAULT_SCALES[fmt] if scale is None else float(scale)
+        entries = _cabi.IQ_U8_ENTRIES if fmt == _cabi.IQ_CU8 else _cabi.IQ_ENTRIES
+        head = (fmt,) if entries.takes_format else ()
+        fused = not (norm or entries.takes_format)      # plain unsigned bytes
+        pair, Cn = _cabi.IQ_PAIR_BYTES[fmt], self.topology.classes
+        L = self._lib()
+        as_numpy = not isinstance(iq, torch.Tensor)
+        if as_numpy:
+            iq = np.ascontiguousarray(np.asarray(iq, dtype=_cabi.IQ_SAMPLE_DTYPE[fmt])).reshape(-1)
+        elif iq.dtype != _tensor_dtype(fmt):
+            raise TypeError(f"iq must be {_cabi.IQ_SAMPLE_DTYPE[fmt].name}, got {iq.dtype}")
+        if as_numpy and not (fused and self.topology.kind == "cnnpy"):      # host samples: the library's streaming driver
+            n = F.window_count(iq.nbytes, hop, pair)
             probs, labels = np.empty((n, Cn), np.float32), np.empty((n,), np.int32)
-            stats = np.empty((n,), _cabi.IQ_WINDOW_STATS) if want_stats else None
-            self._check(self._lib().mdc_predict_host_iq_u8_norm(self._engine(), b.ctypes.data, n, int(hop), level, flags, probs.ctypes.data,
-                                                                labels.ctypes.data, stats.ctypes.data if want_stats else None,
-                                                                self._host_chunk(batch_size)))
+            if not norm:
+                self._check(getattr(L, entries.host)(self._engine(), iq.ctypes.data, *head, n, int(hop), gain, probs.ctypes.data, labels.ctypes.data,
+                                                     self._host_chunk(batch_size)))
+                return probs, labels
+            stats = np.empty((n,), entries.stats) if want_stats else None
+            self._check(getattr(L, entries.host_norm)(self._engine(), iq.ctypes.data, *head, n, int(hop), gain, flags, probs.ctypes.data,
+                                                      labels.ctypes.data, stats.ctypes.data if want_stats else None, self._host_chunk(batch_size)))
             if squelch_dbfs is not None:
-                labels[stats["energy"] < floor] = -1
-            return (probs, labels, window_power_dbfs(stats)) if return_power else (probs, labels)
-        if iq.dtype != torch.uint8:
-            raise TypeError(f"iq must be uint8, got {iq.dtype}")
-        t = iq.to(f"cuda:{self.device_index}").contiguous().view(-1)
-        n = window_count(t.numel(), hop)
-        if t.data_ptr() % 2:
-            t = t.clone()       # a view into a larger buffer starting at an odd byte: the ABI wants whole (I,Q) pairs
+                labels[stats["energy"] < np.uint64(floor)] = -1
+            return (probs, labels, F.window_power_dbfs(stats, fmt)) if return_power else (probs, labels)
+        t = (torch.from_numpy(iq) if as_numpy else iq).to(f"cuda:{self.device_index}").contiguous().view(-1)
+        n = F.window_count(t.numel() * t.element_size(), hop, pair)
+        if t.data_ptr() % pair:
+            t = t.clone()       # a view into a larger buffer starting inside a pair: the ABI wants whole (I,Q) pairs
         probs = torch.empty((n, Cn), dtype=torch.float32, device=t.device)
         labels = torch.empty((n,), dtype=torch.int32, device=t.device)
-        stats = torch.empty((n, 4), dtype=torch.int32, device=t.device) if want_stats else None
-        if n:
-            L, h = self._lib(), self._engine()
+        if want_stats:
+            record = entries.stats.itemsize
+            stats = torch.empty((n, 4), dtype=torch.int32 if record == 16 else torch.int64, device=t.device)
+        if n and fused and self.topology.kind == "cnnpy":
+            self.forward_device(F.frames_from_iq_u8(t, gain, hop=hop), probs, labels, batch_size=batch_size or None)
+        elif n:
+            h = self._engine()
+            frames = None if fused else getattr(L, entries.frames_norm if norm else entries.frames)
             chunk = max(1, min(int(batch_size) if batch_size else self.default_chunk, n))
             with torch.cuda.device(t.device):
                 stream = torch.cuda.current_stream(t.device).cuda_stream
                 ws, ws_bytes = self._workspace(chunk, stream)
-                x = torch.empty((chunk, 2, 128), dtype=torch.float32, device=t.device)      # one chunk of frames, reused in stream order
+                ws_ptr = ws.data_ptr() if ws is not None else None
+                # one chunk of frames, reused in stream order
+                x = None if fused else torch.empty((chunk, 2, 128), dtype=torch.float32, device=t.device)
                 for s0 in range(0, n, chunk):
                     m = min(chunk, n - s0)
-                    self._check(L.mdc_iq_u8_windows_norm(t.data_ptr() + 2 * hop * s0, m, hop, level, flags, x.data_ptr(),
-                                                         (stats.data_ptr() + 16 * s0) if want_stats else None, stream))
-                    self._check(L.mdc_forward(h, x.data_ptr(), m, probs.data_ptr() + s0 * Cn * 4, labels.data_ptr() + s0 * 4, None,
-                                              _cabi.TAP_NONE, ws.data_ptr() if ws is not None else None, ws_bytes, stream))
+                    src, p_out, l_out = t.data_ptr() + pair * hop * s0, probs.data_ptr() + s0 * Cn * 4, labels.data_ptr() + s0 * 4
+                    if fused:
+                        self._check(L.mdc_forward_iq_u8(h, src, m, hop, gain, p_out, l_out, ws_ptr, ws_bytes, stream))
+                        continue
+                    if norm:
+                        self._check(frames(src, *head, m, hop, gain, flags, x.data_ptr(), (stats.data_ptr() + record * s0) if want_stats else None, stream))
+                    else:
+                        self._check(frames(src, *head, m, hop, gain, x.data_ptr(), stream))
+                    self._check(L.mdc_forward(h, x.data_ptr(), m, p_out, l_out, None, _cabi.TAP_NONE, ws_ptr, ws_bytes, stream))
+        if not want_stats:
+            return (probs.cpu().numpy(), labels.cpu().numpy()) if as_numpy else (probs, labels)
         if squelch_dbfs is not None:
-            # (every energy is below 2^31 - 1: the int32 column holds it as it is, and a larger floor means the same as that one)
-            labels.masked_fill_(stats[:, 3] < min(floor, 0x7FFFFFFF), -1)
-        if return_power:
-            return probs, labels, 10.0 * torch.log10(stats[:, 3].to(torch.float64) / FULL_SCALE_ENERGY)
-        return probs, labels
+            # (the int32 column holds the 16-byte record's energies as they are, all below 2^31 - 1, and a larger floor means the same
+            # as that one; the 64-bit energies and floors are all below 2^47)
+            labels.masked_fill_(stats[:, 3] < min(floor, torch.iinfo(stats.dtype).max), -1)
+        return (probs, labels, 10.0 * torch.log10(stats[:, 3].to(torch.float64) / F.full_scale_energy(fmt))) if return_power else (probs, labels)
 
     def predict_iq(self, iq, sample_format, scale: Optional[float] = None, batch_size: int = 0, hop: int = 128,
                    normalize: Optional[str] = None, level: float = 7.8e-3, remove_dc: bool = True, squelch_dbfs: Optional[float] = None,
@@ -899,411 +902,14 @@ class VTCNN2:
             return tuple(r.cpu().numpy() for r in res) if as_numpy else res
         if as_numpy:
             iq = F.host_samples(iq, fmt)
-        elif iq.dtype != {_cabi.IQ_CU8: torch.uint8, _cabi.IQ_CI8: torch.int8, _cabi.IQ_CI16: torch.int16}[fmt]:
+        elif iq.dtype != _tensor_dtype(fmt):
             raise TypeError(f"iq must be {_cabi.IQ_SAMPLE_DTYPE[fmt].name} for sample_format {sample_format!r}, got {iq.dtype}")
-        if fmt == _cabi.IQ_CU8:
-            return self.predict_iq_u8(iq, scale, batch_size=batch_size, hop=hop, normalize=normalize, level=level, remove_dc=remove_dc,
-                                      squelch_dbfs=squelch_dbfs, return_power=return_power)
-        norm = normalize is not None
-        if norm:
-            if normalize != "rms":
-                raise ValueError(f"normalize must be None or 'rms'; got {normalize!r}")
-            if scale is not None:
-                raise ValueError("scale= and normalize='rms' cannot be combined: the normalised path scales each window itself")
-            gain = float(level)
-            if not (gain > 0.0 and np.isfinite(gain)):
-                raise ValueError("level must be finite and > 0")
-        else:
-            if squelch_dbfs is not None or return_power:
-                raise ValueError("squelch_dbfs and return_power need normalize='rms' (the plain path computes no window power)")
-            gain = F.DEFAULT_SCALES[fmt] if scale is None else float(scale)
-        flags = _cabi.IQ_REMOVE_DC if remove_dc else 0
-        want_stats = squelch_dbfs is not None or return_power
-        floor = F.squelch_energy_threshold(squelch_dbfs, fmt) if squelch_dbfs is not None else 0
-        pair, Cn = _cabi.IQ_PAIR_BYTES[fmt], self.topology.classes
-        L = self._lib()
-        if as_numpy:      # host samples: the library's streaming driver
-            n = F.window_count(iq.nbytes, hop, pair)
-            probs, labels = np.empty((n, Cn), np.float32), np.empty((n,), np.int32)
-            if not norm:
-                self._check(L.mdc_predict_host_iq(self._engine(), iq.ctypes.data, fmt, n, int(hop), gain, probs.ctypes.data, labels.ctypes.data,
-                                                  self._host_chunk(batch_size)))
-                return probs, labels
-            stats = np.empty((n,), _cabi.IQ_WINDOW_STATS64) if want_stats else None
-            self._check(L.mdc_predict_host_iq_norm(self._engine(), iq.ctypes.data, fmt, n, int(hop), gain, flags, probs.ctypes.data,
-                                                   labels.ctypes.data, stats.ctypes.data if want_stats else None, self._host_chunk(batch_size)))
-            if squelch_dbfs is not None:
-                labels[stats["energy"] < np.uint64(floor)] = -1
-            return (probs, labels, F.window_power_dbfs(stats, fmt)) if return_power else (probs, labels)
-        t = iq.to(f"cuda:{self.device_index}").contiguous().view(-1)
-        n = F.window_count(t.numel() * t.element_size(), hop, pair)
-        if t.data_ptr() % pair:
-            t = t.clone()       # a view into a larger buffer starting inside a pair: the ABI wants whole (I,Q) pairs
-        probs = torch.empty((n, Cn), dtype=torch.float32, device=t.device)
-        labels = torch.empty((n,), dtype=torch.int32, device=t.device)
-        stats = torch.empty((n, 4), dtype=torch.int64, device=t.device) if want_stats else None
-        if n:
-            h = self._engine()
-            chunk = max(1, min(int(batch_size) if batch_size else self.default_chunk, n))
-            with torch.cuda.device(t.device):
-                stream = torch.cuda.current_stream(t.device).cuda_stream
-                ws, ws_bytes = self._workspace(chunk, stream)
-                x = torch.empty((chunk, 2, 128), dtype=torch.float32, device=t.device)      # one chunk of frames, reused in stream order
-                for s0 in range(0, n, chunk):
-                    m = min(chunk, n - s0)
-                    src = t.data_ptr() + pair * hop * s0
-                    if norm:
-                        self._check(L.mdc_iq_windows_norm(src, fmt, m, hop, gain, flags, x.data_ptr(),
-                                                          (stats.data_ptr() + 32 * s0) if want_stats else None, stream))
-                    else:
-                        self._check(L.mdc_iq_windows(src, fmt, m, hop, gain, x.data_ptr(), stream))
-                    self._check(L.mdc_forward(h, x.data_ptr(), m, probs.data_ptr() + s0 * Cn * 4, labels.data_ptr() + s0 * 4, None,
-                                              _cabi.TAP_NONE, ws.data_ptr() if ws is not None else None, ws_bytes, stream))
-        if squelch_dbfs is not None:
-            labels.masked_fill_(stats[:, 3] < floor, -1)      # (64-bit energies: every E and every floor is below 2^47)
-        if return_power:
-            return probs, labels, 10.0 * torch.log10(stats[:, 3].to(torch.float64) / F.full_scale_energy(fmt))
-        return probs, labels
+        return self._predict_windows(iq, fmt, scale, batch_size, hop, normalize, level, remove_dc, squelch_dbfs, return_power)
 
-    def scan_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_db: float = 6.0, hop: int = 128, level: float = 7.8e-3,
-                squelch_dbfs: Optional[float] = None, refine: bool = False, min_line_db: float = 8.0, bursts: bool = False, hold: float = 0.98,
-                burst_threshold_db: float = 3.0, min_rows: int = 1, merge_rows: int = 1, **find_kw):
-        """A wideband capture in, "what is transmitting where, and what modulation" out.  The capture's power spectrogram
-        (frontend.spectrogram: nfft bins, Hann window, segments nfft // 2 apart, `avg` of them per row, on the device) is averaged
-        over its rows into one spectrum; frontend.find_emitters(spectrum, threshold_db, window=the Hann window, **find_kw) lists
-        the emitters; each one is brought to 0 Hz and to the nets' rate by frontend.channel_plan's (shift, L, D) -- through
-        frontend.ddc when L == 1, else frontend.resample, with frontend.plan_taps(L, D) as the filter --, cut into windows `hop` output pairs apart
-        (hop == 128: the stream is trimmed to whole frames) and classified with predict_iq(..., "ci16", normalize="rms", level=,
-        squelch_dbfs=, return_power=True).  Returns one dict per emitter, in order of centre: centre, bandwidth (cycles per input
-        sample), power_dbfs, snr_db, shift, interpolate, decimate, probs, labels, window_dbfs (predict_iq's three results: device
-        tensors, or numpy arrays for a numpy capture) and label, the most frequent label among the windows the squelch let through
-        (the smallest on a tie; -1 if there are none).
-
-        refine=True replaces the plan's two guesses -- a symbol rate from the thresholded width, a carrier from the centroid -- by
-        the emitter's spectral lines.  Per emitter: (1) isolate it at about four times its width, D0 = clamp(floor(1 / (4
-        bandwidth)), 1, 256), iso = frontend.ddc(capture, shift=-centre, decimate=D0, taps=frontend.plan_taps(1, D0)); b =
-        bandwidth D0 is its width there.  (2) frontend.estimate_symbol_rate(iso, "ci16", lo=b / 2.5, hi=min(0.45, 1.25 b),
-        min_line_db=): a linear modulation's symbol rate is b / (1 + beta), beta in 0..1, and a thresholded width may be 25 % off;
-        the band also keeps the line's harmonics out.  symbol_rate = rate / D0 (None without a line).  (3)
-        frontend.estimate_carrier_offset(iso, "ci16", max_offset=b / 8, min_line_db=) (at most 0.12: an emitter filling the whole
-        band); carrier_offset = offset / D0, and shift = -(centre + carrier_offset), folded into [-0.5, 0.5].  (4) (L, D) = frontend.resample_ratio(1.0, symbol_rate, 8) when the symbol line was found and
-        a ratio within its 1 % exists, else channel_plan's.  (5) The ORIGINAL capture is resampled with that shift and ratio and
-        plan_taps(L, D), and classified as above.  The record gains symbol_rate (cycles per input sample, or None),
-        symbol_line_db, carrier_offset, carrier_order (2, 4, or 0: no line -- 8PSK, analogue and frequency-shift signals show
-        none -- and the centroid stands) and carrier_line_db; centre stays the centroid.  refine=False is the plan alone, and its
-        record has none of the five.
-
-        bursts=True is the scan for INTERMITTENT emitters -- push-to-talk, telemetry bursts, packet traffic --, which the mean over
-        the rows dilutes (on 3 % of the time: by 15 dB) until they are missed or found in fragments.  The spectrogram is then looked
-        at along time per bin: Q = frontend.spectrum_quantiles(spec, (0.5, hold)), one call on the device.  The emitters are
-        find_emitters(Q[1], threshold_db, ...): the spectrum each bin reaches in its top 1 - hold of the rows, whose own median bin
-        is find_emitters' floor, so that the noise's high quantile cancels.  The noise per bin is the median over the bins of
-        Q[0], the median over time, which bursts do not lift.  Per emitter, (first, count) = frontend.emitter_bins(e, nfft), band =
-        frontend.band_power(spec, first, count), and frontend.find_bursts(band, count * noise, burst_threshold_db, min_rows,
-        merge_rows) gives the rows it was on.  The record gains bursts, a list of half-open intervals of INPUT pairs
-        (frontend.burst_pairs), and duty, on-rows / rows.  Plan, refine, tuning, resampling and predict_iq run on the whole
-        capture as without bursts; then every window whose frontend.window_support (the input pairs its 128 outputs read through
-        the filter) is not wholly inside one burst gets label -1, as the squelch does, and label is the majority among the
-        windows still open; probs and window_dbfs are untouched.  A spectrogram's rows drop trailing segments that do not fill a
-        row (and a window's support is wider than the window): the last windows of a capture can therefore be gated even for an
-        emitter that never pauses.  An emitter must revisit its bins in at least 1 - hold of the rows to be seen.  bursts=False
-        (the default) is the mean spectrum, and its record has neither key."""
-        torch = _torch()
-        from . import frontend as F
-        fmt = F.sample_format_id(sample_format)
-        as_numpy = not isinstance(iq, torch.Tensor)
-        dev = F._device_samples(iq, fmt, f"cuda:{self.device_index}")
-        window = F.design_window(nfft)
-        spec = F.spectrogram(dev, fmt, nfft=nfft, avg=avg)
-        if spec.shape[0] == 0:
-            raise ValueError(f"the capture is too short for one row of {avg} segments of {nfft} pairs")
-        if bursts:
-            quant = F.spectrum_quantiles(spec, (0.5, float(hold))).to(torch.float64).cpu().numpy()
-            psd, noise = quant[1], float(np.median(quant[0]))
-        else:
-            psd = spec.to(torch.float64).mean(0).cpu().numpy()
-        out = []
-        for e in F.find_emitters(psd, threshold_db=threshold_db, window=window, **find_kw):
-            shift, L, D, _ = F.channel_plan(e.centre, e.bandwidth)
-            extra = {}
-            if refine:
-                D0 = min(max(int(1.0 / (4.0 * e.bandwidth)), 1), 256)
-                iso = F.ddc(dev, fmt, shift=-e.centre, decimate=D0, taps=F.plan_taps(1, D0)).reshape(-1)
-                b = e.bandwidth * D0
-                rate, rate_db = F.estimate_symbol_rate(iso, _cabi.IQ_CI16, lo=b / 2.5, hi=min(0.45, 1.25 * b), min_line_db=min_line_db)
-                offset, order, offset_db = F.estimate_carrier_offset(iso, _cabi.IQ_CI16, max_offset=min(b / 8.0, 0.12), min_line_db=min_line_db)
-                shift = -(e.centre + offset / D0)
-                if abs(shift) > 0.5:      # an emitter at the band's edge: the same frequency, one turn on
-                    shift -= round(shift)
-                if rate is not None:
-                    try:
-                        L, D, _ = F.resample_ratio(1.0, rate / D0, 8)
-                    except ValueError:      # nothing within 1 %: the plan's ratio stands
-                        pass
-                extra = dict(symbol_rate=None if rate is None else rate / D0, symbol_line_db=rate_db, carrier_offset=offset / D0, carrier_order=order,
-                             carrier_line_db=offset_db)
-            taps = F.plan_taps(L, D)
-            if L == 1:
-                down = F.ddc(dev, fmt, shift=shift, decimate=D, taps=taps)
-            else:
-                down = F.resample(dev, fmt, shift=shift, interpolate=L, decimate=D, taps=taps)
-            if hop == 128:
-                down = down[:down.shape[0] // 128 * 128]
-            probs, labels, dbfs = self.predict_iq(down.reshape(-1), _cabi.IQ_CI16, hop=hop, normalize="rms", level=level, squelch_dbfs=squelch_dbfs,
-                                                  return_power=True)
-            if bursts:
-                first_bin, count = F.emitter_bins(e, nfft)
-                rows_on = F.find_bursts(F.band_power(spec, first_bin, count).cpu(), count * noise, burst_threshold_db, min_rows, merge_rows)
-                on = [F.burst_pairs(a, z, nfft, nfft // 2, avg) for a, z in rows_on]
-                extra.update(bursts=on, duty=sum(z - a for a, z in rows_on) / spec.shape[0])
-                lo, hi = F._window_supports(np.arange(labels.shape[0]), hop, taps.size, L, D)
-                inside = np.zeros(labels.shape[0], bool)
-                for a, z in on:
-                    inside |= (lo >= a) & (hi < z)
-                labels.masked_fill_(torch.from_numpy(~inside).to(labels.device), -1)
-            open_ = labels[labels >= 0]
-            label = int(torch.bincount(open_).argmax()) if open_.numel() else -1
-            if as_numpy:
-                probs, labels, dbfs = probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy()
-            out.append(dict(centre=e.centre, bandwidth=e.bandwidth, power_dbfs=e.power_dbfs, snr_db=e.snr_db, shift=shift, interpolate=L, decimate=D,
-                            labels=labels, probs=probs, window_dbfs=dbfs, label=label, **extra))
-        return out
-
-    def detect_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_db: float = 6.0, floor: str = "flat", reach_rows: int = 2,
-                  reach_bins: int = 3, min_rows: int = 3, min_bins: int = 3, hop: int = 128, level: float = 7.8e-3,
-                  squelch_dbfs: Optional[float] = None, dc_guard: int = 1, batched: bool = False, refine: bool = False, min_line_db: float = 8.0,
-                  line_nfft: int = 1024, line_avg: int = 8):
-        """A wideband capture in, "what transmitted when, where, and what modulation" out: the scan in two dimensions, for
-        frequency hoppers, emitters that share bins at different times and single packets, which scan_iq's one-dimensional
-        searches miss or mangle.  The capture's spectrogram (frontend.spectrogram, as scan_iq builds it: nfft bins, segments nfft //
-        2 apart, `avg` per row) is thresholded per cell at frontend.detection_threshold(spec, threshold_db, dc_guard, floor) and
-        frontend.find_detections(spec, thresh, reach_rows, reach_bins, min_rows, min_bins, avg=avg) joins the on-cells into boxes
-        in time and frequency, all on the device.  Per detection, frontend.channel_plan(centre, bandwidth) and frontend.plan_taps
-        give (shift, L, D) and the filter, and ONLY the pairs [first_pair, stop_pair) of the capture go through frontend.ddc (L ==
-        1) or frontend.resample; the result is cut into windows `hop` output pairs apart (hop == 128: trimmed to whole frames)
-        and classified with predict_iq(..., "ci16", normalize="rms", level=, squelch_dbfs=, return_power=True).  Returns one dict
-        per detection, ordered by (first_pair, centre): the Detection's fields (first_row, stop_row, first_bin, stop_bin, cells,
-        centre, bandwidth, peak_db, snr_db, first_pair, stop_pair) plus shift, interpolate, decimate, probs, labels, window_dbfs
-        (device tensors, or numpy arrays for a numpy capture), windows, their number, and label, the most frequent label among the
-        windows the squelch let through (the smallest on a tie; -1 if there are none).  A detection whose pairs are too few for
-        one window gives windows = 0, label = -1 and empty results.  The default dc_guard of 1 switches bins -1, 0, +1 off, a gap
-        of three that reach_bins = 3 does not bridge: an emitter ON bin 0 comes out as two boxes, one each side of the guard.  A
-        capture without a DC spike takes dc_guard=0 (only bin 0 off) and gets it as one.
-        batched=True gives the same records, key for key and bit for bit, without the loop over detections: one
-        frontend.extract launch tunes, filters and resamples every detection's pairs into one block of whole frames, one
-        predict_iq classifies the block, frontend.segment_votes takes every detection's vote on the device, and the labels come to
-        the host in one transfer; probs, labels and window_dbfs are then slices of the block's results.  It needs hop == 128 (with
-        another hop windows would straddle detections: ValueError).
-        refine=True replaces the plan's two guesses per detection -- a symbol rate from the box's width, a carrier from its
-        centroid -- by the detection's spectral lines, scan_iq(refine=True)'s recipe on the detection's own pairs: D0 = clamp(floor(1
-        / (4 bandwidth)), 1, 256); iso = the pairs [first_pair, stop_pair) through frontend.ddc(shift=-centre, decimate=D0,
-        taps=frontend.plan_taps(1, D0)); b = bandwidth D0.  frontend.line_spectra(iso, "ci16", orders (0, 2, 4), nfft=line_nfft,
-        avg=line_avg) gives the three mean spectra, frontend.find_lines searches the envelope's in [b / 2.5, min(0.45, 1.25 b)] and,
-        with m = min(b / 8, 0.12), the square's in |f| <= 2 m and the fourth power's in |f| <= 4 m.  The symbol line counts from
-        min_line_db on (frontend.estimate_symbol_rate's rule); the carrier is order 2's line if it reaches min_line_db, else order
-        4's, else none (frontend.estimate_carrier_offset's rule).  shift = -(centre + offset / D0), folded into [-0.5, 0.5]; (L, D) =
-        frontend.resample_ratio(1.0, rate / D0, 8) when the symbol line was found and a ratio within its 1 % exists, else the plan's.
-        The record gains symbol_rate (cycles per input sample, or None), symbol_line_db, carrier_offset, carrier_order (2, 4, or 0)
-        and carrier_line_db; centre stays the centroid.  A detection too short for one row of line_avg segments of line_nfft
-        isolated pairs, or whose symbol band holds no bin at line_nfft, keeps the plan: symbol_rate None, symbol_line_db -inf,
-        carrier_offset 0.0, carrier_order 0, carrier_line_db -inf.  The loop does ddc, line_spectra (one job) and find_lines (three
-        bands) per detection; batched=True does ONE frontend.extract(..., whole_frames=False) for all isolations, ONE line_spectra
-        over the block, ONE find_lines whose 3 K records come to the host in one transfer, and then the extraction above with the
-        refined shifts and ratios: the same spectra from the same entries, so both forms agree bit for bit.  refine=False is the
-        plan alone, and its record has none of the five keys."""
-        torch = _torch()
-        from . import frontend as F
-        fmt = F.sample_format_id(sample_format)
-        if batched and hop != 128:
-            raise ValueError(f"batched=True needs hop == 128 (got {hop}): windows at another hop would straddle two detections")
-        as_numpy = not isinstance(iq, torch.Tensor)
-        dev = F._device_samples(iq, fmt, f"cuda:{self.device_index}")
-        spec = F.spectrogram(dev, fmt, nfft=nfft, avg=avg)
-        if spec.shape[0] == 0:
-            raise ValueError(f"the capture is too short for one row of {avg} segments of {nfft} pairs")
-        thresh = F.detection_threshold(spec, threshold_db, dc_guard, floor)
-        if batched:
-            found = F.find_detections(spec, thresh, reach_rows, reach_bins, min_rows, min_bins, avg=avg)
-            if not refine:
-                return self._classify_detections(dev, fmt, found, level, squelch_dbfs, as_numpy)
-            plans, extras = self._refine_detections(dev, fmt, found, min_line_db, line_nfft, line_avg)
-            return self._classify_detections(dev, fmt, found, level, squelch_dbfs, as_numpy, plans, extras)
-        per_pair = _cabi.IQ_PAIR_BYTES[fmt] // dev.element_size()      # elements of `dev` per (I,Q) pair
-        Cn = self.topology.classes
-        out = []
-        for d in F.find_detections(spec, thresh, reach_rows, reach_bins, min_rows, min_bins, avg=avg):
-            shift, L, D, _ = F.channel_plan(d.centre, d.bandwidth)
-            part = dev[d.first_pair * per_pair:d.stop_pair * per_pair]
-            extra = {}
-            if refine:
-                D0, bands = self._line_bands(d.bandwidth, line_nfft)
-                lines = None
-                if bands is not None:
-                    iso = F.ddc(part, fmt, shift=-d.centre, decimate=D0, taps=F.plan_taps(1, D0))
-                    means, rows = F.line_spectra(iso.reshape(-1), _cabi.IQ_CI16, [(0, iso.shape[0])], orders=(0, 2, 4), nfft=line_nfft, avg=line_avg)
-                    if rows[0] > 0:
-                        lines = F.find_lines(means[0], bands)
-                (shift, L, D), extra = self._refined_plan(d.centre, D0, (shift, L, D), lines, min_line_db)
-            taps = F.plan_taps(L, D)
-            if L == 1:
-                n_out = F.ddc_out_count(d.stop_pair - d.first_pair, taps.size, D)
-            else:
-                n_out = F.resample_out_count(d.stop_pair - d.first_pair, taps.size, L, D)
-            if n_out < 128:
-                probs = torch.empty((0, Cn), dtype=torch.float32, device=dev.device)
-                labels = torch.empty((0,), dtype=torch.int32, device=dev.device)
-                dbfs = torch.empty((0,), dtype=torch.float64, device=dev.device)
-            else:
-                if L == 1:
-                    down = F.ddc(part, fmt, shift=shift, decimate=D, taps=taps)
-                else:
-                    down = F.resample(part, fmt, shift=shift, interpolate=L, decimate=D, taps=taps)
-                if hop == 128:
-                    down = down[:down.shape[0] // 128 * 128]
-                probs, labels, dbfs = self.predict_iq(down.reshape(-1), _cabi.IQ_CI16, hop=hop, normalize="rms", level=level,
-                                                      squelch_dbfs=squelch_dbfs, return_power=True)
-            open_ = labels[labels >= 0]
-            label = int(torch.bincount(open_).argmax()) if open_.numel() else -1
-            windows = int(labels.shape[0])
-            if as_numpy:
-                probs, labels, dbfs = probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy()
-            out.append(dict(d._asdict(), shift=shift, interpolate=L, decimate=D, probs=probs, labels=labels, window_dbfs=dbfs, windows=windows,
-                            label=label, **extra))
-        return out
-
-    @staticmethod
-    def _line_bands(bandwidth, line_nfft):
-        """detect_iq(refine=True): (D0, bands) of a detection of that bandwidth -- the isolating decimation and the three bands of
-        frontend.find_lines (envelope, square, fourth power) at its isolated rate; bands is None when the envelope's band holds
-        no bin of line_nfft"""
-        D0 = min(max(int(1.0 / (4.0 * bandwidth)), 1), 256)
-        b = bandwidth * D0
-        lo, hi = b / 2.5, min(0.45, 1.25 * b)
-        f = np.fft.fftfreq(int(line_nfft))
-        if not np.any((f >= lo) & (f <= hi)):
-            return D0, None
-        m = min(b / 8.0, 0.12)
-        return D0, [(lo, hi, False), (0.0, 2.0 * m, True), (0.0, 4.0 * m, True)]
-
-    @staticmethod
-    def _refined_plan(centre, D0, plan, lines, min_line_db):
-        """detect_iq(refine=True): ((shift, L, D), the record's five extra keys) from find_lines' three results at orders 0, 2, 4
-        of the detection isolated at decimation D0 (lines None: no spectrum, the plan stands) -- the decisions of
-        frontend.estimate_symbol_rate and frontend.estimate_carrier_offset, and scan_iq(refine=True)'s use of them"""
-        from . import frontend as F
-        if lines is None:
-            return plan, dict(symbol_rate=None, symbol_line_db=float("-inf"), carrier_offset=0.0, carrier_order=0, carrier_line_db=float("-inf"))
-        shift, L, D = plan
-        (rate, rate_db), (f2, db2), (f4, db4) = lines
-        if rate_db < float(min_line_db):
-            rate = None
-        if db2 >= float(min_line_db):
-            offset, order, offset_db = f2 / 2, 2, db2
-        elif db4 >= float(min_line_db):
-            offset, order, offset_db = f4 / 4, 4, db4
-        else:
-            offset, order, offset_db = 0.0, 0, max(db2, db4)
-        shift = -(centre + offset / D0)
-        if abs(shift) > 0.5:      # a detection at the band's edge: the same frequency, one turn on
-            shift -= round(shift)
-        if rate is not None:
-            try:
-                L, D, _ = F.resample_ratio(1.0, rate / D0, 8)
-            except ValueError:      # nothing within 1 %: the plan's ratio stands
-                pass
-        return (shift, L, D), dict(symbol_rate=None if rate is None else rate / D0, symbol_line_db=rate_db, carrier_offset=offset / D0,
-                                   carrier_order=order, carrier_line_db=offset_db)
-
-    def _refine_detections(self, dev, fmt, found, min_line_db, line_nfft, line_avg):
-        """detect_iq(batched=True, refine=True) before the extraction: (plans, extras) of all detections from one frontend.extract
-        of their isolations, one frontend.line_spectra over that block and one frontend.find_lines"""
-        from . import frontend as F
-        plans = [p[:3] for p in F.channel_plans([(d.centre, d.bandwidth) for d in found])]
-        if not found:
-            return plans, []
-        geo = [self._line_bands(d.bandwidth, line_nfft) for d in found]
-        taps = {}
-        for D0, _ in geo:
-            if D0 not in taps:
-                taps[D0] = F.plan_taps(1, D0)
-        block, offsets = F.extract(dev, fmt, [(d.first_pair, d.stop_pair, -d.centre, 1, D0, taps[D0]) for d, (D0, _) in zip(found, geo)],
-                                   whole_frames=False)
-        means, rows = F.line_spectra(block.reshape(-1), _cabi.IQ_CI16, offsets, orders=(0, 2, 4), nfft=line_nfft, avg=line_avg)
-        live = [k for k, (_, bands) in enumerate(geo) if bands is not None and rows[k] > 0]
-        lines = {}
-        if live:
-            at = _torch().as_tensor(live, dtype=_torch().int64, device=means.device)
-            got = F.find_lines(means[at].reshape(-1, means.shape[2]), [band for k in live for band in geo[k][1]])
-            lines = {k: got[3 * i:3 * i + 3] for i, k in enumerate(live)}
-        out = [self._refined_plan(d.centre, D0, plan, lines.get(k), min_line_db) for k, (d, (D0, _), plan) in enumerate(zip(found, geo, plans))]
-        return [p for p, _ in out], [e for _, e in out]
-
-    def _classify_detections(self, dev, fmt, found, level, squelch_dbfs, as_numpy, plans=None, extras=None):
-        """detect_iq(batched=True) behind the search: the records of `found` (frontend.find_detections) on the device capture dev;
-        plans: (shift, L, D) per detection, None = frontend.channel_plans'; extras: per detection, further keys of its record"""
-        torch = _torch()
-        from . import frontend as F
-        if not found:
-            return []
-        Cn = self.topology.classes
-        if plans is None:
-            plans = [p[:3] for p in F.channel_plans([(d.centre, d.bandwidth) for d in found])]
-        taps = {}
-        for _, L, D in plans:
-            if (L, D) not in taps:
-                taps[L, D] = F.plan_taps(L, D)
-        block, offsets = F.extract(dev, fmt, [(d.first_pair, d.stop_pair, shift, L, D, taps[L, D]) for d, (shift, L, D) in zip(found, plans)],
-                                   whole_frames=True)
-        first = (offsets // 128).tolist()      # in windows
-        if block.shape[0]:
-            probs, labels, dbfs = self.predict_iq(block.reshape(-1), _cabi.IQ_CI16, normalize="rms", level=level, squelch_dbfs=squelch_dbfs,
-                                                  return_power=True)
-        else:
-            probs = torch.empty((0, Cn), dtype=torch.float32, device=dev.device)
-            labels = torch.empty((0,), dtype=torch.int32, device=dev.device)
-            dbfs = torch.empty((0,), dtype=torch.float64, device=dev.device)
-        label = F.segment_votes(labels, offsets // 128, Cn).cpu().tolist()      # the one transfer of the K labels
-        if as_numpy:
-            probs, labels, dbfs = probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy()
-        out = []
-        for k, (d, (shift, L, D)) in enumerate(zip(found, plans)):
-            a, z = first[k], first[k + 1]
-            out.append(dict(d._asdict(), shift=shift, interpolate=L, decimate=D, probs=probs[a:z], labels=labels[a:z], window_dbfs=dbfs[a:z],
-                            windows=z - a, label=label[k], **(extras[k] if extras else {})))
-        return out
-
-    def predict_channels(self, iq, sample_format, channels: int, decimate: Optional[int] = None, taps=None, tap_shift: Optional[int] = None,
-                         hop: int = 128, level: float = 7.8e-3, squelch_dbfs: Optional[float] = None, batch_size: int = 0):
-        """A band with a channel raster in, "what is on every channel" out.  The capture is split into M = channels evenly spaced
-        channels in one pass (frontend.channelize(iq, sample_format, channels, decimate, taps, tap_shift, whole_frames=True):
-        decimate=None is M / 2, taps=None frontend.design_channelizer(M)), and every channel's stream is cut into windows `hop`
-        output pairs apart and classified with predict_iq(..., "ci16", normalize="rms", level=, squelch_dbfs=, return_power=True).
-        With hop == 128 that is ONE predict_iq call over the flat (M * n_out) block: the rows are whole frames, so no window
-        straddles two channels; other hops go channel by channel.  Returns probs (M, W, C), labels (M, W), window_dbfs (M, W) and
-        label (M,), int64: per channel the most frequent label among the windows the squelch let through (the smallest on a tie;
-        -1 if there are none) -- scan_iq's rule.  Row k is the channel centred at frontend.channel_freqs(M)[k].  Device tensors
-        for a device capture, numpy arrays for a numpy capture."""
-        torch = _torch()
-        from . import frontend as F
-        fmt = F.sample_format_id(sample_format)
-        as_numpy = not isinstance(iq, torch.Tensor)
-        down = F.channelize(iq, fmt, channels, decimate=decimate, taps=taps, tap_shift=tap_shift, whole_frames=True,
-                            device=f"cuda:{self.device_index}")
-        M, n_out = down.shape[0], down.shape[1]
-        kw = dict(batch_size=batch_size, hop=hop, normalize="rms", level=level, squelch_dbfs=squelch_dbfs, return_power=True)
-        if hop == 128:
-            probs, labels, dbfs = self.predict_iq(down.view(-1), _cabi.IQ_CI16, **kw)
-            W = n_out // 128
-            probs, labels, dbfs = probs.view(M, W, self.topology.classes), labels.view(M, W), dbfs.view(M, W)
-        else:
-            per = [self.predict_iq(down[k].reshape(-1), _cabi.IQ_CI16, **kw) for k in range(M)]
-            probs, labels, dbfs = (torch.stack([p[i] for p in per]) for i in range(3))
-        classes = torch.arange(self.topology.classes, dtype=labels.dtype, device=labels.device)
-        counts = (labels[:, :, None] == classes).sum(1)      # (M, C): squelched windows (-1) count for no class
-        label = torch.where(counts.sum(1) > 0, counts.argmax(1), torch.full((M,), -1, dtype=torch.int64, device=labels.device))
-        if as_numpy:
-            return probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy(), label.cpu().numpy()
-        return probs, labels, dbfs, label
+    # ------------------------------------------------------------------ wideband captures (capture.py: functions of a model)
+    scan_iq = capture.scan_iq
+    detect_iq = capture.detect_iq
+    predict_channels = capture.predict_channels
 
     # ------------------------------------------------------------------ measurement hooks
     def set_profiling(self, on: bool) -> None:

@@ -18,7 +18,7 @@ import iq_components_ref as CR
 import iq_ddc_ref as D
 import iq_line_ref as R
 import iq_spectrum_ref as S
-from modulationdetectioncnn_amd import VTCNN2, _cabi, frontend
+from modulationdetectioncnn_amd import _cabi, capture, frontend
 
 JOB, BAND = _cabi.IQ_LINE_JOB, _cabi.IQ_LINE_BAND
 EINVAL = -22
@@ -216,7 +216,7 @@ def test_refinement_rule_on_the_reference_spectra_of_the_hopper():
     for d, (first, stop, centre, _) in zip(found, truth):
         plan = frontend.channel_plan(d.centre, d.bandwidth)[:3]
         assert plan[1:] in ((14, 59), (25, 108))                       # the width's guess: 7.59 or 7.41 samples per symbol
-        D0, bands = VTCNN2._line_bands(d.bandwidth, nfft)
+        D0, bands = capture._line_bands(d.bandwidth, nfft)
         assert D0 == min(max(int(1.0 / (4.0 * d.bandwidth)), 1), 256) and bands is not None
         part = iq[2 * d.first_pair:2 * d.stop_pair]
         iso = D.ddc(part, "ci16", 0, frontend.phase_step(-d.centre), D0, frontend.plan_taps(1, D0)).reshape(-1)
@@ -225,7 +225,7 @@ def test_refinement_rule_on_the_reference_spectra_of_the_hopper():
             rows = R.line_spectrum(iso, "ci16", order, nfft, nfft // 2, avg, w, scale)[0]
             assert rows.shape[0] >= 1
             lines.append(frontend.find_line(_mean_in_row_order(rows), *band))
-        (shift, L, Dn), extra = VTCNN2._refined_plan(d.centre, D0, plan, lines, 8.0)
+        (shift, L, Dn), extra = capture._refined_plan(d.centre, D0, plan, lines, 8.0)
         assert (L, Dn) == (1, 4)
         assert extra["symbol_rate"] is not None and abs(extra["symbol_rate"] * CR.HOP_SPS - 1.0) <= 1e-3, extra
         assert extra["symbol_line_db"] >= 8.0 and extra["symbol_line_db"] == lines[0][1]
@@ -234,12 +234,12 @@ def test_refinement_rule_on_the_reference_spectra_of_the_hopper():
         folded = -(d.centre + extra["carrier_offset"])
         assert shift == (folded - round(folded) if abs(folded) > 0.5 else folded) and abs(shift) <= 0.5
         # a bar the lines do not reach: the plan stands, the centroid stands, the prominences are still reported
-        kept, none = VTCNN2._refined_plan(d.centre, D0, plan, lines, 99.0)
+        kept, none = capture._refined_plan(d.centre, D0, plan, lines, 99.0)
         assert kept[1:] == plan[1:] and none["symbol_rate"] is None and none["carrier_order"] == 0 and none["carrier_offset"] == 0.0
         assert none["symbol_line_db"] == lines[0][1] and none["carrier_line_db"] == max(lines[1][1], lines[2][1])
     # no spectrum at all (too short for a row, or no bin in the band): the plan, and the five keys say so
     plan = (-0.1, 5, 6)
-    kept, none = VTCNN2._refined_plan(0.1, 3, plan, None, 8.0)
+    kept, none = capture._refined_plan(0.1, 3, plan, None, 8.0)
     assert kept == plan and none == dict(symbol_rate=None, symbol_line_db=float("-inf"), carrier_offset=0.0, carrier_order=0,
                                          carrier_line_db=float("-inf"))
-    assert VTCNN2._line_bands(1e-5, 64) == (256, None)      # b = 0.00256: the band 0.001 .. 0.0032 lies below the first bin of 64
+    assert capture._line_bands(1e-5, 64) == (256, None)      # b = 0.00256: the band 0.001 .. 0.0032 lies below the first bin of 64
