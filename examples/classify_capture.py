@@ -53,6 +53,14 @@ one pass instead (frontend.channelize, a polyphase filter bank on the device; VT
 
     python examples/classify_capture.py capture.bin --format ci16 --rate 2.4e6 --channels 16
 
+An uncalibrated zero-IF receiver (HackRF, bladeRF, USRP, an RTL-SDR with a direct-conversion tuner) mirrors every emitter at +f
+to -f, 20 .. 40 dB down, and --scan, --detections and --channels then list a strong emitter's image as an emitter.  --balance
+removes the receiver's DC offset and I/Q imbalance first, estimated from the capture itself (frontend.balance, exact integers on
+the device), and --scan prints the image rejection it found:
+
+    python examples/classify_capture.py capture.bin --format ci8 --scan --balance
+    python examples/classify_capture.py --format ci16 --scan --imbalance [--balance]      # the synthetic band 1 dB / 5 degrees off: 4 lines, 3 with --balance
+
 Without a capture file it classifies a synthetic one: bursts of tones at three gains with silence between them (--scan: a
 band of three QPSK emitters of different widths over noise and a DC offset, with --bursts a fourth that is on 4.5 % of the time; --detections: a QPSK hopper of six dwells and a second emitter on an
 earlier dwell's bins; --channels: QPSK on two channels of the raster)."""
@@ -88,11 +96,19 @@ def synthetic_capture(fmt="cu8", seed=1):
     return np.clip(np.rint(iq), lo, hi).astype(DTYPES[fmt]).reshape(-1)
 
 
-def synthetic_band(fmt="ci16", seed=1, pairs=1 << 18, bursty=False):
+BAND_EMITTERS = ((96, -0.31, 0.02), (48, 0.12, 0.05), (20, 0.36, 0.01))      # samples per symbol, centre, rms of full scale
+# the band as an uncalibrated zero-IF receiver delivers it (--imbalance): the Q rail 1 dB up and 5 degrees off, which mirrors every
+# emitter 22.8 dB down.  The emitter at -0.31 is weaker here, so that only the strong one's image, at -0.12, clears the threshold
+IMBALANCED_EMITTERS = ((96, -0.31, 0.004), (48, 0.12, 0.05), (20, 0.36, 0.01))
+IMBALANCE = (1.0, 5.0)
+
+
+def synthetic_band(fmt="ci16", seed=1, pairs=1 << 18, bursty=False, emitters=BAND_EMITTERS, imbalance=None):
     """Three QPSK emitters with a root-raised-cosine pulse (beta 0.35) at 96 / 48 / 20 samples per symbol, centred at -0.31 / +0.12 /
     +0.36 cycles per sample with rms 0.02 / 0.05 / 0.01 of full scale, over noise of rms 0.002 and a tuner's DC offset.  bursty: a
     fourth one at 32 samples per symbol, centred at -0.08 with rms 0.003, that is on only during [0.40, 0.43) and [0.80, 0.815)
-    of the capture."""
+    of the capture.  emitters: other (samples per symbol, centre, rms) triples; imbalance: (gain in dB, phase in degrees) of the
+    receiver's Q rail against its I rail, applied to signals and noise before the DC offset and the quantiser."""
     rng = np.random.default_rng(seed)
     beta, n, z = 0.35, np.arange(pairs), np.zeros(pairs, complex)
 
@@ -111,28 +127,36 @@ def synthetic_band(fmt="ci16", seed=1, pairs=1 << 18, bursty=False):
             base = base * gate
         return base * np.exp(2j * np.pi * fc * n)
 
-    for sps, fc, amp in ((96, -0.31, 0.02), (48, 0.12, 0.05), (20, 0.36, 0.01)):
+    for sps, fc, amp in emitters:
         z += emitter(rng, sps, fc, amp)
     if bursty:      # symbols from a stream of its own: the draws of everything else stay what they are
         z += emitter(np.random.default_rng(seed + 100), 32, -0.08, 0.003, on=((0.40, 0.43), (0.80, 0.815)))
-    z += 0.002 / np.sqrt(2) * (rng.standard_normal(pairs) + 1j * rng.standard_normal(pairs)) + (0.01 - 0.02j)
+    z += 0.002 / np.sqrt(2) * (rng.standard_normal(pairs) + 1j * rng.standard_normal(pairs))
+    if imbalance is not None:      # I = Re z, Q = g Im(e^{-j phi} z)
+        g, phi = 10.0 ** (imbalance[0] / 20.0), np.radians(imbalance[1])
+        z = z.real + 1j * g * (z.imag * np.cos(phi) - z.real * np.sin(phi))
+    z += 0.01 - 0.02j
     if fmt == "cu8":
         return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * 127.5 + 127.5), 0, 255).astype(np.uint8).reshape(-1)
     full, lo, hi = (128.0, -128, 127) if fmt == "ci8" else (32768.0, -32768, 32767)
     return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * full), lo, hi).astype(DTYPES[fmt]).reshape(-1)
 
 
-def scan(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0, refine=False, bursts=False, hold=0.98):
+def scan(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0, refine=False, bursts=False, hold=0.98,
+         balance=False):
     """Print one line per emitter of the capture (VTCNN2.scan_iq) and return the records.  rate: Hz columns instead of cycles per sample.
     refine: symbol rate and carrier from the emitter's spectral lines (scan_iq's refine=True), as two more columns -- the symbol
     rate ("-" where no line was found) and the refined centre.  bursts: the scan for intermittent emitters (scan_iq's bursts=True
     on the `hold` quantile spectrum, spectrogram rows of 2 segments), as two more columns -- the number of bursts and the share of
-    the rows the emitter was on."""
+    the rows the emitter was on.  balance: correct the receiver's DC offset and I/Q imbalance first (scan_iq's balance=True), and
+    print the capture's image rejection before the correction."""
     more = dict(bursts=True, hold=hold, avg=2) if bursts else {}
+    if balance:
+        more["balance"] = True
     found = model.scan_iq(iq[:iq.size // 2 * 2], fmt, nfft=nfft, threshold_db=threshold_db, hop=hop, level=level, squelch_dbfs=squelch,
                           refine=refine, **more)
     k, unit = (rate, "Hz") if rate else (1.0, "cyc/sample")
-    print(f"{len(found)} emitters ({unit})")
+    print(f"{len(found)} emitters ({unit})" + (f", image rejection before correction {found[0]['image_rejection_db']:.1f} dB" if balance and found else ""))
     print(f"{'centre':>12s} {'bandwidth':>12s} {'dBFS':>7s} {'SNR dB':>7s} {'L/D':>7s} {'windows':>8s} {'open':>6s} {'label':>6s}"
           + (f" {'symbol rate':>12s} {'refined':>12s}" if refine else "") + (f" {'bursts':>7s} {'duty':>6s}" if bursts else ""))
     for e in found:
@@ -171,13 +195,17 @@ def synthetic_hopper(fmt="ci16", seed=1, pairs=1 << 19):
     return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * full), lo, hi).astype(DTYPES[fmt]).reshape(-1)
 
 
-def detections(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0, batched=False, refine=False):
+def detections(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0, batched=False, refine=False,
+               balance=False):
     """Print one line per detection of the capture (VTCNN2.detect_iq: boxes in time and frequency) and return the records: the
     box's span in input pairs, centre and width (Hz with rate, else cycles per sample), the peak over the threshold, the plan and
     the label.  batched: all boxes in one extraction launch and one forward (needs hop == 128); the same records.  refine: symbol
     rate and carrier from each box's spectral lines (detect_iq's refine=True), as two more columns -- the symbol rate ("-" where no
-    line was found) and the refined centre."""
+    line was found) and the refined centre.  balance: correct the receiver's DC offset and I/Q imbalance first (detect_iq's
+    balance=True)."""
     more = dict(refine=True) if refine else {}
+    if balance:
+        more["balance"] = True
     found = model.detect_iq(iq[:iq.size // 2 * 2], fmt, nfft=nfft, threshold_db=threshold_db, hop=hop, level=level, squelch_dbfs=squelch,
                             batched=batched, **more)
     k, unit = (rate, "Hz") if rate else (1.0, "cyc/sample")
@@ -215,11 +243,13 @@ def synthetic_raster(fmt="ci16", channels=16, seed=1, pairs=1 << 16):
     return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) * full), lo, hi).astype(DTYPES[fmt]).reshape(-1)
 
 
-def channels(model, iq, fmt, nchannels, rate=None, hop=128, level=7.8e-3, squelch=-60.0):
+def channels(model, iq, fmt, nchannels, rate=None, hop=128, level=7.8e-3, squelch=-60.0, balance=False):
     """Print one line per channel of the raster (VTCNN2.predict_channels: M = nchannels channels, each 2 x oversampled) and return
-    (labels, window dBFS, label per channel).  rate: the centres in Hz instead of cycles per sample."""
+    (labels, window dBFS, label per channel).  rate: the centres in Hz instead of cycles per sample.  balance: correct the
+    receiver's DC offset and I/Q imbalance first (predict_channels' balance=True)."""
     from modulationdetectioncnn_amd import frontend
-    _, labels, dbfs, label = model.predict_channels(iq[:iq.size // 2 * 2], fmt, nchannels, hop=hop, level=level, squelch_dbfs=squelch)
+    more = dict(balance=True) if balance else {}
+    _, labels, dbfs, label = model.predict_channels(iq[:iq.size // 2 * 2], fmt, nchannels, hop=hop, level=level, squelch_dbfs=squelch, **more)
     k, unit = (rate, "Hz") if rate else (1.0, "cyc/sample")
     print(f"{nchannels} channels ({unit}), {labels.shape[1]} windows each")
     print(f"{'centre':>12s} {'median dBFS':>12s} {'open':>6s} {'label':>6s}")
@@ -295,6 +325,11 @@ def main():
                          "time and frequency; uses --nfft and --threshold")
     ap.add_argument("--batched", action="store_true",
                     help="with --detections: extract all boxes in one launch and classify them in one forward (the same lines; needs --hop 128)")
+    ap.add_argument("--balance", action="store_true",
+                    help="with --scan, --detections or --channels: remove the receiver's DC offset and I/Q imbalance, estimated from the "
+                         "capture, first (an uncalibrated zero-IF receiver lists every strong emitter's mirror image as an emitter)")
+    ap.add_argument("--imbalance", action="store_true",
+                    help="with --scan and no capture file: the synthetic band as a receiver 1 dB / 5 degrees out of balance delivers it")
     a = ap.parse_args()
     if a.detections:
         iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_hopper(a.format)
@@ -303,7 +338,7 @@ def main():
         else:
             model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
         detections(model, iq, a.format, nfft=a.nfft, threshold_db=a.threshold, rate=a.rate if a.rate != 1.0 else None, hop=a.hop, level=a.level,
-                   squelch=a.squelch, batched=a.batched, refine=a.refine)
+                   squelch=a.squelch, batched=a.batched, refine=a.refine, balance=a.balance)
         return
     if a.channels:
         iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_raster(a.format, a.channels)
@@ -311,16 +346,18 @@ def main():
             model = VTCNN2.synthetic("deployed3")
         else:
             model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
-        channels(model, iq, a.format, a.channels, rate=a.rate if a.rate != 1.0 else None, hop=a.hop, level=a.level, squelch=a.squelch)
+        channels(model, iq, a.format, a.channels, rate=a.rate if a.rate != 1.0 else None, hop=a.hop, level=a.level, squelch=a.squelch,
+                 balance=a.balance)
         return
     if a.scan:
-        iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else synthetic_band(a.format, bursty=a.bursts)
+        iq = np.fromfile(a.capture, DTYPES[a.format]) if a.capture else (
+            synthetic_band(a.format, bursty=a.bursts, emitters=IMBALANCED_EMITTERS, imbalance=IMBALANCE) if a.imbalance else synthetic_band(a.format, bursty=a.bursts))
         if a.weights is None:
             model = VTCNN2.synthetic("deployed3")
         else:
             model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
         scan(model, iq, a.format, nfft=a.nfft, threshold_db=a.threshold, rate=a.rate if a.rate != 1.0 else None, hop=a.hop, level=a.level,
-             squelch=a.squelch, refine=a.refine, bursts=a.bursts, hold=a.hold)
+             squelch=a.squelch, refine=a.refine, bursts=a.bursts, hold=a.hold, balance=a.balance)
         return
     if a.symbol_rate is not None:
         from modulationdetectioncnn_amd import frontend

@@ -65,7 +65,9 @@ extern "C" {
                                   mdc_iq_extract_filter (K stretches of a capture through mdc_iq_resample's chain in one launch);
                                   mdc_iq_line_spectra / mdc_iq_line_spectra_rows, mdc_iq_line_job (the line spectra of K stretches
                                   at several orders, and their float64 means, in one call); mdc_iq_find_lines, mdc_iq_line_band,
-                                  mdc_iq_line_record (the line search of S spectra on the device) */
+                                  mdc_iq_line_record (the line search of S spectra on the device);
+                                  mdc_iq_balance / mdc_iq_balance_stats / mdc_iq_balance_blocks, mdc_iq_balance_coeffs (a
+                                  receiver's I/Q imbalance and DC offset, measured and corrected in exact integers) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -367,6 +369,50 @@ typedef struct mdc_iq_window_stats64 {   /* 32 B */
 MDC_API int mdc_iq_windows(const void* iq_dev, int format, int64_t n, int64_t hop, float scale, float* x_dev, void* hip_stream);
 MDC_API int mdc_iq_windows_norm(const void* iq_dev, int format, int64_t n, int64_t hop, float level, int flags,
                            float* x_dev, mdc_iq_window_stats64* stats64_dev, void* hip_stream);
+
+/* ---- I/Q balance: a receiver's gain / phase imbalance and DC offset, measured and corrected (additive in ABI 5) -----------------
+ * A zero-IF receiver's I and Q rails differ in gain by a fraction of a dB to a dB and are a few degrees off 90: every emitter
+ * at +f then has a mirror image at -f, 20 .. 40 dB below it (1 dB and 5 degrees: 22.83 dB), which a detector 6 dB above the
+ * floor reports as an emitter of its own.  mdc_iq_balance_stats measures, the caller designs six integers on the host, and
+ * mdc_iq_balance applies them: all in EXACT integer arithmetic (the numpy int64 restatement is tests/iq_balance_ref.py), the
+ * result an ordinary MDC_IQ_CI16 stream for every other mdc_iq_* entry.  Normatively, with (x_n, y_n) the widened I and Q of
+ * input pair n -- the widening is mdc_iq_ddc's, below --:
+ *   statistics  the capture is cut into blocks of B = block_pairs pairs, 64 <= B <= 2^20, ANY integer in between (an odd B puts
+ *               blocks on odd pairs); block b covers the pairs [b B, min((b + 1) B, pairs_in)), the last one may be partial:
+ *               nblocks = ceil(pairs_in / B) = mdc_iq_balance_blocks.  Per block five int64 sums, in this order:
+ *               sum x, sum y, sum x^2, sum y^2, sum x y; sums_dev is nblocks x 5, block-major.  |sum x^2| <= 2^20 * 2^30:
+ *               every sum is exact, so any order of summation gives the same bits.  The whole capture's sums are the blocks'
+ *               sums added on the host; a caller may leave blocks out (a stretch where a strong real-valued emitter sits on
+ *               0 Hz), or compare blocks to see the imbalance drift.
+ *   design      (host; the library's Python mirror has one: frontend.design_balance) dc = the means of x and y, rounded;
+ *               M = sqrt(tr C / 2) C^(-1/2), C the covariance of (x, y): the symmetric whitening matrix, which equalises the
+ *               rails, makes them orthogonal, keeps the total power and does not rotate; m_ij = rint(16384 M_ij), Q14.
+ *   correction  a = x - dc_i, b = y - dc_q;
+ *               out_I = clamp((m00 a + m01 b + 8192) >> 14, -32768, 32767), out_Q likewise with m10, m11 (arithmetic
+ *               shift: round half up).  Hard preconditions: |dc_i|, |dc_q| <= 32768 and |m_i0| + |m_i1| <= 32767 per row.
+ *               Then |a|, |b| <= 32768 + 32768 = 65536, |m_i0 a + m_i1 b| <= 32767 * 65536 = 2^31 - 65536, and + 8192 stays
+ *               below 2^31: 32-bit accumulation is exact.  The identity is (0, 0, 16384, 0, 0, 16384): MDC_IQ_CI16 comes out
+ *               as it went in, the 8-bit formats come out widened.  A general matrix also expresses the I/Q swap of a
+ *               wrongly wired capture (spectrum inversion), (0, 16384, 16384, 0), and conjugation, (16384, 0, 0, -16384).
+ *   output      pairs_in int16 pairs.  The pass is pointwise: a capture corrected in pieces gives the same bits as in one call.
+ * The estimate is BLIND: it takes the capture as a whole to be proper, E[z^2] = 0.  Any mix of emitters away from 0 Hz and
+ * from half the rate is (a BPSK at f0 turns at 2 f0 and averages out); a dominant real-valued modulation (BPSK, PAM, AM-DSB)
+ * centred exactly on 0 Hz is not, and is taken for imbalance: leave its blocks out, or pass coefficients measured elsewhere.
+ * The imbalance is taken as flat over the band: one matrix, no frequency dependence.
+ * iq_dev is aligned to one pair (2 / 2 / 4 bytes), sums_dev to 8 bytes, out_dev to 4 bytes; out_dev must not overlap the input.
+ * coeffs_host is read (and validated) during the call and travels with the launch.  nblocks must equal
+ * mdc_iq_balance_blocks.  Every argument error is MDC_EINVAL before any device call; pairs_in == 0 is MDC_OK with nothing
+ * launched.  Both calls only enqueue on hip_stream (no synchronisation, no allocation: capturable in a hipGraph) and run on
+ * the current device.  mdc_iq_balance_blocks returns nblocks, or a negative MDC_EINVAL. */
+typedef struct mdc_iq_balance_coeffs {   /* 24 B */
+    int32_t dc_i, dc_q;             /* subtracted from the widened I and Q */
+    int32_t m00, m01, m10, m11;     /* Q14 */
+} mdc_iq_balance_coeffs;
+MDC_API int64_t mdc_iq_balance_blocks(int64_t pairs_in, int64_t block_pairs);
+MDC_API int mdc_iq_balance_stats(const void* iq_dev, int format, int64_t pairs_in, int64_t block_pairs,
+                           int64_t* sums_dev /* nblocks x 5 */, int64_t nblocks, void* hip_stream);
+MDC_API int mdc_iq_balance(const void* iq_dev, int format, int64_t pairs_in, const mdc_iq_balance_coeffs* coeffs_host,
+                           int16_t* out_dev, void* hip_stream);
 
 /* ---- digital down-converter: frequency shift, low-pass, decimate (additive in ABI 5) ---------------------------------------
  * A capture comes off the radio at its own rate and with the signal at some offset from the tuner's centre; the nets want

@@ -42,6 +42,7 @@ EXPORTS = [
     "mdc_iq_spectrum_quantiles",
     "mdc_iq_spectrogram_components", "mdc_iq_spectrogram_components_workspace",
     "mdc_iq_line_spectra", "mdc_iq_line_spectra_rows", "mdc_iq_find_lines",
+    "mdc_iq_balance", "mdc_iq_balance_stats", "mdc_iq_balance_blocks",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
@@ -76,6 +77,12 @@ IQ_ENTRIES = IqWindowEntries("mdc_iq_windows", "mdc_iq_windows_norm", "mdc_predi
 # mdc_iq_ddc: limits of include/mdc.h, and the kernel's tiling (csrc/iq_ddc.hip: kDdcTilePairs, kDdcGridCap) for tests and tools
 DDC_MAX_DECIMATE, DDC_MAX_TAPS, DDC_MAX_TAPS_ABS_SUM, DDC_NCO_ENTRIES = 256, 1024, 65535, 4096
 DDC_TILE_PAIRS, DDC_GRID_CAP = 8192, 1024
+# mdc_iq_balance_stats / mdc_iq_balance: limits of include/mdc.h, the coefficient record (mdc_iq_balance_coeffs, 24 B), and the
+# kernels' grids (csrc/iq_balance.hip: kBalStatsGridCap blocks in flight; kBalGridCap work-groups of BALANCE_GROUP_PAIRS pairs)
+BALANCE_MIN_BLOCK, BALANCE_MAX_BLOCK = 64, 1 << 20
+BALANCE_MAX_DC, BALANCE_MAX_ROW_ABS_SUM, BALANCE_ONE = 32768, 32767, 16384
+BALANCE_STATS_GRID_CAP, BALANCE_GRID_CAP, BALANCE_GROUP_PAIRS = 2048, 2048, 1024
+IQ_BALANCE_COEFFS = np.dtype([("dc_i", np.int32), ("dc_q", np.int32), ("m00", np.int32), ("m01", np.int32), ("m10", np.int32), ("m11", np.int32)])
 # mdc_iq_resample: limits of include/mdc.h (taps and decimation as the DDC's; the sum |h| bound holds per BRANCH), and the kernel's
 # tiling (csrc/iq_resample.hip): a tile is ((RESAMPLE_TILE_PAIRS - ceil(T / L)) // D) * L outputs, RESAMPLE_GRID_CAP work-groups
 RESAMPLE_MAX_INTERPOLATE, RESAMPLE_MAX_DECIMATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BRANCH_ABS_SUM = 32, 256, 1024, 65535
@@ -210,12 +217,16 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_iq_spectrum_quantiles", [vp, i64, i32, vp, i32, vp, vp]),
                        ("mdc_iq_spectrogram_components", [vp, i64, i32, vp, i32, i32, vp, vp, i64, vp, vp, vp]),
                        ("mdc_iq_line_spectra", [vp, i32, i64, vp, vp, i64, vp, i32, i32, i64, i32, vp, C.c_float, vp, i64, vp, vp]),
-                       ("mdc_iq_find_lines", [vp, i64, i32, vp, vp, vp, vp])):
+                       ("mdc_iq_find_lines", [vp, i64, i32, vp, vp, vp, vp]),
+                       ("mdc_iq_balance_stats", [vp, i32, i64, i64, vp, i64, vp]),
+                       ("mdc_iq_balance", [vp, i32, i64, vp, vp, vp])):
         fn = getattr(L, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, i32
     if getattr(L, "mdc_iq_ddc_out_count", None) is not None:
         L.mdc_iq_ddc_out_count.argtypes, L.mdc_iq_ddc_out_count.restype = [i64, i32, i32], i64
+    if getattr(L, "mdc_iq_balance_blocks", None) is not None:
+        L.mdc_iq_balance_blocks.argtypes, L.mdc_iq_balance_blocks.restype = [i64, i64], i64
     if getattr(L, "mdc_iq_resample_out_count", None) is not None:
         L.mdc_iq_resample_out_count.argtypes, L.mdc_iq_resample_out_count.restype = [i64, i32, i32, i32], i64
     if getattr(L, "mdc_iq_extract_plan_bytes", None) is not None:

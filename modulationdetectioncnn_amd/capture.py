@@ -21,6 +21,17 @@ def _tuned(dev, fmt, shift, L, D, taps, hop):
     return down[:down.shape[0] // 128 * 128] if hop == 128 else down
 
 
+def _capture(iq, fmt, balance, device):
+    """scan_iq's and detect_iq's capture on the device: (flat tensor, format id, the records' extra keys).  balance False: as it
+    came, no key; True or a coefficients tuple: through frontend.balance first, then "ci16", and image_rejection_db -- the
+    capture's estimate before correction, None for given coefficients"""
+    from . import frontend as F
+    if balance is False or balance is None:
+        return F._device_samples(iq, fmt, device), fmt, {}
+    dev, fmt, irr = F.balanced_capture(iq, fmt, balance, device)
+    return dev, fmt, dict(image_rejection_db=irr)
+
+
 def _no_windows(classes, device):
     """predict_iq(..., return_power=True)'s three results for a stretch without a window"""
     import torch
@@ -87,7 +98,7 @@ def _refined_plan(centre, D0, plan, lines, min_line_db):
 
 def scan_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_db: float = 6.0, hop: int = 128, level: float = 7.8e-3,
             squelch_dbfs: Optional[float] = None, refine: bool = False, min_line_db: float = 8.0, bursts: bool = False, hold: float = 0.98,
-            burst_threshold_db: float = 3.0, min_rows: int = 1, merge_rows: int = 1, **find_kw):
+            burst_threshold_db: float = 3.0, min_rows: int = 1, merge_rows: int = 1, balance=False, **find_kw):
     """A wideband capture in, "what is transmitting where, and what modulation" out.  The capture's power spectrogram
     (frontend.spectrogram: nfft bins, Hann window, segments nfft // 2 apart, `avg` of them per row, on the device) is averaged
     over its rows into one spectrum; frontend.find_emitters(spectrum, threshold_db, window=the Hann window, **find_kw) lists
@@ -127,12 +138,18 @@ def scan_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_d
     windows still open; probs and window_dbfs are untouched.  A spectrogram's rows drop trailing segments that do not fill a
     row (and a window's support is wider than the window): the last windows of a capture can therefore be gated even for an
     emitter that never pauses.  An emitter must revisit its bins in at least 1 - hold of the rows to be seen.  bursts=False
-    (the default) is the mean spectrum, and its record has neither key."""
+    (the default) is the mean spectrum, and its record has neither key.
+
+    balance=True first removes the receiver's DC offset and I/Q imbalance, estimated from the capture itself
+    (frontend.balance), and carries on with the corrected "ci16" stream: an uncalibrated zero-IF receiver mirrors every emitter
+    at +f to -f, 20 .. 40 dB down, and a strong one's image is otherwise listed -- and classified -- as an emitter.  A
+    coefficients tuple (frontend.BalanceCoeffs) is applied as given.  The records gain image_rejection_db, the capture's estimate
+    before correction (None for given coefficients).  balance=False (the default) changes nothing and adds no key."""
     import torch
     from . import frontend as F
     fmt = F.sample_format_id(sample_format)
     as_numpy = not isinstance(iq, torch.Tensor)
-    dev = F._device_samples(iq, fmt, f"cuda:{self.device_index}")
+    dev, fmt, balanced = _capture(iq, fmt, balance, f"cuda:{self.device_index}")
     window = F.design_window(nfft)
     spec = F.spectrogram(dev, fmt, nfft=nfft, avg=avg)
     if spec.shape[0] == 0:
@@ -170,14 +187,14 @@ def scan_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_d
         if as_numpy:
             probs, labels, dbfs = probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy()
         out.append(dict(centre=e.centre, bandwidth=e.bandwidth, power_dbfs=e.power_dbfs, snr_db=e.snr_db, shift=shift, interpolate=L, decimate=D,
-                        labels=labels, probs=probs, window_dbfs=dbfs, label=label, **extra))
+                        labels=labels, probs=probs, window_dbfs=dbfs, label=label, **extra, **balanced))
     return out
 
 
 def detect_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_db: float = 6.0, floor: str = "flat", reach_rows: int = 2,
               reach_bins: int = 3, min_rows: int = 3, min_bins: int = 3, hop: int = 128, level: float = 7.8e-3,
               squelch_dbfs: Optional[float] = None, dc_guard: int = 1, batched: bool = False, refine: bool = False, min_line_db: float = 8.0,
-              line_nfft: int = 1024, line_avg: int = 8):
+              line_nfft: int = 1024, line_avg: int = 8, balance=False):
     """A wideband capture in, "what transmitted when, where, and what modulation" out: the scan in two dimensions, for
     frequency hoppers, emitters that share bins at different times and single packets, which scan_iq's one-dimensional
     searches miss or mangle.  The capture's spectrogram (frontend.spectrogram, as scan_iq builds it: nfft bins, segments nfft //
@@ -215,14 +232,16 @@ def detect_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold
     bands) per detection; batched=True does ONE frontend.extract(..., whole_frames=False) for all isolations, ONE line_spectra
     over the block, ONE find_lines whose 3 K records come to the host in one transfer, and then the extraction above with the
     refined shifts and ratios: the same spectra from the same entries, so both forms agree bit for bit.  refine=False is the
-    plan alone, and its record has none of the five keys."""
+    plan alone, and its record has none of the five keys.
+    balance: as scan_iq's -- True, or a coefficients tuple, corrects the capture's DC offset and I/Q imbalance first
+    (frontend.balance) and the records gain image_rejection_db; False (the default) changes nothing and adds no key."""
     import torch
     from . import frontend as F
     fmt = F.sample_format_id(sample_format)
     if batched and hop != 128:
         raise ValueError(f"batched=True needs hop == 128 (got {hop}): windows at another hop would straddle two detections")
     as_numpy = not isinstance(iq, torch.Tensor)
-    dev = F._device_samples(iq, fmt, f"cuda:{self.device_index}")
+    dev, fmt, balanced = _capture(iq, fmt, balance, f"cuda:{self.device_index}")
     spec = F.spectrogram(dev, fmt, nfft=nfft, avg=avg)
     if spec.shape[0] == 0:
         raise ValueError(f"the capture is too short for one row of {avg} segments of {nfft} pairs")
@@ -232,7 +251,7 @@ def detect_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold
         plans, extras = [p[:3] for p in F.channel_plans([(d.centre, d.bandwidth) for d in found])], None
         if refine and found:
             plans, extras = _refine_detections(dev, fmt, found, plans, min_line_db, line_nfft, line_avg)
-        return _classify_detections(self, dev, fmt, found, plans, extras, level, squelch_dbfs, as_numpy)
+        return [dict(r, **balanced) for r in _classify_detections(self, dev, fmt, found, plans, extras, level, squelch_dbfs, as_numpy)]
     per_pair = _cabi.IQ_PAIR_BYTES[fmt] // dev.element_size()      # elements of `dev` per (I,Q) pair
     out = []
     for d in found:
@@ -258,7 +277,7 @@ def detect_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold
         if as_numpy:
             probs, labels, dbfs = probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy()
         out.append(dict(d._asdict(), shift=shift, interpolate=L, decimate=D, probs=probs, labels=labels, window_dbfs=dbfs, windows=windows,
-                        label=label, **extra))
+                        label=label, **extra, **balanced))
     return out
 
 
@@ -316,7 +335,7 @@ def _classify_detections(self, dev, fmt, found, plans, extras, level, squelch_db
 
 
 def predict_channels(self, iq, sample_format, channels: int, decimate: Optional[int] = None, taps=None, tap_shift: Optional[int] = None,
-                     hop: int = 128, level: float = 7.8e-3, squelch_dbfs: Optional[float] = None, batch_size: int = 0):
+                     hop: int = 128, level: float = 7.8e-3, squelch_dbfs: Optional[float] = None, batch_size: int = 0, balance=False):
     """A band with a channel raster in, "what is on every channel" out.  The capture is split into M = channels evenly spaced
     channels in one pass (frontend.channelize(iq, sample_format, channels, decimate, taps, tap_shift, whole_frames=True):
     decimate=None is M / 2, taps=None frontend.design_channelizer(M)), and every channel's stream is cut into windows `hop`
@@ -325,11 +344,14 @@ def predict_channels(self, iq, sample_format, channels: int, decimate: Optional[
     straddles two channels; other hops go channel by channel.  Returns probs (M, W, C), labels (M, W), window_dbfs (M, W) and
     label (M,), int64: per channel the most frequent label among the windows the squelch let through (the smallest on a tie;
     -1 if there are none) -- scan_iq's rule.  Row k is the channel centred at frontend.channel_freqs(M)[k].  Device tensors
-    for a device capture, numpy arrays for a numpy capture."""
+    for a device capture, numpy arrays for a numpy capture.  balance=True, or a coefficients tuple, corrects the capture's DC
+    offset and I/Q imbalance first (frontend.balance); False (the default) changes nothing."""
     import torch
     from . import frontend as F
     fmt = F.sample_format_id(sample_format)
     as_numpy = not isinstance(iq, torch.Tensor)
+    if balance is not False and balance is not None:
+        iq, fmt, _ = F.balanced_capture(iq, fmt, balance, f"cuda:{self.device_index}")
     down = F.channelize(iq, fmt, channels, decimate=decimate, taps=taps, tap_shift=tap_shift, whole_frames=True,
                         device=f"cuda:{self.device_index}")
     M, n_out = down.shape[0], down.shape[1]

@@ -7,6 +7,7 @@ An RTL-SDR delivers unsigned 8-bit interleaved (I, Q) samples; a frame of the cl
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -214,6 +215,172 @@ def window_stats_iq(iq, sample_format, hop: int = HOP_FRAME, remove_dc: bool = T
     """The statistics alone (no frames are written): a numpy array of _cabi.IQ_WINDOW_STATS64 records, one per window."""
     flags = _cabi.IQ_REMOVE_DC if remove_dc else 0
     return stats64_tensor_to_numpy(_windows(iq, _cabi.IQ_ENTRIES, sample_format_id(sample_format), hop, 1.0, flags, False, True, device)[1])
+
+
+# ---- I/Q balance (mdc_iq_balance_stats / mdc_iq_balance): gain / phase imbalance and DC offset -- exact integers, on the device ----
+class BalanceCoeffs(NamedTuple):
+    """The six integers of mdc_iq_balance (include/mdc.h): the DC offsets in widened units and the Q14 matrix.  scale is what
+    design_balance multiplied the matrix by to keep a row's |m_i0| + |m_i1| <= 32767 (1.0: nothing; it is no argument of the
+    correction)."""
+    dc_i: int
+    dc_q: int
+    m00: int
+    m01: int
+    m10: int
+    m11: int
+    scale: float = 1.0
+
+
+BALANCE_IDENTITY = BalanceCoeffs(0, 0, _cabi.BALANCE_ONE, 0, 0, _cabi.BALANCE_ONE)
+BALANCE_SWAP = BalanceCoeffs(0, 0, 0, _cabi.BALANCE_ONE, _cabi.BALANCE_ONE, 0)            # I <-> Q: spectrum inversion of a wrongly wired capture
+BALANCE_CONJUGATE = BalanceCoeffs(0, 0, _cabi.BALANCE_ONE, 0, 0, -_cabi.BALANCE_ONE)      # Q -> -Q (-32768 clamps to 32767)
+
+
+def balance_blocks(pairs_in: int, block_pairs: int = 65536) -> int:
+    """mdc_iq_balance_blocks: ceil(pairs_in / block_pairs), the rows of balance_stats (needs no GPU)."""
+    return _cabi.check(_cabi.lib().mdc_iq_balance_blocks(int(pairs_in), int(block_pairs)))
+
+
+def balance_stats(iq, sample_format, block_pairs: int = 65536, device=None):
+    """The capture's exact second-order statistics per block of block_pairs pairs (mdc_iq_balance_stats, include/mdc.h): the
+    (nblocks, 5) int64 device tensor of sum x, sum y, sum x^2, sum y^2, sum x y over each block's widened samples.  The tensor
+    carries the capture's pair count and the block size as attributes `pairs` and `block_pairs` for design_balance and
+    image_rejection_db (a slice or copy of it does not: pass pairs= there).  Enqueues on torch's current stream without
+    synchronising."""
+    import torch
+    fmt = sample_format_id(sample_format)
+    t = _device_samples(iq, fmt, device)
+    pairs, B = _pair_count(t, fmt), int(block_pairs)
+    L = _cabi.lib()
+    nblocks = _cabi.check(L.mdc_iq_balance_blocks(pairs, B))
+    sums = torch.empty((nblocks, 5), dtype=torch.int64, device=t.device)
+    with torch.cuda.device(t.device):
+        _cabi.check(L.mdc_iq_balance_stats(t.data_ptr() if pairs else None, fmt, pairs, B, sums.data_ptr() if nblocks else None, nblocks,
+                                           torch.cuda.current_stream(t.device).cuda_stream))
+    sums.pairs, sums.block_pairs = pairs, B
+    return sums
+
+
+def _total_sums(sums, pairs):
+    """(n, Sx, Sy, Sxx, Syy, Sxy) as Python integers from balance_stats' tensor, a numpy array of block rows or one summed row"""
+    if pairs is None:
+        pairs = getattr(sums, "pairs", None)
+    if pairs is None:
+        raise ValueError("pairs= is needed: only the tensor balance_stats returned knows how many pairs its sums cover")
+    rows = sums.cpu().numpy() if hasattr(sums, "cpu") else np.asarray(sums)
+    if rows.dtype.kind not in "iu" and rows.dtype != object:
+        raise TypeError(f"the sums must be integers (got {rows.dtype})")
+    rows = rows.reshape(-1, 5)
+    return (int(pairs),) + tuple(sum(int(v) for v in rows[:, k]) for k in range(5))
+
+
+def _central_moments(sums, pairs):
+    """n and the exact integers n^2 times the (co)variances: cxx = n Sxx - Sx^2, cyy, cxy = n Sxy - Sx Sy"""
+    n, Sx, Sy, Sxx, Syy, Sxy = _total_sums(sums, pairs)
+    return n, Sx, Sy, n * Sxx - Sx * Sx, n * Syy - Sy * Sy, n * Sxy - Sx * Sy
+
+
+def design_balance(sums, pairs=None) -> BalanceCoeffs:
+    """The coefficients of mdc_iq_balance from a capture's statistics (include/mdc.h, "design").  sums: balance_stats' tensor
+    (it knows its pair count), or a numpy array of block rows or one summed row (sum x, sum y, sum x^2, sum y^2, sum x y) with
+    pairs= the number of pairs they cover -- a caller who leaves blocks out passes the rows kept and their pairs.  dc = (2 S + n)
+    // (2 n): the mean, round half up, exact.  M = sqrt(tr C / 2) C^(-1/2) in float64 from the exact integer central moments --
+    the symmetric whitening matrix: it equalises the rails, makes them orthogonal, keeps the total power and does not rotate --,
+    m_ij = rint(16384 M_ij).  If a row's |m_i0| + |m_i1| exceeds 32767 (an imbalance near 6 dB: no real receiver) M is scaled
+    down until both rows hold, and the result's `scale` says by how much.  No pairs, or a capture without variance on a rail or
+    with fully correlated rails (nothing to estimate): the identity matrix, the DC alone.  The estimate is blind: it takes the
+    capture as a whole to be proper (include/mdc.h says when that fails)."""
+    import math
+    n, Sx, Sy, cxx, cyy, cxy = _central_moments(sums, pairs)
+    if n <= 0:
+        return BALANCE_IDENTITY
+    dc_i, dc_q = (2 * Sx + n) // (2 * n), (2 * Sy + n) // (2 * n)
+    det = cxx * cyy - cxy * cxy
+    if cxx <= 0 or cyy <= 0 or det <= 0:
+        return BALANCE_IDENTITY._replace(dc_i=dc_i, dc_q=dc_q)
+    n2 = float(n) * float(n)
+    a, b, d = cxx / n2, cxy / n2, cyy / n2
+    s = math.sqrt(a * d - b * b) if a * d - b * b > 0.0 else math.sqrt(det) / n2
+    # C^(1/2) = (C + s I) / t, t = sqrt(tr C + 2 s), s = sqrt(det C) (Cayley-Hamilton for 2 x 2); its inverse, times sqrt(tr C / 2)
+    t = math.sqrt(a + d + 2.0 * s)
+    g = math.sqrt((a + d) / 2.0) * t / ((a + s) * (d + s) - b * b)
+    M = (g * (d + s), -g * b, -g * b, g * (a + s))
+    scale = 1.0
+    while True:
+        m = [int(np.rint(_cabi.BALANCE_ONE * scale * v)) for v in M]
+        worst = max(abs(m[0]) + abs(m[1]), abs(m[2]) + abs(m[3]))
+        if worst <= _cabi.BALANCE_MAX_ROW_ABS_SUM:
+            return BalanceCoeffs(dc_i, dc_q, *m, scale=scale)
+        scale *= (_cabi.BALANCE_MAX_ROW_ABS_SUM - 0.5) / worst
+
+
+def image_rejection_db(sums, pairs=None) -> float:
+    """The capture's own image rejection ratio in dB from its statistics (sums, pairs: as design_balance), before any
+    correction: with the exact integer central moments cxx, cyy, cxy, rho = hypot(cxx - cyy, 2 cxy) / (cxx + cyy) = |E[z^2]| /
+    E[|z|^2], r = (1 - sqrt(1 - rho^2)) / rho the image's amplitude relative to the signal's, IRR = -20 log10 r; inf when rho
+    is 0 (or there is nothing to measure).  1 dB and 5 degrees give 22.83 dB.  On a balanced capture the estimate's own noise
+    ends it near 90 dB for 2^18 pairs."""
+    import math
+    n, _, _, cxx, cyy, cxy = _central_moments(sums, pairs)
+    if n <= 0 or cxx + cyy <= 0:
+        return math.inf
+    num2 = (cxx - cyy) ** 2 + 4 * cxy * cxy      # exact
+    if num2 == 0:
+        return math.inf
+    rho = min(math.sqrt(num2) / (cxx + cyy), 1.0)
+    r = (1.0 - math.sqrt(1.0 - rho * rho)) / rho
+    if r <= 0.0:      # rho below float64's resolution of 1 - rho^2: r = rho / 2 to first order
+        r = rho / 2.0
+    return -20.0 * math.log10(r)
+
+
+def _balance_record(coeffs):
+    """The six integers of `coeffs` (a BalanceCoeffs, or any sequence of at least six integers) as the 24-byte record"""
+    c = tuple(coeffs)[:6]
+    if len(c) != 6:
+        raise ValueError("coeffs must hold dc_i, dc_q, m00, m01, m10, m11")
+    rec = np.zeros((), _cabi.IQ_BALANCE_COEFFS)
+    for name, v in zip(_cabi.IQ_BALANCE_COEFFS.names, c):
+        if int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31:
+            raise ValueError(f"coeffs.{name} must be a 32-bit integer (got {v!r})")
+        rec[name] = int(v)
+    return rec
+
+
+def balance(iq, sample_format, coeffs=None, block_pairs: int = 65536, device=None, return_coeffs: bool = False):
+    """Remove a capture's DC offset and I/Q imbalance on the device (mdc_iq_balance, include/mdc.h: exact integer arithmetic).
+    Returns the (n, 2) int16 device tensor of corrected pairs: an ordinary "ci16" capture for every other function here.
+    coeffs=None estimates from this capture -- one balance_stats launch, one transfer of 40 bytes per block, design_balance,
+    one correction launch; passing a BalanceCoeffs (or any six integers dc_i, dc_q, m00, m01, m10, m11) skips the first two:
+    the normal use for a receiver calibrated once per tuning and gain.  BALANCE_SWAP exchanges I and Q, BALANCE_CONJUGATE
+    negates Q; BALANCE_IDENTITY only widens.  return_coeffs=True returns (tensor, the BalanceCoeffs applied, the capture's
+    image_rejection_db before correction -- None when coefficients were passed).  With given coefficients the call enqueues on
+    torch's current stream without synchronising."""
+    import torch
+    fmt = sample_format_id(sample_format)
+    t = _device_samples(iq, fmt, device)
+    pairs = _pair_count(t, fmt)
+    irr = None
+    if coeffs is None:
+        sums = balance_stats(t, fmt, block_pairs)
+        host = sums.cpu().numpy()
+        coeffs, irr = design_balance(host, pairs), image_rejection_db(host, pairs)
+    elif not isinstance(coeffs, BalanceCoeffs):
+        coeffs = BalanceCoeffs(*(int(v) for v in tuple(coeffs)[:6]))
+    rec = _balance_record(coeffs)
+    out = torch.empty((pairs, 2), dtype=torch.int16, device=t.device)
+    with torch.cuda.device(t.device):
+        _cabi.check(_cabi.lib().mdc_iq_balance(t.data_ptr() if pairs else None, fmt, pairs, rec.ctypes.data, out.data_ptr() if pairs else None,
+                                               torch.cuda.current_stream(t.device).cuda_stream))
+    return (out, coeffs, irr) if return_coeffs else out
+
+
+def balanced_capture(iq, sample_format, balance_arg, device=None):
+    """The `balance=` keyword of predict_iq / scan_iq / detect_iq / predict_channels: (capture, format id, image_rejection_db or
+    None).  balance_arg True: estimated from the capture; a coefficients tuple: applied as given.  The capture comes back flat,
+    as "ci16", on the device."""
+    out, _, irr = balance(iq, sample_format, None if balance_arg is True else balance_arg, device=device, return_coeffs=True)
+    return out.view(-1), _cabi.IQ_CI16, irr
 
 
 # ---- digital down-converter (mdc_iq_ddc): frequency shift, low-pass, decimate -- exact integers, on the device -------------

@@ -865,7 +865,7 @@ class VTCNN2:
 
     def predict_iq(self, iq, sample_format, scale: Optional[float] = None, batch_size: int = 0, hop: int = 128,
                    normalize: Optional[str] = None, level: float = 7.8e-3, remove_dc: bool = True, squelch_dbfs: Optional[float] = None,
-                   return_power: bool = False, shift: float = 0.0, decimate: int = 1, taps=None, interpolate: int = 1):
+                   return_power: bool = False, shift: float = 0.0, decimate: int = 1, taps=None, interpolate: int = 1, balance=False):
         """predict_iq_u8 for a capture in any integer sample format: sample_format "cu8" (unsigned bytes, RTL-SDR), "ci8"
         (signed bytes: HackRF) or "ci16" (signed 16-bit little-endian: USRP sc16, SDRplay, bladeRF, Airspy); SigMF's
         "ci16_le" etc. are aliases.  iq: a numpy array or torch tensor of the format's dtype (uint8 / int8 / int16; a
@@ -887,11 +887,22 @@ class VTCNN2:
         interpolate: a rate that no integer decimation brings to 8 samples per symbol (2.4 MS/s on 250 ksym/s wants 5/6:
         frontend.resample_ratio) goes through frontend.resample(iq, sample_format, shift, interpolate, decimate, taps) instead --
         taps=None is frontend.design_resampler of the reduced factors --; everything after it is the same.  With interpolate == 1
-        the route above is taken unchanged."""
+        the route above is taken unchanged.
+
+        balance=True first removes the receiver's DC offset and I/Q imbalance, estimated from the capture itself
+        (frontend.balance: exact integers, on the device), and carries on with the corrected stream as "ci16" (scale=None then
+        means 1/32768); a coefficients tuple (frontend.BalanceCoeffs) is applied as given.  A numpy capture is moved to the
+        device for this and numpy results come back.  balance=False (the default) changes nothing."""
         torch = _torch()
         from . import frontend as F
         fmt = F.sample_format_id(sample_format)
         as_numpy = not isinstance(iq, torch.Tensor)
+        if balance is not False and balance is not None:
+            flat, _, _ = F.balanced_capture(iq, fmt, balance, f"cuda:{self.device_index}")
+            res = self.predict_iq(flat, _cabi.IQ_CI16, scale, batch_size=batch_size, hop=hop, normalize=normalize, level=level, remove_dc=remove_dc,
+                                  squelch_dbfs=squelch_dbfs, return_power=return_power, shift=shift, decimate=decimate, taps=taps,
+                                  interpolate=interpolate)
+            return tuple(r.cpu().numpy() for r in res) if as_numpy else res
         if shift != 0.0 or decimate != 1 or taps is not None or interpolate != 1:
             if interpolate != 1:
                 down = F.resample(iq, fmt, shift=shift, interpolate=interpolate, decimate=decimate, taps=taps, device=f"cuda:{self.device_index}")
