@@ -232,7 +232,7 @@ int mdc_iq_balance_stats(const void* iq_dev, int format, int64_t pairs_in, int64
         return MDC_EINVAL;
     }
     if ((rc = iq_pair_aligned("mdc_iq_balance_stats", "iq_dev", format, iq_dev)) != MDC_OK) return rc;
-    if ((reinterpret_cast<uintptr_t>(sums_dev) & 7) != 0) { set_error("mdc_iq_balance_stats: sums_dev must be 8-byte aligned"); return MDC_EINVAL; }
+    if ((rc = iq_aligned("mdc_iq_balance_stats", "sums_dev", sums_dev, 8)) != MDC_OK) return rc;
     if (pairs_in == 0) return MDC_OK;
     if (!iq_dev || !sums_dev) { set_error("mdc_iq_balance_stats: null buffer"); return MDC_EINVAL; }
     const unsigned char* p = static_cast<const unsigned char*>(iq_dev);
@@ -260,7 +260,7 @@ int mdc_iq_balance(const void* iq_dev, int format, int64_t pairs_in, const mdc_i
         return MDC_EINVAL;
     }
     if ((rc = iq_pair_aligned("mdc_iq_balance", "iq_dev", format, iq_dev)) != MDC_OK) return rc;
-    if ((reinterpret_cast<uintptr_t>(out_dev) & 3) != 0) { set_error("mdc_iq_balance: output must be 4-byte aligned"); return MDC_EINVAL; }
+    if ((rc = iq_aligned("mdc_iq_balance", "output", out_dev, 4)) != MDC_OK) return rc;
     if (pairs_in == 0) return MDC_OK;
     if (!iq_dev || !out_dev) { set_error("mdc_iq_balance: null buffer"); return MDC_EINVAL; }
     const uintptr_t in0 = reinterpret_cast<uintptr_t>(iq_dev), out0 = reinterpret_cast<uintptr_t>(out_dev);

@@ -15,11 +15,9 @@
 //             each by the same work-group and come from L1 / L2 after the first.  Taps past T are zero, pairs
 //             past the capture are never read: memory-safe for any taps; sums that break the header's per-residue
 //             precondition wrap (the accumulation is unsigned).
-//   passes    the spectrogram's transform (iq_spectrogram.hip: Stockham autosort, decimation in frequency, radix 4, a last
-//             radix-2 pass for an odd log2 M, table twiddles from iq_fft_twiddles.h, one element of padding after every 16),
-//             restated here for G transforms side by side: butterfly b of a pass is transform b / (M / 4), index b mod (M / 4).
-//             With 256 threads and 1024 elements a radix-4 pass is one butterfly per thread, the radix-2 pass two.  M = 8, 16,
-//             32 are new sizes; the structure is the same.
+//   passes    iq_fft.h's transform, G of them side by side in one image: transform g starts at element g M, and butterfly b of a
+//             pass is transform b / (M / 4), index b mod (M / 4).  With 256 threads and 1024 elements a radix-4 pass is one
+//             butterfly per thread, the radix-2 pass that ends an odd log2 M two.
 //   output    the last pass keeps its outputs in registers: out = clamp(rint(Y 2^-(15+s))) as an int16 pair, written to an LDS
 //             image [channel][step of the tile] (chan_image_slot: columns swizzled against bank conflicts).  When the tile is
 //             done the image leaves channel by channel: runs of kJ pairs (>= 64 bytes) per channel row, one dword per lane.
@@ -28,6 +26,7 @@
 // Every step's arithmetic is the same whatever tile, group or slot it lands in -- integer sums are exact and the transform of a
 // slot touches that slot's elements only --: the same bits on every run, for every split of a capture.
 // The call only enqueues; vector memory for every store.
+#include "iq_fft.h"
 #include "iq_mix.h"
 
 namespace mdc {
@@ -38,26 +37,8 @@ constexpr int kChanMinLog2 = 3, kChanMaxLog2 = 10, kChanTapsPerChannel = 16, kCh
 constexpr long kChanGridCap = 2048;      // work-groups; beyond it the kernel strides (_cabi.CHANNELIZER_GRID_CAP)
 constexpr int kChanThreads = 256;
 constexpr int kChanGroupElems = 1024;    // complex elements of one group of transforms: 4 per thread
-constexpr int kChanTwQuadrant = 1024;    // entries of iq_fft_twiddles.h: a quarter of the 4096-point circle
-
-__device__ const unsigned d_chan_tw[2 * kChanTwQuadrant] = {
-#include "iq_fft_twiddles.h"
-};
 
 __host__ __device__ constexpr int chan_tile_steps(int log2m) { return kChanGroupElems >> log2m < 16 ? 16 : kChanGroupElems >> log2m; }
-__host__ __device__ constexpr int chan_slot(int e) { return e + (e >> 4); }
-
-// e^{-2 pi i J / 4096}, 0 <= J < 3072
-__device__ __forceinline__ float2 chan_twiddle(int J) {
-    const int j = J & (kChanTwQuadrant - 1), quadrant = J >> 10;
-    const float c = __uint_as_float(d_chan_tw[2 * j]), s = __uint_as_float(d_chan_tw[2 * j + 1]);
-    return quadrant == 0 ? make_float2(c, -s) : quadrant == 1 ? make_float2(-s, -c) : make_float2(-c, s);
-}
-
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cmul(float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
-__device__ __forceinline__ float2 cmuli(float2 a) { return make_float2(-a.y, a.x); }      // a * i
 
 // the tile's output image: channel c's row of J dwords, its columns XORed with the channel's bits above SWZ.  Unswizzled rows put
 // the last pass's writes (a wave: consecutive channels of one column, row stride 16 dwords at M >= 64) on 4 of the 64 banks; with
@@ -77,20 +58,14 @@ __global__ __launch_bounds__(kChanThreads) void iq_channelizer_kernel(const unsi
                                                                      unsigned* __restrict__ out, long n_out) {
     constexpr int M = 1 << LOG2M, NB = M / 4, G = kChanGroupElems / M, kJ = chan_tile_steps(LOG2M);
     constexpr int kSwz = kJ >= 64 ? 0 : kJ == 32 ? 1 : 2;      // chan_image_slot
-    constexpr bool kOdd = (LOG2M & 1) != 0;
-    constexpr int kStoredPasses = kOdd ? LOG2M / 2 : LOG2M / 2 - 1;
+    constexpr unsigned NL = M / fft_last_radix(LOG2M);         // butterflies of a transform's last pass: one per thread, or two
     static_assert(kJ % G == 0 && G * NB == kChanThreads, "a group is one radix-4 butterfly per thread");
-    __shared__ float2 x[chan_slot(kChanGroupElems)];
+    __shared__ float2 x[fft_slot(kChanGroupElems)];
     __shared__ float2 tw[3 * NB];
     __shared__ unsigned res[M * kJ];
     const int tid = threadIdx.x;
     const int g = tid >> (LOG2M - 2), q = tid & (NB - 1);      // this thread's transform of the group, and its quad / butterfly in it
-    for (int j = tid; j < NB; j += kChanThreads) {
-        const int J = j << (12 - LOG2M);
-        tw[j] = chan_twiddle(J);
-        tw[NB + j] = chan_twiddle(2 * J);
-        tw[2 * NB + j] = chan_twiddle(3 * J);
-    }
+    fft_fill_twiddles<LOG2M, kChanThreads>(tw, tid);
     const long tiles = (n_out + kJ - 1) / kJ;
     for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const long j0 = tile * kJ;
@@ -129,42 +104,19 @@ __global__ __launch_bounds__(kChanThreads) void iq_channelizer_kernel(const unsi
             __syncthreads();      // the twiddles are in place; the previous group's last pass has read its image
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                x[chan_slot(g * M + ((4 * q + e + rot) & (M - 1)))] = make_float2((float)(int)ar[e], (float)(int)ai[e]);
+                x[fft_slot(g * M + ((4 * q + e + rot) & (M - 1)))] = make_float2((float)(int)ar[e], (float)(int)ai[e]);
             __syncthreads();
-            const int eb = g * M;      // this transform's first element of the group's image
+            float2 y[1][4];
+            fft_stored_passes<LOG2M, 1, NB>(x, tw, g * M, q, y);
+            // the last pass: butterfly b of the group is transform b / NL, index b mod NL (radix 4: g and q again); its outputs are
+            // the channels of the step in column grp G + b / NL of the tile's image
 #pragma unroll
-            for (int pass = 0; pass < kStoredPasses; ++pass) {
-                const int s = 1 << (2 * pass);
-                const float2 a = x[chan_slot(eb + q)], b = x[chan_slot(eb + q + NB)], c = x[chan_slot(eb + q + 2 * NB)], d = x[chan_slot(eb + q + 3 * NB)];
-                const float2 apc = cadd(a, c), amc = csub(a, c), bpd = cadd(b, d), jbmd = cmuli(csub(b, d));
-                const int jt = q & ~(s - 1);
-                const float2 y0 = cadd(apc, bpd), y1 = cmul(csub(amc, jbmd), tw[jt]), y2 = cmul(csub(apc, bpd), tw[NB + jt]),
-                             y3 = cmul(cadd(amc, jbmd), tw[2 * NB + jt]);
-                __syncthreads();
-                const int r = q & (s - 1), base = eb + r + 4 * (q - r);
-                x[chan_slot(base)] = y0;
-                x[chan_slot(base + s)] = y1;
-                x[chan_slot(base + 2 * s)] = y2;
-                x[chan_slot(base + 3 * s)] = y3;
-                __syncthreads();
-            }
-            const int jj = grp * G + g;      // the step's column of the tile's image
-            if (!kOdd) {      // the last radix-4 pass: stride M/4, no twiddles, channels q + k M/4
-                const float2 a = x[chan_slot(eb + q)], b = x[chan_slot(eb + q + NB)], c = x[chan_slot(eb + q + 2 * NB)], d = x[chan_slot(eb + q + 3 * NB)];
-                const float2 apc = cadd(a, c), amc = csub(a, c), bpd = cadd(b, d), jbmd = cmuli(csub(b, d));
-                res[chan_image_slot<kJ, kSwz>(q, jj)] = chan_pack(cadd(apc, bpd), scale);
-                res[chan_image_slot<kJ, kSwz>(q + NB, jj)] = chan_pack(csub(amc, jbmd), scale);
-                res[chan_image_slot<kJ, kSwz>(q + 2 * NB, jj)] = chan_pack(csub(apc, bpd), scale);
-                res[chan_image_slot<kJ, kSwz>(q + 3 * NB, jj)] = chan_pack(cadd(amc, jbmd), scale);
-            } else {          // the last radix-2 pass: stride M/2, channels t and t + M/2; two butterflies per thread
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const int b2 = tid + i * kChanThreads, g2 = b2 >> (LOG2M - 1), t = b2 & (M / 2 - 1);
-                    const float2 a = x[chan_slot(g2 * M + t)], b = x[chan_slot(g2 * M + t + M / 2)];
-                    const int jj2 = grp * G + g2;
-                    res[chan_image_slot<kJ, kSwz>(t, jj2)] = chan_pack(cadd(a, b), scale);
-                    res[chan_image_slot<kJ, kSwz>(t + M / 2, jj2)] = chan_pack(csub(a, b), scale);
-                }
+            for (int i = 0; i < G * (int)NL / kChanThreads; ++i) {
+                const unsigned b = tid + i * kChanThreads;
+                const int gl = (int)(b / NL), jj = grp * G + gl;
+                fft_last_pass<LOG2M, 1, (int)NL>(x, gl * M, (int)(b % NL), [&](int, int, int channel, float2 v) {
+                    res[chan_image_slot<kJ, kSwz>(channel, jj)] = chan_pack(v, scale);
+                });
             }
         }
         __syncthreads();      // the tile's image is complete
@@ -189,29 +141,8 @@ int chan_launch(const unsigned char* iq, int64_t pairs, unsigned rot0, int decim
     return MDC_OK;
 }
 
-template <int FMT>
-int chan_launch_fmt(int log2m, const unsigned char* iq, int64_t pairs, unsigned rot0, int decimate, const int16_t* taps, int ntaps, float scale,
-                    int16_t* out, int64_t n_out, hipStream_t s) {
-    switch (log2m) {
-        case 3: return chan_launch<FMT, 3>(iq, pairs, rot0, decimate, taps, ntaps, scale, out, n_out, s);
-        case 4: return chan_launch<FMT, 4>(iq, pairs, rot0, decimate, taps, ntaps, scale, out, n_out, s);
-        case 5: return chan_launch<FMT, 5>(iq, pairs, rot0, decimate, taps, ntaps, scale, out, n_out, s);
-        case 6: return chan_launch<FMT, 6>(iq, pairs, rot0, decimate, taps, ntaps, scale, out, n_out, s);
-        case 7: return chan_launch<FMT, 7>(iq, pairs, rot0, decimate, taps, ntaps, scale, out, n_out, s);
-        case 8: return chan_launch<FMT, 8>(iq, pairs, rot0, decimate, taps, ntaps, scale, out, n_out, s);
-        case 9: return chan_launch<FMT, 9>(iq, pairs, rot0, decimate, taps, ntaps, scale, out, n_out, s);
-        default: return chan_launch<FMT, 10>(iq, pairs, rot0, decimate, taps, ntaps, scale, out, n_out, s);
-    }
-}
-
-int chan_log2(int channels) {      // log2 of a power of two in 8..1024, else -1
-    for (int l = kChanMinLog2; l <= kChanMaxLog2; ++l)
-        if (channels == 1 << l) return l;
-    return -1;
-}
-
 int chan_shape_check(const char* who, int64_t pairs, int channels, int ntaps, int decimate) {
-    if (chan_log2(channels) < 0) {
+    if (pow2_log2(channels, kChanMinLog2, kChanMaxLog2) < 0) {
         set_error("%s: channels must be a power of two in %d..%d (got %d)", who, 1 << kChanMinLog2, 1 << kChanMaxLog2, channels);
         return MDC_EINVAL;
     }
@@ -224,8 +155,6 @@ int chan_shape_check(const char* who, int64_t pairs, int channels, int ntaps, in
     return MDC_OK;
 }
 
-int64_t chan_out_count(int64_t pairs, int ntaps, int decimate) { return pairs >= ntaps ? (pairs - ntaps) / decimate + 1 : 0; }
-
 }  // namespace
 
 }  // namespace mdc
@@ -234,7 +163,7 @@ using namespace mdc;
 
 int64_t mdc_iq_channelizer_out_count(int64_t pairs_in, int channels, int ntaps, int decimate) {
     const int rc = chan_shape_check("mdc_iq_channelizer_out_count", pairs_in, channels, ntaps, decimate);
-    return rc != MDC_OK ? (int64_t)rc : chan_out_count(pairs_in, ntaps, decimate);
+    return rc != MDC_OK ? (int64_t)rc : iq_span_count(pairs_in, ntaps, decimate);
 }
 
 int mdc_iq_channelizer(const void* iq_dev, int format, int64_t pairs_in, int64_t first_index, int channels, int decimate, const int16_t* taps_dev,
@@ -244,17 +173,17 @@ int mdc_iq_channelizer(const void* iq_dev, int format, int64_t pairs_in, int64_t
     if ((rc = chan_shape_check("mdc_iq_channelizer", pairs_in, channels, ntaps, decimate)) != MDC_OK) return rc;
     if (tap_shift < 0 || tap_shift > kChanMaxShift) { set_error("mdc_iq_channelizer: tap_shift must be in 0..%d (got %d)", kChanMaxShift, tap_shift); return MDC_EINVAL; }
     if (first_index < 0) { set_error("mdc_iq_channelizer: negative first_index"); return MDC_EINVAL; }
-    if (n_out != chan_out_count(pairs_in, ntaps, decimate)) {
+    if (n_out != iq_span_count(pairs_in, ntaps, decimate)) {
         set_error("mdc_iq_channelizer: n_out is %lld, mdc_iq_channelizer_out_count gives %lld", (long long)n_out,
-                  (long long)chan_out_count(pairs_in, ntaps, decimate));
+                  (long long)iq_span_count(pairs_in, ntaps, decimate));
         return MDC_EINVAL;
     }
     if ((rc = iq_pair_aligned("mdc_iq_channelizer", "iq_dev", format, iq_dev)) != MDC_OK) return rc;
-    if ((reinterpret_cast<uintptr_t>(taps_dev) & 1) != 0) { set_error("mdc_iq_channelizer: taps_dev must be 2-byte aligned"); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(out_dev) & 3) != 0) { set_error("mdc_iq_channelizer: out_dev must be 4-byte aligned"); return MDC_EINVAL; }
+    if ((rc = iq_aligned("mdc_iq_channelizer", "taps_dev", taps_dev, 2)) != MDC_OK) return rc;
+    if ((rc = iq_aligned("mdc_iq_channelizer", "out_dev", out_dev, 4)) != MDC_OK) return rc;
     if (n_out == 0) return MDC_OK;
     if (!iq_dev || !taps_dev || !out_dev) { set_error("mdc_iq_channelizer: null buffer"); return MDC_EINVAL; }
-    const int log2m = chan_log2(channels);
+    const int log2m = pow2_log2(channels, kChanMinLog2, kChanMaxLog2);
     const unsigned rot0 = (unsigned)(first_index & (int64_t)(channels - 1));
     float scale = 1.f;
     for (int i = 0; i < 15 + tap_shift; ++i) scale *= 0.5f;      // 2^-(15+s), exact
@@ -262,6 +191,9 @@ int mdc_iq_channelizer(const void* iq_dev, int format, int64_t pairs_in, int64_t
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     return guarded("mdc_iq_channelizer", [&]() -> int {
         return with_format(format, [&](auto fmt) {
-            return chan_launch_fmt<decltype(fmt)::value>(log2m, p, pairs_in, rot0, decimate, taps_dev, ntaps, scale, out_dev, n_out, s); });
+            return with_log2<kChanMinLog2, kChanMaxLog2>(log2m, [&](auto l2) {
+                return chan_launch<decltype(fmt)::value, decltype(l2)::value>(p, pairs_in, rot0, decimate, taps_dev, ntaps, scale, out_dev, n_out, s);
+            });
+        });
     });
 }

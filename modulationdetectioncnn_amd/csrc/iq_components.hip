@@ -334,12 +334,6 @@ __global__ __launch_bounds__(kCompThreads) void iq_comp_records_kernel(mdc_iq_co
     comps[i].peak_bin = (int)(at & (unsigned)(nfft - 1));
 }
 
-int comp_log2(int nfft) {      // log2 of a power of two in 64..4096, else -1
-    for (int l = kCompMinLog2; l <= kCompMaxLog2; ++l)
-        if (nfft == 1 << l) return l;
-    return -1;
-}
-
 }  // namespace
 
 }  // namespace mdc
@@ -350,7 +344,7 @@ static_assert(sizeof(mdc_iq_component) == 32, "mdc_iq_component is 32 bytes");
 
 int64_t mdc_iq_spectrogram_components_workspace(int64_t rows, int nfft) {
     const char* who = "mdc_iq_spectrogram_components_workspace";
-    if (comp_log2(nfft) < 0) { set_error("%s: nfft must be a power of two in %d..%d (got %d)", who, 1 << kCompMinLog2, 1 << kCompMaxLog2, nfft); return MDC_EINVAL; }
+    if (pow2_log2(nfft, kCompMinLog2, kCompMaxLog2) < 0) { set_error("%s: nfft must be a power of two in %d..%d (got %d)", who, 1 << kCompMinLog2, 1 << kCompMaxLog2, nfft); return MDC_EINVAL; }
     if (rows < 1 || rows > 2147483647LL / nfft) { set_error("%s: rows must be >= 1 and rows * nfft <= 2^31-1 (got %lld)", who, (long long)rows); return MDC_EINVAL; }
     const int64_t nchunks = (rows * nfft + kChunk - 1) / kChunk;
     return (nchunks * 4 + 15) / 16 * 16;
@@ -360,19 +354,20 @@ int mdc_iq_spectrogram_components(const float* power_dev, int64_t rows, int nfft
                                   int32_t* labels_dev, mdc_iq_component* comps_dev, int64_t capacity, int64_t* count_dev, void* work_dev,
                                   void* hip_stream) {
     const char* who = "mdc_iq_spectrogram_components";
-    const int lognfft = comp_log2(nfft);
+    const int lognfft = pow2_log2(nfft, kCompMinLog2, kCompMaxLog2);
     if (lognfft < 0) { set_error("%s: nfft must be a power of two in %d..%d (got %d)", who, 1 << kCompMinLog2, 1 << kCompMaxLog2, nfft); return MDC_EINVAL; }
     if (rows < 1 || rows > 2147483647LL / nfft) { set_error("%s: rows must be >= 1 and rows * nfft <= 2^31-1 (got %lld)", who, (long long)rows); return MDC_EINVAL; }
     if (reach_rows < 0 || reach_rows > kCompMaxReach) { set_error("%s: reach_rows must be in 0..%d (got %d)", who, kCompMaxReach, reach_rows); return MDC_EINVAL; }
     if (reach_bins < 0 || reach_bins > kCompMaxReach) { set_error("%s: reach_bins must be in 0..%d (got %d)", who, kCompMaxReach, reach_bins); return MDC_EINVAL; }
     if (capacity < 0) { set_error("%s: capacity must be >= 0 (got %lld)", who, (long long)capacity); return MDC_EINVAL; }
     if (!power_dev || !thresh_dev || !labels_dev || !count_dev || !work_dev || (capacity > 0 && !comps_dev)) { set_error("%s: null buffer", who); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(power_dev) & 3) != 0) { set_error("%s: power_dev must be 4-byte aligned", who); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(thresh_dev) & 3) != 0) { set_error("%s: thresh_dev must be 4-byte aligned", who); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(labels_dev) & 3) != 0) { set_error("%s: labels_dev must be 4-byte aligned", who); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(comps_dev) & 7) != 0) { set_error("%s: comps_dev must be 8-byte aligned", who); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(count_dev) & 7) != 0) { set_error("%s: count_dev must be 8-byte aligned", who); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(work_dev) & 15) != 0) { set_error("%s: work_dev must be 16-byte aligned", who); return MDC_EINVAL; }
+    int rc = iq_aligned(who, "power_dev", power_dev, 4);
+    if (rc != MDC_OK) return rc;
+    if ((rc = iq_aligned(who, "thresh_dev", thresh_dev, 4)) != MDC_OK) return rc;
+    if ((rc = iq_aligned(who, "labels_dev", labels_dev, 4)) != MDC_OK) return rc;
+    if ((rc = iq_aligned(who, "comps_dev", comps_dev, 8)) != MDC_OK) return rc;
+    if ((rc = iq_aligned(who, "count_dev", count_dev, 8)) != MDC_OK) return rc;
+    if ((rc = iq_aligned(who, "work_dev", work_dev, 16)) != MDC_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const int cells = (int)(rows * nfft), nr = (int)rows;
     const int tiles_c = nfft / kTileCols, tiles = tiles_c * ((nr + kTileRows - 1) / kTileRows), nchunks = (int)(((int64_t)cells + kChunk - 1) / kChunk);

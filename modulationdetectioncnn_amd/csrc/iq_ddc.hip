@@ -71,8 +71,6 @@ int ddc_launch(const unsigned char* iq, int64_t pairs, uint32_t phase0, uint32_t
     return MDC_OK;
 }
 
-int64_t ddc_out_count(int64_t pairs, int ntaps, int decimate) { return pairs >= ntaps ? (pairs - ntaps) / decimate + 1 : 0; }
-
 int ddc_shape_check(const char* who, int64_t pairs, int ntaps, int decimate) {
     if (decimate < 1 || decimate > kMaxDecimate) { set_error("%s: decimate must be in 1..%d (got %d)", who, kMaxDecimate, decimate); return MDC_EINVAL; }
     if (ntaps < 1 || ntaps > kMaxTaps) { set_error("%s: ntaps must be in 1..%d (got %d)", who, kMaxTaps, ntaps); return MDC_EINVAL; }
@@ -88,7 +86,7 @@ using namespace mdc;
 
 int64_t mdc_iq_ddc_out_count(int64_t pairs_in, int ntaps, int decimate) {
     const int rc = ddc_shape_check("mdc_iq_ddc_out_count", pairs_in, ntaps, decimate);
-    return rc != MDC_OK ? (int64_t)rc : ddc_out_count(pairs_in, ntaps, decimate);
+    return rc != MDC_OK ? (int64_t)rc : iq_span_count(pairs_in, ntaps, decimate);
 }
 
 int mdc_iq_ddc_nco_table(int16_t* cos_sin_host) {
@@ -112,12 +110,12 @@ int mdc_iq_ddc(const void* iq_dev, int format, int64_t pairs_in, uint32_t phase0
         set_error("mdc_iq_ddc: the taps' absolute values sum to %ld; at most 65535 keeps the 32-bit accumulation exact", abs_sum);
         return MDC_EINVAL;
     }
-    if (n_out != ddc_out_count(pairs_in, ntaps, decimate)) {
-        set_error("mdc_iq_ddc: n_out is %lld, mdc_iq_ddc_out_count gives %lld", (long long)n_out, (long long)ddc_out_count(pairs_in, ntaps, decimate));
+    if (n_out != iq_span_count(pairs_in, ntaps, decimate)) {
+        set_error("mdc_iq_ddc: n_out is %lld, mdc_iq_ddc_out_count gives %lld", (long long)n_out, (long long)iq_span_count(pairs_in, ntaps, decimate));
         return MDC_EINVAL;
     }
     if ((rc = iq_pair_aligned("mdc_iq_ddc", "input", format, iq_dev)) != MDC_OK) return rc;
-    if ((reinterpret_cast<uintptr_t>(out_dev) & 3) != 0) { set_error("mdc_iq_ddc: output must be 4-byte aligned"); return MDC_EINVAL; }
+    if ((rc = iq_aligned("mdc_iq_ddc", "output", out_dev, 4)) != MDC_OK) return rc;
     if (n_out == 0) return MDC_OK;
     if (!iq_dev || !out_dev) { set_error("mdc_iq_ddc: null buffer"); return MDC_EINVAL; }
     DdcTaps taps{};

@@ -314,8 +314,8 @@ int mdc_iq_extract(const void* iq_dev, int format, int64_t pairs_in, const void*
     if (h.pairs_in != pairs_in) { set_error("%s: pairs_in is %lld, the plan was made for %lld", who, (long long)pairs_in, (long long)h.pairs_in); return MDC_EINVAL; }
     if (h.out_pairs != out_pairs) { set_error("%s: out_pairs is %lld, the plan was made for %lld", who, (long long)out_pairs, (long long)h.out_pairs); return MDC_EINVAL; }
     if ((rc = iq_pair_aligned(who, "input", format, iq_dev)) != MDC_OK) return rc;
-    if ((reinterpret_cast<uintptr_t>(out_dev) & 3) != 0) { set_error("%s: output must be 4-byte aligned", who); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(plan_dev) & 7) != 0) { set_error("%s: plan_dev must be 8-byte aligned", who); return MDC_EINVAL; }
+    if ((rc = iq_aligned(who, "output", out_dev, 4)) != MDC_OK) return rc;
+    if ((rc = iq_aligned(who, "plan_dev", plan_dev, 8)) != MDC_OK) return rc;
     if (h.ntiles == 0) return MDC_OK;
     if (!iq_dev || !out_dev || !plan_dev) { set_error("%s: null buffer", who); return MDC_EINVAL; }
     const unsigned char* p = static_cast<const unsigned char*>(iq_dev);

@@ -210,6 +210,12 @@ int iq_pair_aligned(const char* who, const char* what, int format, const void* p
     return MDC_EINVAL;
 }
 
+int iq_aligned(const char* who, const char* what, const void* p, int bytes) {
+    if ((reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0) return MDC_OK;
+    set_error("%s: %s must be %d-byte aligned", who, what, bytes);
+    return MDC_EINVAL;
+}
+
 int iq_format_check(const char* who, int format, int64_t hop) {
     const int rc = iq_format_known(who, format);
     if (rc != MDC_OK) return rc;

@@ -199,10 +199,10 @@ int mdc_iq_line_spectra(const void* iq_dev, int format, int64_t pairs_in, const 
         return MDC_EINVAL;
     }
     if ((rc = iq_pair_aligned(who, "iq_dev", format, iq_dev)) != MDC_OK) return rc;
-    if ((reinterpret_cast<uintptr_t>(window_dev) & 1) != 0) { set_error("%s: window_dev must be 2-byte aligned", who); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(rows_dev) & 3) != 0) { set_error("%s: rows_dev must be 4-byte aligned", who); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(mean_dev) & 7) != 0) { set_error("%s: mean_dev must be 8-byte aligned", who); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(jobs_dev) & 7) != 0) { set_error("%s: jobs_dev must be 8-byte aligned", who); return MDC_EINVAL; }
+    if ((rc = iq_aligned(who, "window_dev", window_dev, 2)) != MDC_OK) return rc;
+    if ((rc = iq_aligned(who, "rows_dev", rows_dev, 4)) != MDC_OK) return rc;
+    if ((rc = iq_aligned(who, "mean_dev", mean_dev, 8)) != MDC_OK) return rc;
+    if ((rc = iq_aligned(who, "jobs_dev", jobs_dev, 8)) != MDC_OK) return rc;
     if (njobs == 0) return MDC_OK;
     if (!jobs_dev || !mean_dev) { set_error("%s: null buffer", who); return MDC_EINVAL; }
     if (total > 0 && (!iq_dev || !window_dev || !rows_dev)) { set_error("%s: null buffer", who); return MDC_EINVAL; }

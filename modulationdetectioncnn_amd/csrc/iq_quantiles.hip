@@ -129,12 +129,6 @@ __global__ __launch_bounds__(kQuantThreads) void iq_quantiles_kernel(const unsig
     if (tid < n * W) out[(long)(tid / W) * nfft + column] = prefix[tid / W][c];
 }
 
-int quant_log2(int nfft) {      // log2 of a power of two in 64..4096, else -1
-    for (int l = kQuantMinLog2; l <= kQuantMaxLog2; ++l)
-        if (nfft == 1 << l) return l;
-    return -1;
-}
-
 }  // namespace
 
 }  // namespace mdc
@@ -144,10 +138,11 @@ using namespace mdc;
 int mdc_iq_spectrum_quantiles(const float* power_dev, int64_t rows, int nfft, const int64_t* ranks_host, int nranks, float* out_dev, void* hip_stream) {
     const char* who = "mdc_iq_spectrum_quantiles";
     if (nranks < 0 || nranks > kQuantMaxRanks) { set_error("%s: nranks must be in 0..%d (got %d)", who, kQuantMaxRanks, nranks); return MDC_EINVAL; }
-    if (quant_log2(nfft) < 0) { set_error("%s: nfft must be a power of two in %d..%d (got %d)", who, 1 << kQuantMinLog2, 1 << kQuantMaxLog2, nfft); return MDC_EINVAL; }
+    if (pow2_log2(nfft, kQuantMinLog2, kQuantMaxLog2) < 0) { set_error("%s: nfft must be a power of two in %d..%d (got %d)", who, 1 << kQuantMinLog2, 1 << kQuantMaxLog2, nfft); return MDC_EINVAL; }
     if (rows < 1 || rows > 2147483647LL) { set_error("%s: rows must be in 1..2^31-1 (got %lld)", who, (long long)rows); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(power_dev) & 3) != 0) { set_error("%s: power_dev must be 4-byte aligned", who); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(out_dev) & 3) != 0) { set_error("%s: out_dev must be 4-byte aligned", who); return MDC_EINVAL; }
+    int rc = iq_aligned(who, "power_dev", power_dev, 4);
+    if (rc != MDC_OK) return rc;
+    if ((rc = iq_aligned(who, "out_dev", out_dev, 4)) != MDC_OK) return rc;
     if (nranks == 0) return MDC_OK;
     if (!power_dev || !out_dev || !ranks_host) { set_error("%s: null buffer", who); return MDC_EINVAL; }
     QuantRanks ranks{};

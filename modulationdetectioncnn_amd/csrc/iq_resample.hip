@@ -152,7 +152,7 @@ int mdc_iq_resample(const void* iq_dev, int format, int64_t pairs_in, uint32_t p
         return MDC_EINVAL;
     }
     if ((rc = iq_pair_aligned("mdc_iq_resample", "input", format, iq_dev)) != MDC_OK) return rc;
-    if ((reinterpret_cast<uintptr_t>(out_dev) & 3) != 0) { set_error("mdc_iq_resample: output must be 4-byte aligned"); return MDC_EINVAL; }
+    if ((rc = iq_aligned("mdc_iq_resample", "output", out_dev, 4)) != MDC_OK) return rc;
     if (n_out == 0) return MDC_OK;
     if (!iq_dev || !out_dev) { set_error("mdc_iq_resample: null buffer"); return MDC_EINVAL; }
     ResTaps taps{};

@@ -24,7 +24,7 @@ struct ResPlan {
 int64_t resample_out_count(int64_t pairs, int ntaps, int L, int D) {
     if (pairs < 1) return 0;
     const int64_t lv = (pairs - 1) * L + 1;      // the zero-stuffed length; pairs <= 2^58 is checked
-    return lv >= ntaps ? (lv - ntaps) / D + 1 : 0;
+    return iq_span_count(lv, ntaps, D);
 }
 
 int resample_shape_check(const char* who, int64_t pairs, int ntaps, int L, int D) {

@@ -10,18 +10,11 @@
 //   stage     each thread takes four adjacent pairs at a time (iq_mix.h's load_quad: one 8- or 16-byte vector load, widened to
 //             16-bit full scale), multiplies them by the window's int16 values in int32 (exact, |v| < 2^30), converts to f32 and
 //             writes four complex values into the LDS image.
-//   passes    Stockham autosort, decimation in frequency, radix 4: butterfly t of a pass with stride s = 4^pass reads elements
-//             t + k nfft/4 (k = 0..3: contiguous over the lanes), multiplies outputs 1..3 by w^(j), w^(2j), w^(3j), j = t with its
-//             low log2(s) bits cleared, w = e^{-2 pi i / nfft}, and writes elements q + 4 (t - q) + k s, q = t mod s.  In place:
-//             every thread reads all its butterflies, barrier, writes them, barrier.  An odd log2(nfft) ends with one radix-2 pass.
-//             The LAST pass writes nothing: its outputs are bins t + k nfft/4 (radix 4; t + k nfft/2 for radix 2) in natural order,
-//             and the thread adds their squared magnitudes to its accumulators.  The row's store is then coalesced.
-//   twiddles  three tables w^j, w^2j, w^3j (j < nfft/4) in LDS, filled once per work-group from the first quadrant of the
-//             4096-point circle (iq_fft_twiddles.h: float64 cos / sin rounded to f32 by tools/gen_fft_twiddles.py; the other
-//             quadrants are swaps and sign changes, exact).  Nothing is computed with device sines.
-//   LDS       complex f32 elements, one element of padding after every 16 (spec_slot): the writes of the first pass, element
-//             stride 4 over the lanes, would otherwise put each 16-lane group of a 64-bit store on 4 of its 16 bank pairs.  nfft = 4096:
-//             34 KiB of image + 24 KiB of twiddles, two work-groups per CU.
+//   transform iq_fft.h: every pass but the last in place in the LDS image; the last pass's outputs stay in registers, and the
+//             thread adds their squared magnitudes to its accumulators, bins t + k nfft/4 (t + k nfft/2 after an odd log2's
+//             radix-2 pass).  The row's store is then coalesced.
+//   LDS       the image (iq_fft.h: one element of padding after every 16) and the three twiddle tables.  nfft = 4096: 34 KiB of
+//             image + 24 KiB of twiddles, two work-groups per CU.
 // mdc_iq_line_spectrum is the same kernel with ORDER != 1: the staging alone differs (spec_stage; include/mdc.h, "line spectrum";
 // tests/iq_line_ref.py), everything from the image on is shared -- DESIGN.md 5.19.
 // mdc_iq_line_spectra (iq_line_spectra.hip) is the same kernel again, handed a JOB TABLE: its rows are then the jobs' rows back to
@@ -30,6 +23,7 @@
 // very instructions that serve a call on the slice compute the row, so its bits are that call's by construction, and no pair
 // outside the job is read: every segment of a row the rows function counts lies inside the bound.
 // The call only enqueues; vector memory for every store.
+#include "iq_fft.h"
 #include "iq_mix.h"
 
 namespace mdc {
@@ -38,26 +32,8 @@ namespace {
 
 constexpr int kSpecMinLog2 = 6, kSpecMaxLog2 = 12, kSpecMaxAvg = 4096;
 constexpr long kSpecGridCap = 2048;      // work-groups; beyond it the kernel strides (_cabi.SPECTROGRAM_GRID_CAP)
-constexpr int kTwQuadrant = 1024;        // entries of iq_fft_twiddles.h: a quarter of the 4096-point circle
-
-__device__ const unsigned d_tw[2 * kTwQuadrant] = {
-#include "iq_fft_twiddles.h"
-};
 
 __host__ __device__ constexpr int spec_threads(int log2n) { return (1 << log2n) / 4 < 64 ? 64 : (1 << log2n) / 4 > 512 ? 512 : (1 << log2n) / 4; }
-__host__ __device__ constexpr int spec_slot(int e) { return e + (e >> 4); }
-
-// e^{-2 pi i J / 4096}, 0 <= J < 3072
-__device__ __forceinline__ float2 spec_twiddle(int J) {
-    const int j = J & (kTwQuadrant - 1), quadrant = J >> 10;
-    const float c = __uint_as_float(d_tw[2 * j]), s = __uint_as_float(d_tw[2 * j + 1]);
-    return quadrant == 0 ? make_float2(c, -s) : quadrant == 1 ? make_float2(-s, -c) : make_float2(-c, s);
-}
-
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cmul(float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
-__device__ __forceinline__ float2 cmuli(float2 a) { return make_float2(-a.y, a.x); }      // a * i
 __device__ __forceinline__ float norm2(float2 a) { return a.x * a.x + a.y * a.y; }
 
 // What is transformed (ORDER; include/mdc.h, "line spectrum"): the widened pair itself (1: mdc_iq_spectrogram), or an exact
@@ -93,18 +69,13 @@ __global__ __launch_bounds__(spec_threads(LOG2N)) void iq_spectrogram_kernel(con
     constexpr int N = 1 << LOG2N, NB = N / 4, T = spec_threads(LOG2N);
     constexpr int B = (NB + T - 1) / T;              // radix-4 butterflies (and staged quads) per thread
     constexpr bool kWhole = NB % T == 0;             // false only for nfft 64 and 128: fewer butterflies than lanes
-    constexpr bool kOdd = (LOG2N & 1) != 0;
-    constexpr int kStoredPasses = kOdd ? LOG2N / 2 : LOG2N / 2 - 1;
-    constexpr int B2 = N / 2 / T;                    // radix-2 butterflies per thread in the last pass of an odd log2
-    __shared__ float2 x[spec_slot(N)];
+    constexpr int R = fft_last_radix(LOG2N), NL = N / R;      // the last pass: NL butterflies of R outputs
+    constexpr int BL = (NL + T - 1) / T;             // of them per thread
+    constexpr bool kLastWhole = NL % T == 0;
+    __shared__ float2 x[fft_slot(N)];
     __shared__ float2 tw[3 * NB];
     const int tid = threadIdx.x;
-    for (int j = tid; j < NB; j += T) {
-        const int J = j << (kSpecMaxLog2 - LOG2N);
-        tw[j] = spec_twiddle(J);
-        tw[NB + j] = spec_twiddle(2 * J);
-        tw[2 * NB + j] = spec_twiddle(3 * J);
-    }
+    fft_fill_twiddles<LOG2N, T>(tw, tid);
 
     for (long grow = blockIdx.x; grow < rows; grow += gridDim.x) {
         const unsigned char* src = iq;      // the capture, or with a job table the row's job: all uniform over the work-group
@@ -119,9 +90,9 @@ __global__ __launch_bounds__(spec_threads(LOG2N)) void iq_spectrogram_kernel(con
             bound = jobs[lo].pairs;
             row = grow - jobs[lo].first_row;
         }
-        float acc[4 * B];
+        float acc[R * BL];
 #pragma unroll
-        for (int i = 0; i < 4 * B; ++i) acc[i] = 0.f;
+        for (int i = 0; i < R * BL; ++i) acc[i] = 0.f;
         for (int sg = 0; sg < avg; ++sg) {
             const long start = (row * avg + sg) * hop;
             __syncthreads();      // the twiddles are in place; the previous segment's last pass has read its image
@@ -134,78 +105,21 @@ __global__ __launch_bounds__(spec_threads(LOG2N)) void iq_spectrogram_kernel(con
                     short w[4];
                     __builtin_memcpy(w, window + 4 * q, sizeof(w));
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) x[spec_slot(4 * q + e)] = spec_stage<ORDER>(I[e], Q[e], (int)w[e]);
+                    for (int e = 0; e < 4; ++e) x[fft_slot(4 * q + e)] = spec_stage<ORDER>(I[e], Q[e], (int)w[e]);
                 }
             }
             __syncthreads();
-#pragma unroll
-            for (int pass = 0; pass < kStoredPasses; ++pass) {
-                const int s = 1 << (2 * pass);
-                float2 y[B][4];
-#pragma unroll
-                for (int i = 0; i < B; ++i) {
-                    const int t = tid + i * T;
-                    if (kWhole || t < NB) {
-                        const float2 a = x[spec_slot(t)], b = x[spec_slot(t + NB)], c = x[spec_slot(t + 2 * NB)], d = x[spec_slot(t + 3 * NB)];
-                        const float2 apc = cadd(a, c), amc = csub(a, c), bpd = cadd(b, d), jbmd = cmuli(csub(b, d));
-                        const int j = t & ~(s - 1);
-                        y[i][0] = cadd(apc, bpd);
-                        y[i][1] = cmul(csub(amc, jbmd), tw[j]);
-                        y[i][2] = cmul(csub(apc, bpd), tw[NB + j]);
-                        y[i][3] = cmul(cadd(amc, jbmd), tw[2 * NB + j]);
-                    }
-                }
-                __syncthreads();
-#pragma unroll
-                for (int i = 0; i < B; ++i) {
-                    const int t = tid + i * T;
-                    if (kWhole || t < NB) {
-                        const int q = t & (s - 1), base = q + 4 * (t - q);
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) x[spec_slot(base + k * s)] = y[i][k];
-                    }
-                }
-                __syncthreads();
-            }
-            if (!kOdd) {      // the last radix-4 pass: stride nfft/4, no twiddles, bins t + k nfft/4
-#pragma unroll
-                for (int i = 0; i < B; ++i) {
-                    const int t = tid + i * T;
-                    if (kWhole || t < NB) {
-                        const float2 a = x[spec_slot(t)], b = x[spec_slot(t + NB)], c = x[spec_slot(t + 2 * NB)], d = x[spec_slot(t + 3 * NB)];
-                        const float2 apc = cadd(a, c), amc = csub(a, c), bpd = cadd(b, d), jbmd = cmuli(csub(b, d));
-                        acc[4 * i + 0] += norm2(cadd(apc, bpd));
-                        acc[4 * i + 1] += norm2(csub(amc, jbmd));
-                        acc[4 * i + 2] += norm2(csub(apc, bpd));
-                        acc[4 * i + 3] += norm2(cadd(amc, jbmd));
-                    }
-                }
-            } else {          // the last radix-2 pass: stride nfft/2, bins t and t + nfft/2
-#pragma unroll
-                for (int i = 0; i < B2; ++i) {
-                    const int t = tid + i * T;
-                    const float2 a = x[spec_slot(t)], b = x[spec_slot(t + N / 2)];
-                    acc[2 * i + 0] += norm2(cadd(a, b));
-                    acc[2 * i + 1] += norm2(csub(a, b));
-                }
-            }
+            float2 y[B][4];
+            fft_stored_passes<LOG2N, B, T>(x, tw, 0, tid, y);
+            fft_last_pass<LOG2N, BL, T>(x, 0, tid, [&](int i, int k, int, float2 v) { acc[R * i + k] += norm2(v); });
         }
         float* out = power + grow * N;
-        if (!kOdd) {
 #pragma unroll
-            for (int i = 0; i < B; ++i) {
-                const int t = tid + i * T;
-                if (kWhole || t < NB) {
+        for (int i = 0; i < BL; ++i) {
+            const int t = tid + i * T;
+            if (kLastWhole || t < NL) {
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) out[t + k * NB] = acc[4 * i + k] * gain;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < B2; ++i) {
-                const int t = tid + i * T;
-                out[t] = acc[2 * i] * gain;
-                out[t + N / 2] = acc[2 * i + 1] * gain;
+                for (int k = 0; k < R; ++k) out[t + k * NL] = acc[R * i + k] * gain;
             }
         }
     }
@@ -221,28 +135,8 @@ int spec_launch(const unsigned char* iq, int64_t pairs, int64_t hop, int avg, co
     return MDC_OK;
 }
 
-template <int FMT, int ORDER>
-int spec_launch_fmt(int log2n, const unsigned char* iq, int64_t pairs, int64_t hop, int avg, const int16_t* window, float gain, float* power, int64_t rows,
-                    const mdc_iq_line_job* jobs, int64_t njobs, hipStream_t s) {
-    switch (log2n) {
-        case 6: return spec_launch<FMT, 6, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
-        case 7: return spec_launch<FMT, 7, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
-        case 8: return spec_launch<FMT, 8, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
-        case 9: return spec_launch<FMT, 9, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
-        case 10: return spec_launch<FMT, 10, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
-        case 11: return spec_launch<FMT, 11, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
-        default: return spec_launch<FMT, 12, ORDER>(iq, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
-    }
-}
-
-int spec_log2(int nfft) {      // log2 of a power of two in 64..4096, else -1
-    for (int l = kSpecMinLog2; l <= kSpecMaxLog2; ++l)
-        if (nfft == 1 << l) return l;
-    return -1;
-}
-
 int spec_shape_check(const char* who, int64_t pairs, int nfft, int64_t hop, int avg) {
-    if (spec_log2(nfft) < 0) { set_error("%s: nfft must be a power of two in %d..%d (got %d)", who, 1 << kSpecMinLog2, 1 << kSpecMaxLog2, nfft); return MDC_EINVAL; }
+    if (pow2_log2(nfft, kSpecMinLog2, kSpecMaxLog2) < 0) { set_error("%s: nfft must be a power of two in %d..%d (got %d)", who, 1 << kSpecMinLog2, 1 << kSpecMaxLog2, nfft); return MDC_EINVAL; }
     if (hop < 1) { set_error("%s: hop must be >= 1 pair (got %lld)", who, (long long)hop); return MDC_EINVAL; }
     if (avg < 1 || avg > kSpecMaxAvg) { set_error("%s: avg must be in 1..%d (got %d)", who, kSpecMaxAvg, avg); return MDC_EINVAL; }
     if (pairs < 0) { set_error("%s: negative pair count", who); return MDC_EINVAL; }
@@ -250,21 +144,22 @@ int spec_shape_check(const char* who, int64_t pairs, int nfft, int64_t hop, int 
 }
 
 int64_t spec_rows(int64_t pairs, int nfft, int64_t hop, int avg) {
-    const int64_t segs = pairs >= nfft ? (pairs - nfft) / hop + 1 : 0;
-    return segs / avg;
+    return iq_span_count(pairs, nfft, hop) / avg;
 }
 
-// format and order as template arguments; jobs == nullptr: the rows of the capture itself
+// format, log2 nfft and order as template arguments; jobs == nullptr: the rows of the capture itself
 int spec_dispatch(int format, int order, int log2n, const unsigned char* p, int64_t pairs, int64_t hop, int avg, const int16_t* window, float gain, float* power,
                   int64_t rows, const mdc_iq_line_job* jobs, int64_t njobs, hipStream_t s) {
     return with_format(format, [&](auto fmt) {
-        constexpr int F = decltype(fmt)::value;
-        switch (order) {
-            case 0: return spec_launch_fmt<F, 0>(log2n, p, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
-            case 1: return spec_launch_fmt<F, 1>(log2n, p, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
-            case 2: return spec_launch_fmt<F, 2>(log2n, p, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
-            default: return spec_launch_fmt<F, 4>(log2n, p, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
-        }
+        return with_log2<kSpecMinLog2, kSpecMaxLog2>(log2n, [&](auto l2) {
+            constexpr int F = decltype(fmt)::value, L = decltype(l2)::value;
+            switch (order) {
+                case 0: return spec_launch<F, L, 0>(p, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+                case 1: return spec_launch<F, L, 1>(p, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+                case 2: return spec_launch<F, L, 2>(p, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+                default: return spec_launch<F, L, 4>(p, pairs, hop, avg, window, gain, power, rows, jobs, njobs, s);
+            }
+        });
     });
 }
 
@@ -275,7 +170,7 @@ int iq_spec_shape_check(const char* who, int64_t pairs, int nfft, int64_t hop, i
 int64_t iq_spec_rows(int64_t pairs, int nfft, int64_t hop, int avg) { return spec_rows(pairs, nfft, hop, avg); }
 int iq_spec_jobs_launch(const void* iq, int format, int order, int nfft, int64_t hop, int avg, const int16_t* window, float gain, float* power, int64_t rows,
                         const mdc_iq_line_job* jobs_dev, int64_t njobs, hipStream_t s) {
-    return spec_dispatch(format, order, spec_log2(nfft), static_cast<const unsigned char*>(iq), 0, hop, avg, window, gain, power, rows, jobs_dev, njobs, s);
+    return spec_dispatch(format, order, pow2_log2(nfft, kSpecMinLog2, kSpecMaxLog2), static_cast<const unsigned char*>(iq), 0, hop, avg, window, gain, power, rows, jobs_dev, njobs, s);
 }
 
 }  // namespace mdc
@@ -300,12 +195,12 @@ static int spec_run(const char* who, const void* iq_dev, int format, int64_t pai
         return MDC_EINVAL;
     }
     if ((rc = iq_pair_aligned(who, "iq_dev", format, iq_dev)) != MDC_OK) return rc;
-    if ((reinterpret_cast<uintptr_t>(window_dev) & 1) != 0) { set_error("%s: window_dev must be 2-byte aligned", who); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(power_dev) & 3) != 0) { set_error("%s: power_dev must be 4-byte aligned", who); return MDC_EINVAL; }
+    if ((rc = iq_aligned(who, "window_dev", window_dev, 2)) != MDC_OK) return rc;
+    if ((rc = iq_aligned(who, "power_dev", power_dev, 4)) != MDC_OK) return rc;
     if (rows == 0) return MDC_OK;
     if (!iq_dev || !window_dev || !power_dev) { set_error("%s: null buffer", who); return MDC_EINVAL; }
     const float gain = (float)((double)scale / (double)avg);
-    const int log2n = spec_log2(nfft);
+    const int log2n = pow2_log2(nfft, kSpecMinLog2, kSpecMaxLog2);
     const unsigned char* p = static_cast<const unsigned char*>(iq_dev);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     return guarded(who, [&]() -> int { return spec_dispatch(format, order, log2n, p, pairs_in, hop, avg, window_dev, gain, power_dev, rows, nullptr, 0, s); });

@@ -233,11 +233,17 @@ int iq_norm_launch(const uint8_t* iq, int64_t n, int64_t hop, float level, int f
 // iq_formats.hip: what every raw-I/Q entry states once
 constexpr long kIqGridCap = 16384;      // work-groups of the window kernels; beyond it they stride
 int iq_pair_bytes(int format);      // 2 / 2 / 4; 0 for an unknown format
+// how many spans of `span` pairs, `step` pairs apart, lie inside `pairs` pairs: the outputs of a decimating filter, the segments
+// of a spectrogram
+constexpr int64_t iq_span_count(int64_t pairs, int64_t span, int64_t step) { return pairs >= span ? (pairs - span) / step + 1 : 0; }
 // the two checks every raw-I/Q entry makes of its capture, each where the entry's order of errors has it:
 int iq_format_known(const char* who, int format);      // else `who: unknown sample format ...`
 // p starts on a whole pair of a known format, else `who: <what> must start on a whole (I,Q) pair ...` (what: the entry's word
 // for the capture, "input" or "iq_dev")
 int iq_pair_aligned(const char* who, const char* what, int format, const void* p);
+// any other buffer: p is a multiple of `bytes` (a power of two), else `who: <what> must be <bytes>-byte aligned` (what: the entry's
+// word for the buffer, its parameter's name or "output")
+int iq_aligned(const char* who, const char* what, const void* p, int bytes);
 int iq_format_check(const char* who, int format, int64_t hop);
 // the wave-per-window normaliser's MDC_IQ_CU8 instantiation with the record in 32-bit fields (n > 0; x or stats may be NULL)
 int iq_norm_wave_launch(const uint8_t* iq, int64_t n, int64_t hop, float level, int flags, float* x, mdc_iq_window_stats* stats, hipStream_t s);
@@ -253,6 +259,22 @@ inline int with_format(int format, Fn&& fn) {
     if (format == MDC_IQ_CU8) return fn(std::integral_constant<int, MDC_IQ_CU8>{});
     if (format == MDC_IQ_CI8) return fn(std::integral_constant<int, MDC_IQ_CI8>{});
     return fn(std::integral_constant<int, MDC_IQ_CI16>{});
+}
+// log2 of a power of two in 2^lo..2^hi, else -1
+inline int pow2_log2(int value, int lo, int hi) {
+    for (int l = lo; l <= hi; ++l)
+        if (value == 1 << l) return l;
+    return -1;
+}
+// fn(std::integral_constant<int, L>) for L = log2, which pow2_log2(., LO, HI) has given: the runtime log2 as a template argument
+template <int LO, int HI, class Fn>
+inline int with_log2(int log2, Fn&& fn) {
+    if constexpr (LO < HI) {
+        if (log2 == LO) return fn(std::integral_constant<int, LO>{});
+        return with_log2<LO + 1, HI>(log2, fn);
+    } else {
+        return fn(std::integral_constant<int, HI>{});
+    }
 }
 // flags[i] = 1 iff frame i of x holds a NaN / +-Inf sample (else 0), *count += their number (count may be NULL); poison: the
 // flagged frames' probability rows become NaN and their labels 0 (probs / labels may be NULL).  mdc_forward_checked.

@@ -4,7 +4,7 @@ iq_line_ref.py and iq_channelizer_ref.py are the float64 DEFINITION and the head
 kernels' own rounding noise: the same operation count in the same number format, every operation rounded on its own (numpy
 never fuses a multiply into an add), real and imaginary parts kept as separate float32 arrays.
 
-  fft_stockham4   the passes as the head of csrc/iq_spectrogram.hip describes them: Stockham autosort, decimation in
+  fft_stockham4   the passes as the head of csrc/iq_fft.h describes them: Stockham autosort, decimation in
                   frequency, radix 4, a last radix-2 pass for an odd log2 n, the three tables w^j, w^2j, w^3j read from the first
                   quadrant of the 4096-point circle as tools/gen_fft_twiddles.py rounds it.  n = 8 .. 4096.
   fft_radix2      an unrelated algorithm in the same format: plain recursive radix 2, decimation in time.

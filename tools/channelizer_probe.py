@@ -13,7 +13,7 @@ per channel, each with shift -k / M, decimation D and frontend.design_lowpass(D)
 Timing: device events around `reps` back-to-back launches after a warm-up, the median of `rounds` such windows, the cases
 alternating within every round.  Needs the GPU; prints a table and one JSON line.
 
-    python tools/channelizer_probe.py [--log2-pairs 24] [--rounds 5] [--reps 10] [--out FILE]
+    python tools/channelizer_probe.py [--log2-pairs 24] [--rounds 5] [--reps 10] [--out FILE] [--lib PATH]
 """
 import argparse
 import json
@@ -48,12 +48,15 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", default=None, help="also write the JSON record to this file")
+    ap.add_argument("--lib", default=None, help="time this build of libmdc.so instead of the tree's (an A/B against a saved library)")
     a = ap.parse_args()
     import torch
     from modulationdetectioncnn_amd import _cabi, frontend
     if not torch.cuda.is_available():
         raise SystemExit("channelizer_probe needs the GPU: a CPU run says nothing about speed")
     P = 1 << a.log2_pairs
+    if a.lib:
+        _cabi.LIB_PATHS["product"] = os.path.abspath(a.lib)      # before the first use: lib() loads once
     lib = _cabi.lib()
     stream = torch.cuda.current_stream().cuda_stream
     g = torch.Generator(device="cuda").manual_seed(1)

@@ -24,7 +24,7 @@ measurements, all in this one process:
 
 Needs the GPU; prints tables and one JSON line.
 
-    python tools/line_spectra_probe.py [--log2-pairs 22] [--reps 20] [--boxes 7,256] [--out FILE]
+    python tools/line_spectra_probe.py [--log2-pairs 22] [--reps 20] [--boxes 7,256] [--out FILE] [--lib PATH]
 """
 import argparse
 import json
@@ -58,6 +58,7 @@ def main():
     ap.add_argument("--boxes", default="7,256")
     ap.add_argument("--out", default=None, help="also write the JSON record to this file")
     ap.add_argument("--trace-hint", action="store_true", help="print the profiler command that splits the calls' time per kernel, and exit")
+    ap.add_argument("--lib", default=None, help="time this build of libmdc.so instead of the tree's (an A/B against a saved library)")
     a = ap.parse_args()
     if a.trace_hint:
         print("rocprofv3 --kernel-trace --stats -d profile_out -- python tools/line_spectra_probe.py --reps 5")
@@ -69,6 +70,8 @@ def main():
     if a.reps < 20:
         print(f"note: {a.reps} repetitions; the figures quoted in DESIGN.md 5.23 want at least 20")
     P = 1 << a.log2_pairs
+    if a.lib:
+        _cabi.LIB_PATHS["product"] = os.path.abspath(a.lib)      # before the first use: lib() loads once
     lib = _cabi.lib()
     stream = torch.cuda.current_stream().cuda_stream
     g = torch.Generator(device="cuda").manual_seed(1)
