@@ -67,7 +67,9 @@ extern "C" {
                                   at several orders, and their float64 means, in one call); mdc_iq_find_lines, mdc_iq_line_band,
                                   mdc_iq_line_record (the line search of S spectra on the device);
                                   mdc_iq_balance / mdc_iq_balance_stats / mdc_iq_balance_blocks, mdc_iq_balance_coeffs (a
-                                  receiver's I/Q imbalance and DC offset, measured and corrected in exact integers) */
+                                  receiver's I/Q imbalance and DC offset, measured and corrected in exact integers);
+                                  mdc_iq_cf32_histogram / mdc_iq_cf32_quantize (a complex float32 capture: the exponent
+                                  histogram of its components, and one exact rounding into an MDC_IQ_CI16 stream) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -356,8 +358,8 @@ MDC_API int mdc_iq_u8_windows_norm(const uint8_t* iq_dev, int64_t n, int64_t hop
  * x_dev (n,2,128) f32, 8-byte aligned; stats64_dev (n), 16-byte aligned; in mdc_iq_windows_norm each may be NULL, not both.
  * level, flags as mdc_iq_u8_windows_norm.  n == 0 is MDC_OK.  Both calls only enqueue on hip_stream (no synchronisation, no
  * allocation: capturable in a hipGraph) and run on the current device.
- * Float captures (cf32) are not served: they need their own decision on non-finite samples and on what "exact statistics"
- * means.  Big-endian 16-bit samples must be swapped by the caller. */
+ * Float captures (cf32) are no fourth format of these entries: mdc_iq_cf32_quantize, below, turns one into an MDC_IQ_CI16 stream
+ * once, in front of them.  Big-endian 16-bit samples must be swapped by the caller. */
 enum { MDC_IQ_CU8 = 0, MDC_IQ_CI8 = 1, MDC_IQ_CI16 = 2 };
 
 typedef struct mdc_iq_window_stats64 {   /* 32 B */
@@ -369,6 +371,39 @@ typedef struct mdc_iq_window_stats64 {   /* 32 B */
 MDC_API int mdc_iq_windows(const void* iq_dev, int format, int64_t n, int64_t hop, float scale, float* x_dev, void* hip_stream);
 MDC_API int mdc_iq_windows_norm(const void* iq_dev, int format, int64_t n, int64_t hop, float level, int flags,
                            float* x_dev, mdc_iq_window_stats64* stats64_dev, void* hip_stream);
+
+/* ---- float captures: exponent histogram and exact quantiser of complex float32 into MDC_IQ_CI16 (additive in ABI 5) ------------
+ * GNU Radio's file sink, UHD's fc32 and SigMF's cf32_le write interleaved complex float32.  Such a capture is converted ONCE, at
+ * the door, into an ordinary MDC_IQ_CI16 stream: everything behind it stays exact-integer and bit-reproducible.  Two decisions
+ * make that conversion as well defined as the integer entries (the numpy restatement is tests/iq_cf32_ref.py):
+ *   input       iq_dev holds 2 * pairs_in little-endian IEEE-754 binary32 values, I0 Q0 I1 Q1 ..., aligned to ONE PAIR (8 bytes)
+ *               and to nothing more: a buffer that starts 8 bytes off a 16-byte boundary is served.
+ *   histogram   the "exact statistics" of a float capture are integer counts: for every component with bit pattern b,
+ *               hist[(b >> 23) & 0xFF] += 1, the biased exponent byte.  Bin 0 holds zeros and denormals; bin e in 1 .. 254 the
+ *               normal numbers with 2^(e-127) <= |x| < 2^(e-126); bin 255 NaN and +-Inf.  The bins sum to 2 * pairs_in.  The call
+ *               ADDS into hist_dev (256 uint64, 8-byte aligned): the caller zeroes it, and a file read in chunks accumulates.
+ *               Counts are order-free: bit-identical on every run.  They answer "which power-of-two gain?" on the host, also
+ *               for a capture with a few glitch samples that a plain maximum would be ruined by (the library's Python mirror
+ *               has the design: frontend.design_cf32_gain).
+ *   quantiser   gain must be a finite f32 in [2^-126, 2^125], else MDC_EINVAL.  Per pair: if either component is non-finite
+ *               (exponent byte 255) the pair becomes (0, 0) and counts[0] += 1.  Otherwise, per component: t = x * gain as ONE
+ *               correctly rounded f32 multiplication; r = rintf(t), to nearest, ties to even; if r > 32767 or r < -32768,
+ *               counts[1] += 1; the output is clamp(r, -32768, 32767) as int16.  A finite x whose product overflows to +-Inf is
+ *               clipped and counted, not treated as non-finite.  With a power-of-two gain the multiplication is exact and the
+ *               quantisation is one rounding per sample.  In the gain's range a denormal x times the gain is below 2^-126 *
+ *               2^125 = 0.5 in magnitude and rounds to 0, as a denormal flushed to zero does -- and a product that is itself
+ *               denormal rounds to 0 either way: the result does not depend on whether denormals are flushed.
+ *               counts_dev (2 uint64, 8-byte aligned: non-finite pairs, clipped components) is ADDED to and may be NULL.
+ *   output      pairs_in int16 pairs, out_dev 4-byte aligned, not overlapping the input.  The pass is pointwise: a capture
+ *               converted in pieces gives the same bits as in one call.
+ * pairs_in <= 2^40 per call (the work-groups count in 32 bits), otherwise MDC_EINVAL.  Every argument error is MDC_EINVAL with a
+ * mdc_last_error() text before any device call; pairs_in == 0 is MDC_OK with nothing launched.  Both calls only enqueue on
+ * hip_stream (no synchronisation, no allocation, no memset: capturable in a hipGraph) and run on the current device.
+ * 0 dBFS of everything computed from the result is the float amplitude 32768 / gain.  A 16-bit stream carries 16 bits: an
+ * emitter more than about 80 dB below the capture's peak is lost to the rounding. */
+MDC_API int mdc_iq_cf32_histogram(const float* iq_dev, int64_t pairs_in, uint64_t* hist_dev /* 256 */, void* hip_stream);
+MDC_API int mdc_iq_cf32_quantize(const float* iq_dev, int64_t pairs_in, float gain, int16_t* out_dev,
+                           uint64_t* counts_dev /* 2, may be NULL */, void* hip_stream);
 
 /* ---- I/Q balance: a receiver's gain / phase imbalance and DC offset, measured and corrected (additive in ABI 5) -----------------
  * A zero-IF receiver's I and Q rails differ in gain by a fraction of a dB to a dB and are a few degrees off 90: every emitter

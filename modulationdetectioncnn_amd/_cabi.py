@@ -43,6 +43,7 @@ EXPORTS = [
     "mdc_iq_spectrogram_components", "mdc_iq_spectrogram_components_workspace",
     "mdc_iq_line_spectra", "mdc_iq_line_spectra_rows", "mdc_iq_find_lines",
     "mdc_iq_balance", "mdc_iq_balance_stats", "mdc_iq_balance_blocks",
+    "mdc_iq_cf32_histogram", "mdc_iq_cf32_quantize",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
@@ -83,6 +84,10 @@ BALANCE_MIN_BLOCK, BALANCE_MAX_BLOCK = 64, 1 << 20
 BALANCE_MAX_DC, BALANCE_MAX_ROW_ABS_SUM, BALANCE_ONE = 32768, 32767, 16384
 BALANCE_STATS_GRID_CAP, BALANCE_GRID_CAP, BALANCE_GROUP_PAIRS = 2048, 2048, 1024
 IQ_BALANCE_COEFFS = np.dtype([("dc_i", np.int32), ("dc_q", np.int32), ("m00", np.int32), ("m01", np.int32), ("m10", np.int32), ("m11", np.int32)])
+# mdc_iq_cf32_histogram / mdc_iq_cf32_quantize: limits of include/mdc.h (the gain's range, pairs per call), and the kernels' grid
+# (csrc/iq_cf32.hip: at most kCfGridCap work-groups, each taking CF32_GROUP_PAIRS pairs per stride step)
+CF32_MIN_GAIN, CF32_MAX_GAIN, CF32_MAX_PAIRS = 2.0 ** -126, 2.0 ** 125, 1 << 40
+CF32_GRID_CAP, CF32_GROUP_PAIRS = 1024, 1024
 # mdc_iq_resample: limits of include/mdc.h (taps and decimation as the DDC's; the sum |h| bound holds per BRANCH), and the kernel's
 # tiling (csrc/iq_resample.hip): a tile is ((RESAMPLE_TILE_PAIRS - ceil(T / L)) // D) * L outputs, RESAMPLE_GRID_CAP work-groups
 RESAMPLE_MAX_INTERPOLATE, RESAMPLE_MAX_DECIMATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BRANCH_ABS_SUM = 32, 256, 1024, 65535
@@ -219,7 +224,9 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_iq_line_spectra", [vp, i32, i64, vp, vp, i64, vp, i32, i32, i64, i32, vp, C.c_float, vp, i64, vp, vp]),
                        ("mdc_iq_find_lines", [vp, i64, i32, vp, vp, vp, vp]),
                        ("mdc_iq_balance_stats", [vp, i32, i64, i64, vp, i64, vp]),
-                       ("mdc_iq_balance", [vp, i32, i64, vp, vp, vp])):
+                       ("mdc_iq_balance", [vp, i32, i64, vp, vp, vp]),
+                       ("mdc_iq_cf32_histogram", [vp, i64, vp, vp]),
+                       ("mdc_iq_cf32_quantize", [vp, i64, C.c_float, vp, vp, vp])):
         fn = getattr(L, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, i32

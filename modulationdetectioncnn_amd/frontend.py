@@ -217,6 +217,139 @@ def window_stats_iq(iq, sample_format, hop: int = HOP_FRAME, remove_dc: bool = T
     return stats64_tensor_to_numpy(_windows(iq, _cabi.IQ_ENTRIES, sample_format_id(sample_format), hop, 1.0, flags, False, True, device)[1])
 
 
+# ---- float captures (mdc_iq_cf32_histogram / mdc_iq_cf32_quantize): complex float32 -> an ordinary "ci16" stream, once, at the door ----
+def _device_cf32(iq, device=None):
+    """A complex float32 capture -- complex64 (n,), float32 (2n,) interleaved or float32 (n, 2); numpy or torch, host or device --
+    as a flat float32 device tensor I0 Q0 I1 Q1 ... starting on a whole pair.  Big-endian numpy input is byte-swapped on the host
+    (as host_samples does); any other dtype is a TypeError, any other shape a ValueError."""
+    import torch
+    if isinstance(iq, torch.Tensor):
+        t = iq
+        if t.dtype not in (torch.complex64, torch.float32):
+            raise TypeError(f"a cf32 capture must be complex64 or float32, got {t.dtype}")
+    else:
+        a = np.asarray(iq)
+        if not ((a.dtype.kind == "c" and a.dtype.itemsize == 8) or (a.dtype.kind == "f" and a.dtype.itemsize == 4)):
+            raise TypeError(f"a cf32 capture must be complex64 or float32, got {a.dtype}")
+        t = torch.from_numpy(np.ascontiguousarray(a.astype(a.dtype.newbyteorder("<"), copy=False)))
+    if t.dtype == torch.complex64:
+        if t.dim() != 1:
+            raise ValueError(f"a complex64 capture must have shape (n,), got {tuple(t.shape)}")
+    elif not ((t.dim() == 1 and t.numel() % 2 == 0) or (t.dim() == 2 and t.shape[1] == 2)):
+        raise ValueError(f"a float32 capture must have shape (2n,) or (n, 2), got {tuple(t.shape)}")
+    if not t.is_cuda:
+        t = t.to(device if device is not None else "cuda:0")
+    t = t.contiguous()
+    t = (torch.view_as_real(t) if t.dtype == torch.complex64 else t).reshape(-1)
+    if t.data_ptr() % 8:
+        t = t.clone()       # a view starting inside a pair of a larger buffer: the ABI wants whole (I,Q) pairs
+    return t
+
+
+def _cf32_histogram_into(t, hist):
+    """mdc_iq_cf32_histogram of the flat float32 device tensor t, added into the uint64[256] device tensor hist"""
+    import torch
+    pairs = t.numel() // 2
+    with torch.cuda.device(t.device):
+        _cabi.check(_cabi.lib().mdc_iq_cf32_histogram(t.data_ptr() if pairs else None, pairs, hist.data_ptr(),
+                                                      torch.cuda.current_stream(t.device).cuda_stream))
+    return hist
+
+
+def cf32_histogram(iq, hist=None, device=None):
+    """The exact statistics of a complex float32 capture (mdc_iq_cf32_histogram, include/mdc.h): the uint64[256] device tensor
+    of how many components carry each biased exponent byte -- bin 0 zeros and denormals, bin e the normal numbers with
+    2^(e-127) <= |x| < 2^(e-126), bin 255 NaN and +-Inf.  iq: complex64 (n,), float32 (2n,) or (n, 2), numpy or torch.  hist: a
+    tensor an earlier call returned; this capture's counts are ADDED to it (a file read in chunks) and it is returned.  Integer
+    counts: bit-identical on every run.  Enqueues on torch's current stream without synchronising."""
+    import torch
+    t = _device_cf32(iq, device)
+    if hist is None:
+        hist = torch.zeros(256, dtype=torch.int64, device=t.device).view(torch.uint64)
+    elif not (isinstance(hist, torch.Tensor) and hist.dtype == torch.uint64 and hist.shape == (256,) and hist.is_contiguous()
+              and hist.device == t.device):
+        raise ValueError("hist must be the contiguous uint64[256] tensor of an earlier call, on the capture's device")
+    return _cf32_histogram_into(t, hist)
+
+
+def _host_histogram(hist) -> np.ndarray:
+    h = hist.cpu().numpy() if hasattr(hist, "cpu") else np.asarray(hist)
+    if h.dtype.kind not in "iu" or h.shape != (256,):
+        raise ValueError("hist must hold 256 integer counts")
+    return h.astype(np.uint64, copy=False)
+
+
+def design_cf32_gain(hist, clip_fraction: float = 0.0) -> float:
+    """The power-of-two gain of quantize_cf32 from a capture's exponent histogram (cf32_histogram's tensor, or 256 integers).
+    Walk down from bin 254 while the components in the bins above stay within floor(clip_fraction * finite components): the
+    bin the walk stops at is the top kept bin e -- with clip_fraction 0 the highest occupied one -- and every kept component
+    has |x| < 2^(e-126).  gain = 2^clamp(140 - e, -126, 125): every kept component then has |x * gain| < 2^14, so nothing kept
+    can clip and the largest kept ones use 13 to 14 bits (the clamp keeps the gain inside mdc_iq_cf32_quantize's range; only its
+    upper end can bind, for a capture whose top bin is below 15: |x| < 2^-111).  clip_fraction > 0 gives up that share of the components to a few glitch
+    samples, which then clip (and are counted) instead of costing everyone else their resolution.  No normal component at all
+    (an empty, all-zero or denormal-only capture): 1.0."""
+    p = float(clip_fraction)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"clip_fraction must be in [0, 1) (got {clip_fraction!r})")
+    h = [int(v) for v in _host_histogram(hist)]
+    budget = int(p * sum(h[:255]))      # floor: both factors are non-negative
+    above, e = 0, 254
+    while e >= 1 and above + h[e] <= budget:
+        above += h[e]
+        e -= 1
+    if e < 1:
+        return 1.0
+    return float(2.0 ** min(max(140 - e, -126), 125))
+
+
+def quantize_cf32(iq, full_scale=None, clip_fraction: float = 0.0, nonfinite: str = "zero", device=None, return_report: bool = False):
+    """A complex float32 capture (GNU Radio's file sink, UHD's fc32, SigMF's cf32_le) as an ordinary "ci16" capture: the flat
+    int16 device tensor I0 Q0 I1 Q1 ... of mdc_iq_cf32_quantize (include/mdc.h) -- per component ONE correctly rounded
+    multiplication by the gain, ONE rounding to nearest (ties to even), saturation to -32768 .. 32767.  iq: complex64 (n,),
+    float32 (2n,) or (n, 2); numpy or torch, host or device.
+    full_scale: the float amplitude that becomes 32768 (UHD and GNU Radio write +-1.0 as ADC full scale): gain =
+    float32(32768 / full_scale).  None measures instead: cf32_histogram, then design_cf32_gain(hist, clip_fraction) -- a power of
+    two, so the multiplication is exact, with the capture's peak in [2^13, 2^14).
+    nonfinite: a pair with a NaN or +-Inf component becomes (0, 0) and is counted ("zero"), or the call raises
+    NonFiniteInputError with the number of such components, taken from the histogram's bin 255 before anything is written
+    ("raise": one extra histogram pass when full_scale is given).
+    return_report=True returns (tensor, report): gain, full_scale = 32768 / gain (the float amplitude that 0 dBFS of every
+    later record refers to), nonfinite_pairs, clipped (components that saturated) and pairs.  The report, the measurement and
+    nonfinite="raise" read counts back and synchronise; with a given full_scale and neither of the others the call only
+    enqueues on torch's current stream."""
+    import torch
+    if nonfinite not in ("zero", "raise"):
+        raise ValueError(f"nonfinite must be 'zero' or 'raise'; got {nonfinite!r}")
+    if not 0.0 <= float(clip_fraction) < 1.0:
+        raise ValueError(f"clip_fraction must be in [0, 1) (got {clip_fraction!r})")
+    if full_scale is not None:
+        fs = float(full_scale)
+        # (a NaN fails every comparison; the range's ends are float32 values, so rounding to float32 cannot leave it)
+        if not (0.0 < fs < float("inf") and _cabi.CF32_MIN_GAIN <= 32768.0 / fs <= _cabi.CF32_MAX_GAIN):
+            raise ValueError(f"full_scale must be a positive float with 32768 / full_scale in 2^-126 .. 2^125 (got {full_scale!r})")
+        gain = float(np.float32(32768.0 / fs))
+    t = _device_cf32(iq, device)
+    pairs = t.numel() // 2
+    if full_scale is None or nonfinite == "raise":
+        hist = _cf32_histogram_into(t, torch.zeros(256, dtype=torch.int64, device=t.device).view(torch.uint64)).cpu().numpy()
+        if nonfinite == "raise" and int(hist[255]):
+            from .model import NonFiniteInputError
+            raise NonFiniteInputError([], count=int(hist[255]),
+                                      message=f"{int(hist[255])} component(s) of the cf32 capture are NaN or +-Inf")
+        if full_scale is None:
+            gain = design_cf32_gain(hist, clip_fraction)
+    out = torch.empty(2 * pairs, dtype=torch.int16, device=t.device)
+    counts = torch.zeros(2, dtype=torch.int64, device=t.device) if return_report else None
+    with torch.cuda.device(t.device):
+        _cabi.check(_cabi.lib().mdc_iq_cf32_quantize(t.data_ptr() if pairs else None, pairs, gain, out.data_ptr() if pairs else None,
+                                                     counts.data_ptr() if counts is not None else None,
+                                                     torch.cuda.current_stream(t.device).cuda_stream))
+    if not return_report:
+        return out
+    c = counts.cpu().numpy()
+    return out, dict(gain=gain, full_scale=32768.0 / gain, nonfinite_pairs=int(c[0]), clipped=int(c[1]), pairs=pairs)
+
+
 # ---- I/Q balance (mdc_iq_balance_stats / mdc_iq_balance): gain / phase imbalance and DC offset -- exact integers, on the device ----
 class BalanceCoeffs(NamedTuple):
     """The six integers of mdc_iq_balance (include/mdc.h): the DC offsets in widened units and the Q14 matrix.  scale is what

@@ -47,13 +47,15 @@ _NONFINITE = {"propagate": _cabi.NONFINITE_PROPAGATE, "raise": _cabi.NONFINITE_R
 
 
 class NonFiniteInputError(ValueError):
-    """nonfinite="raise": some input frames hold a NaN or +-Inf sample.  .frames: their indices (sorted), .count: how many."""
+    """nonfinite="raise": some input frames hold a NaN or +-Inf sample.  .frames: their indices (sorted), .count: how many.
+    frontend.quantize_cf32 raises it for a float capture, before any frame exists: no indices, count (the capture's NaN or
+    +-Inf components) and message given."""
 
-    def __init__(self, frames: Sequence[int]):
+    def __init__(self, frames: Sequence[int], count: Optional[int] = None, message: Optional[str] = None):
         self.frames = [int(i) for i in frames]
-        self.count = len(self.frames)
+        self.count = len(self.frames) if count is None else int(count)
         shown = ", ".join(str(i) for i in self.frames[:8]) + (", ..." if self.count > 8 else "")
-        super().__init__(f"{self.count} input frame(s) hold a NaN or +-Inf sample: {shown}")
+        super().__init__(message if message is not None else f"{self.count} input frame(s) hold a NaN or +-Inf sample: {shown}")
 
 
 def _nonfinite_policy(nonfinite: Optional[str], tap: Optional[str] = None) -> Optional[int]:
