@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The training half of the reference's cnn.py (lines 42-153; CNN.ipynb cells 2-9) on this library, call for call:
 
-    X_train / X_test / Y_train / Y_test from the dataset dict                 cnn.py:42-82   -> formats/rml2016.py (or synthetic cells)
+    X_train / X_test / Y_train / Y_test from the dataset dict                 cnn.py:42-82   -> formats/rml2016.py, or --synth: synth_dataset
     model = Sequential([... Conv2D ... Dense ...]); model.compile(            cnn.py:104-113 -> VTCNN2.synthetic(topology) (glorot_uniform /
         loss='categorical_crossentropy', optimizer='adam')                                      he_normal / zero biases); model.compile(...)
     history = model.fit(X_train, Y_train, batch_size=1024, epochs=100,        cnn.py:135-146 -> the same call (callbacks module of this package)
@@ -16,6 +16,10 @@ signal-shaped frames of tests/signals.py with a class-dependent level: a separab
     python examples/train_like_cnn_py.py [filepath.h5] [--net deployed3|deployed10|cnnpy] [--epochs 100]
     python examples/train_like_cnn_py.py filepath.h5 --dataset RML2016.10a_dict.pkl [--mods WBFM,AM-SSB,GFSK] [--snrs 2,...,18]
            [--train-fraction 0.7] [--seed 2015]
+    python examples/train_like_cnn_py.py filepath.h5 --synth [BPSK,QPSK,QAM16] [--snrs -4,0,...] [--frames 27000]
+
+--synth takes its frames from the library's own generator instead (synth_recipe / synth_dataset: a balanced modulation x SNR
+grid of modulated, noisy frames made and normalised on the device; no argument: --mods), split by the same split_indices.
 """
 import argparse
 import os
@@ -40,6 +44,11 @@ def synthetic_cells(n=18900 + 8100, seed=2015):
     return (x * np.array([0.4, 1.0, 2.2], np.float32)[lab][:, None, None]).astype(np.float32), lab.astype(np.int64)
 
 
+def torch_index(i, device):
+    import torch
+    return torch.as_tensor(np.asarray(i), dtype=torch.int64, device=device)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("filepath", nargs="?", default="convmodrecnets_CNN2_0.5.wts.h5")      # cnn.py:133
@@ -52,9 +61,17 @@ def main(argv=None):
     ap.add_argument("--snrs", default="2,4,6,8,10,12,14,16,18")
     ap.add_argument("--train-fraction", type=float, default=0.7)
     ap.add_argument("--seed", type=int, default=2015)
+    ap.add_argument("--synth", nargs="?", const="", metavar="MODS")
+    ap.add_argument("--frames", type=int, default=18900 + 8100)      # --synth: frames in all (CNN.ipynb cell 2's selection has 27,000)
     args = ap.parse_args(argv)
 
-    if args.dataset:
+    if args.synth is not None:
+        from modulationdetectioncnn_amd import synth_dataset, synth_recipe
+        mods = (args.synth or args.mods).split(",")
+        recipe = synth_recipe(mods=mods, snrs_db=[int(s) for s in args.snrs.split(",")])
+        X, labels, _snr_db = synth_dataset(args.frames, recipe, seed=args.seed)              # device tensors; the split indexes them there
+        idx = labels.cpu().numpy().astype(np.int64)
+    elif args.dataset:
         mods = args.mods.split(",")
         ds = rml2016.RML2016.load(args.dataset)                                              # cnn.py:42-45
         X, lbl = ds.select(mods, [int(s) for s in args.snrs.split(",")])                     # cnn.py:49-59
@@ -63,7 +80,10 @@ def main(argv=None):
         X, idx = synthetic_cells(seed=args.seed)
         mods = ["WBFM", "AM-SSB", "GFSK"]
     train_idx, test_idx = rml2016.split_indices(len(X), args.train_fraction, seed=args.seed)     # cnn.py:66-72
-    X_train, X_test = X[train_idx], X[test_idx]
+    if args.synth is not None:
+        X_train, X_test = X[torch_index(train_idx, X.device)], X[torch_index(test_idx, X.device)]
+    else:
+        X_train, X_test = X[train_idx], X[test_idx]
     Y_train, Y_test = to_onehot(idx[train_idx], len(mods)), to_onehot(idx[test_idx], len(mods))  # cnn.py:74-82
     print(X_train.shape, list(X_train.shape[1:]))                                                 # cnn.py:89-90
 

@@ -69,7 +69,9 @@ extern "C" {
                                   mdc_iq_balance / mdc_iq_balance_stats / mdc_iq_balance_blocks, mdc_iq_balance_coeffs (a
                                   receiver's I/Q imbalance and DC offset, measured and corrected in exact integers);
                                   mdc_iq_cf32_histogram / mdc_iq_cf32_quantize (a complex float32 capture: the exponent
-                                  histogram of its components, and one exact rounding into an MDC_IQ_CI16 stream) */
+                                  histogram of its components, and one exact rounding into an MDC_IQ_CI16 stream);
+                                  mdc_iq_synth_plan / mdc_iq_synth_plan_bytes / mdc_iq_synth_frames, mdc_iq_synth_class (labelled
+                                  I/Q frames of a balanced modulation x SNR grid, synthesised on the device in exact integers) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -795,6 +797,84 @@ MDC_API int mdc_iq_spectrogram_components(const float* power_dev, int64_t rows, 
 MDC_API int64_t mdc_iq_channelizer_out_count(int64_t pairs_in, int channels, int ntaps, int decimate);
 MDC_API int mdc_iq_channelizer(const void* iq_dev, int format, int64_t pairs_in, int64_t first_index, int channels, int decimate,
                                const int16_t* taps_dev, int ntaps, int tap_shift, int16_t* out_dev, int64_t n_out, void* hip_stream);
+
+/* ---- frame synthesis: labelled I/Q frames of a balanced (modulation x SNR) grid, made on the device (additive in ABI 5) -------------
+ * What cnn.py reads from RML2016.10a_dict.pkl (cnn.py:42-82) -- frames of 128 (I,Q) pairs, each with a modulation and an SNR --
+ * generated instead of loaded: exact integers end to end, so the numpy restatement (tests/iq_synth_ref.py) is held bit for bit.
+ * A frame is 128 MDC_IQ_CI16 pairs.  Its content is a function of (recipe, seed, absolute frame index f) and of nothing else:
+ * not of n_frames, not of the frame's place in the call, not of the launch.  f = first_frame + i (mod 2^64) for frame i of a call.
+ *   labels     the recipe has C classes and S SNR entries: cell = f mod (C S), class = cell mod C, snr_index = cell / C.  Any C S
+ *              consecutive frames are one exactly balanced grid.  No randomness goes into labels.
+ *   generator  counter-based on fmix32 (mdc_trainer_set_dropout, below, states it).  With seed and f split into 32-bit words,
+ *                  k_seed = fmix32(fmix32(seed_lo + 0x9E3779B9) ^ seed_hi)
+ *                  key_f  = fmix32(fmix32(k_seed ^ (f_lo * 0x85EBCA6B)) ^ (f_hi * 0x85EBCA6B + 1))
+ *              (all mod 2^32), and draw j of the frame is d(j) = fmix32(key_f + j * 0xC2B2AE35).  The counters:
+ *                  j = 0              timing offset   tau   = (d * sps) >> 32                     (64-bit product; 0 <= tau < sps)
+ *                  j = 1              carrier phase   phi0  = d
+ *                  j = 2              carrier step    step  = ((d * (2 max_step + 1)) >> 32) - max_step   (then mod 2^32)
+ *                  j = 3              PHASE start     theta0 = d
+ *                  j = 16 + 4 k + e   source symbol k (e = 0 .. 3; an alphabet uses e = 0 only), k = 0 .. 143
+ *                  j = 1024 + 8 n + 4 c + e   noise of output sample n, component c (0 = I, 1 = Q), e = 0 .. 3
+ *              g(d0 .. d3) = sum over the four draws of (d & 0xFFFF) + (d >> 16), minus 262140: eight uniform 16-bit integers,
+ *              mean 0, variance 8 (2^32 - 1) / 12 exactly, |g| <= 262140.
+ *   source     per class, symbol k is a complex integer a_k: MDC_SYNTH_ALPHABET: point number (d(16 + 4k) * M) >> 32 of the class's
+ *              M points (int16 pairs; M a power of two in 1..64); MDC_SYNTH_GAUSS: a_k = (g(d(16 + 4k) .. d(16 + 4k + 3)), 0).
+ *   pulse      sps * span complex int16 Q15 taps h_0 .. (1 <= sps <= 16, 1 <= span <= 16, sps * span <= 128), given in natural order;
+ *              the plan stores them branch-major (branch b = h_b, h_{b+sps}, ...), as the resampler stores its taps.  Output sample n
+ *              of the frame sits at p = n + tau of the symbol stream: with m = p / sps and b = p mod sps,
+ *                  y_n = (sum over i in 0 .. span-1 of a_{m + span - 1 - i} * h_{b + i sps}  +  2^14 (1 + j)) >> 15
+ *              -- complex products, re and im accumulated in int64, ONE rounding shift (arithmetic, i.e. floor) per component.  The
+ *              span - 1 symbols before the frame that the pulse still reaches are drawn like the others: no ramp-up inside a frame.
+ *              Hard precondition, checked by the plan: for every branch b, B_b = amax * sum_i (|re h_{b+i sps}| + |im h_{b+i sps}|)
+ *              with amax = the largest |component| of the alphabet (262140 for MDC_SYNTH_GAUSS) satisfies
+ *              ((B_b + 2^14) >> 15) + max(|add_re|, |add_im|) <= 32767: y_n + add fits int16 (and 32-bit accumulation is exact too).
+ *   mode       MDC_SYNTH_LINEAR: z_n = y_n + add (add: the class's complex int16 constant -- AM's carrier).
+ *              MDC_SYNTH_PHASE:  inc_n = (re y_n * phase_factor) mod 2^32; theta_n = theta0 + inc_0 + ... + inc_n (mod 2^32, the sum
+ *              INCLUDES inc_n); (c, s) = the oscillator table's entry theta_n >> 20 (mdc_iq_ddc_nco_table, mdc_iq_ddc's rule);
+ *              z_n = ((c * amplitude + 2^14) >> 15, (s * amplitude + 2^14) >> 15) + add; |amplitude| + max|add| <= 32767 (checked).
+ *   channel    phi_n = phi0 + n * step (mod 2^32), (c, s) = table entry phi_n >> 20, and the mixer of mdc_iq_ddc, word for word:
+ *                  m_n = ((re z c - im z s + 32768) >> 16, (re z s + im z c + 32768) >> 16)            (z e^{j phi} / 2)
+ *              then, per component, in int64, with w = g(the component's four noise draws):
+ *                  out = clamp((m * gain_sig[class * S + snr_index] + w * gain_noise[snr_index] + 2^(q-1)) >> q, -32768, 32767)
+ *              Every component the clamp changes is counted into *saturated_dev (+=, one uint64; the caller zeroes it).
+ * Stated limit: the noise is an Irwin-Hall sum of eight uniforms, not a Gaussian: excess kurtosis -0.15, no sample beyond
+ * 262140 / sqrt(8 (2^32 - 1) / 12) = 4.9 sigma.  There is no multipath fading, no sample-rate drift and no carrier random walk.
+ *
+ * mdc_iq_synth_plan (host code, no GPU) validates a recipe and writes the plan blob (position-independent: offsets from its first
+ * byte; copy it anywhere, hand mdc_iq_synth_frames the same bytes in host and in device memory).  classes_host: C records, 1 <= C
+ * <= 64; points_host: npoints int16 PAIRS, a class's alphabet being pairs first_point .. first_point + points - 1; taps_host: ntaps
+ * int16 PAIRS (re, im), a class's pulse being pairs first_tap .. first_tap + sps * span - 1; gain_sig_host: ngain_sig int32, which
+ * must equal C * nsnrs (class-major); gain_noise_host: nsnrs int32, 1 <= nsnrs <= 64; max_step <= 2^30; 1 <= q <= 40; reserved
+ * fields 0.  plan_bytes must equal mdc_iq_synth_plan_bytes(C, nsnrs, classes_host), which depends on the records' shapes only
+ * (a negative MDC_EINVAL for shapes the plan would refuse).  Every refusal is MDC_EINVAL with an error text that names the class.
+ * mdc_iq_synth_frames: iq_out_dev takes n_frames * 128 pairs (4-byte aligned); labels_dev / snr_index_dev (n_frames int32 each) and
+ * saturated_dev (8-byte aligned) may be NULL; 0 <= n_frames <= 2^30; n_frames == 0 is MDC_OK without a launch.  plan_dev is 8-byte
+ * aligned.  The call only enqueues on hip_stream (no synchronisation, no allocation, no copy: capturable in a hipGraph) and runs
+ * on the current device.  The same arguments give the same bits on every run. */
+#define MDC_SYNTH_ALPHABET 0
+#define MDC_SYNTH_GAUSS 1
+#define MDC_SYNTH_LINEAR 0
+#define MDC_SYNTH_PHASE 1
+typedef struct mdc_iq_synth_class {
+    int32_t source;            /* MDC_SYNTH_ALPHABET / MDC_SYNTH_GAUSS */
+    int32_t points;            /* M: alphabet size (a power of two in 1..64); 0 for MDC_SYNTH_GAUSS */
+    int32_t first_point;       /* the alphabet's first pair in points_host */
+    int32_t sps, span;         /* samples per symbol, pulse length in symbols */
+    int32_t first_tap;         /* the pulse's first pair in taps_host */
+    int32_t mode;              /* MDC_SYNTH_LINEAR / MDC_SYNTH_PHASE */
+    int32_t phase_factor;      /* MDC_SYNTH_PHASE: phase increment per unit of re y */
+    int16_t amplitude;         /* MDC_SYNTH_PHASE: the carrier's amplitude */
+    int16_t add_re, add_im;    /* constant added after filtering / to the carrier */
+    int16_t reserved;          /* 0 */
+} mdc_iq_synth_class;          /* 40 bytes */
+MDC_API int64_t mdc_iq_synth_plan_bytes(int32_t nclasses, int32_t nsnrs, const mdc_iq_synth_class* classes_host);
+MDC_API int mdc_iq_synth_plan(const mdc_iq_synth_class* classes_host, int32_t nclasses, const int16_t* points_host, int64_t npoints,
+                              const int16_t* taps_host, int64_t ntaps, const int32_t* gain_sig_host, int64_t ngain_sig,
+                              const int32_t* gain_noise_host, int32_t nsnrs, uint32_t max_step, int32_t q, void* plan_host,
+                              int64_t plan_bytes);
+MDC_API int mdc_iq_synth_frames(const void* plan_host, const void* plan_dev, int64_t plan_bytes, uint64_t seed, uint64_t first_frame,
+                                int64_t n_frames, int16_t* iq_out_dev, int32_t* labels_dev, int32_t* snr_index_dev,
+                                uint64_t* saturated_dev, void* hip_stream);
 
 /* test_Y_hat = model.predict(X_test, batch_size=batch_size)  (cnn.py:198, 237) when X_test lies in HOST memory -- a
  * numpy array, or whatever buffer a cgo / JNI / N-API caller holds: the library's own driver in front of mdc_forward.

@@ -44,6 +44,7 @@ EXPORTS = [
     "mdc_iq_line_spectra", "mdc_iq_line_spectra_rows", "mdc_iq_find_lines",
     "mdc_iq_balance", "mdc_iq_balance_stats", "mdc_iq_balance_blocks",
     "mdc_iq_cf32_histogram", "mdc_iq_cf32_quantize",
+    "mdc_iq_synth_plan_bytes", "mdc_iq_synth_plan", "mdc_iq_synth_frames",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
@@ -88,6 +89,15 @@ IQ_BALANCE_COEFFS = np.dtype([("dc_i", np.int32), ("dc_q", np.int32), ("m00", np
 # (csrc/iq_cf32.hip: at most kCfGridCap work-groups, each taking CF32_GROUP_PAIRS pairs per stride step)
 CF32_MIN_GAIN, CF32_MAX_GAIN, CF32_MAX_PAIRS = 2.0 ** -126, 2.0 ** 125, 1 << 40
 CF32_GRID_CAP, CF32_GROUP_PAIRS = 1024, 1024
+# mdc_iq_synth_plan / mdc_iq_synth_frames: the class record of include/mdc.h (mdc_iq_synth_class, 40 B), its limits, and the kernel's
+# walk (csrc/iq_synth.hip: kSynGridCap work-groups of SYNTH_GROUP_FRAMES waves, one frame per wave; more frames are walked in passes)
+SYNTH_ALPHABET, SYNTH_GAUSS, SYNTH_LINEAR, SYNTH_PHASE = 0, 1, 0, 1
+IQ_SYNTH_CLASS = np.dtype([("source", np.int32), ("points", np.int32), ("first_point", np.int32), ("sps", np.int32), ("span", np.int32),
+                           ("first_tap", np.int32), ("mode", np.int32), ("phase_factor", np.int32), ("amplitude", np.int16),
+                           ("add_re", np.int16), ("add_im", np.int16), ("reserved", np.int16)])
+SYNTH_MAX_CLASSES, SYNTH_MAX_SNRS, SYNTH_MAX_POINTS, SYNTH_MAX_SPS, SYNTH_MAX_SPAN, SYNTH_MAX_TAPS = 64, 64, 64, 16, 16, 128
+SYNTH_GAUSS_MAX, SYNTH_MAX_STEP, SYNTH_MAX_Q, SYNTH_MAX_FRAMES = 262140, 1 << 30, 40, 1 << 30
+SYNTH_GRID_CAP, SYNTH_GROUP_FRAMES = 2048, 4
 # mdc_iq_resample: limits of include/mdc.h (taps and decimation as the DDC's; the sum |h| bound holds per BRANCH), and the kernel's
 # tiling (csrc/iq_resample.hip): a tile is ((RESAMPLE_TILE_PAIRS - ceil(T / L)) // D) * L outputs, RESAMPLE_GRID_CAP work-groups
 RESAMPLE_MAX_INTERPOLATE, RESAMPLE_MAX_DECIMATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BRANCH_ABS_SUM = 32, 256, 1024, 65535
@@ -226,7 +236,9 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_iq_balance_stats", [vp, i32, i64, i64, vp, i64, vp]),
                        ("mdc_iq_balance", [vp, i32, i64, vp, vp, vp]),
                        ("mdc_iq_cf32_histogram", [vp, i64, vp, vp]),
-                       ("mdc_iq_cf32_quantize", [vp, i64, C.c_float, vp, vp, vp])):
+                       ("mdc_iq_cf32_quantize", [vp, i64, C.c_float, vp, vp, vp]),
+                       ("mdc_iq_synth_plan", [vp, C.c_int32, vp, i64, vp, i64, vp, i64, vp, C.c_int32, C.c_uint32, C.c_int32, vp, i64]),
+                       ("mdc_iq_synth_frames", [vp, vp, i64, C.c_uint64, C.c_uint64, i64, vp, vp, vp, vp, vp])):
         fn = getattr(L, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, i32
@@ -238,6 +250,8 @@ def lib(variant: str = "product") -> C.CDLL:
         L.mdc_iq_resample_out_count.argtypes, L.mdc_iq_resample_out_count.restype = [i64, i32, i32, i32], i64
     if getattr(L, "mdc_iq_extract_plan_bytes", None) is not None:
         L.mdc_iq_extract_plan_bytes.argtypes, L.mdc_iq_extract_plan_bytes.restype = [i64, C.c_int32, vp, vp], i64
+    if getattr(L, "mdc_iq_synth_plan_bytes", None) is not None:
+        L.mdc_iq_synth_plan_bytes.argtypes, L.mdc_iq_synth_plan_bytes.restype = [C.c_int32, C.c_int32, vp], i64
     if getattr(L, "mdc_iq_spectrogram_rows", None) is not None:
         L.mdc_iq_spectrogram_rows.argtypes, L.mdc_iq_spectrogram_rows.restype = [i64, i32, i64, i32], i64
     if getattr(L, "mdc_iq_line_spectra_rows", None) is not None:

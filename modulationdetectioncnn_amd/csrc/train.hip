@@ -30,6 +30,7 @@
 // The batch of the reference (1,024 frames x 2,334 parameters) is launch-latency bound on this chip; that is why a step
 // is two launches and an epoch needs no host round trip but the final read of the loss.
 #include "dense_chain_common.h"      // mdc_internal.h, f32x4, row_allreduce (the 16-lane DPP butterflies of the softmax head)
+#include "mdc_fmix32.h"
 
 #include <cmath>
 #include <cstddef>
@@ -81,11 +82,7 @@ struct TrainState {
 // keep an element iff fmix32(k_frame + element * 0xC2B2AE35) >= thr, k_frame = fmix32(k_step ^ (frame * 0x85EBCA6B + site)),
 // k_step = fmix32(seed + 0x9E3779B9 * (step + 1)); step = Adam's iteration count, read from the device (a replayed hipGraph
 // draws new masks at every step), frame = the frame's index in the data set (a frame's mask does not depend on its batch).
-struct DropArgs { unsigned seed, thr; float inv; };
-__device__ __forceinline__ unsigned fmix32(unsigned h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
+struct DropArgs { unsigned seed, thr; float inv; };      // (fmix32: mdc_fmix32.h)
 __device__ __forceinline__ unsigned drop_step_key(const DropArgs& d, const TrainState* st) {
     return fmix32(d.seed + 0x9E3779B9u * (unsigned)(st->iterations + 1));
 }

@@ -1652,3 +1652,270 @@ def find_detections(spec, thresh, reach_rows: int = 2, reach_bins: int = 3, min_
     if count > int(capacity):
         raise ValueError(f"the spectrogram holds {count} components, capacity is {int(capacity)}: raise capacity or the threshold")
     return detections_from_components(spec, thresh, records, count, min_rows, min_bins, nfft_hop, avg)
+
+
+# ---- frame synthesis (mdc_iq_synth_plan / mdc_iq_synth_frames): labelled frames of a balanced (modulation x SNR) grid ----------
+RML2016_MODS = ("8PSK", "AM-DSB", "AM-SSB", "BPSK", "CPFSK", "GFSK", "PAM4", "QAM16", "QAM64", "QPSK", "WBFM")      # the dataset's order
+SYNTH_NOISE_VARIANCE = 8.0 * (2 ** 32 - 1) / 12.0      # of the sum of eight uniform 16-bit integers (include/mdc.h: exact)
+_SYNTH_Q = 20
+_SYNTH_PEAK = 16384          # the largest component of an alphabet, and the PHASE classes' amplitude
+
+
+class SynthRecipe(NamedTuple):
+    """What synth_recipe designs: the tables as mdc_iq_synth_plan takes them, the plan blob, and what the design knows.
+    power[k]: the exact expected |m|^2 (both components, after the mixer, before the gains) of class k; snr_exact_db[k, s]: the
+    SNR the integer gains give, 10 log10 of gain_sig^2 power / (gain_noise^2 2 var(w))."""
+    mods: tuple
+    snrs_db: tuple
+    classes: np.ndarray
+    points: np.ndarray
+    taps: np.ndarray
+    gain_sig: np.ndarray
+    gain_noise: np.ndarray
+    max_step: int
+    q: int
+    blob: np.ndarray
+    power: np.ndarray
+    snr_exact_db: np.ndarray
+
+
+def _rrc_pulse(sps: int, span: int, beta: float) -> np.ndarray:
+    """Root-raised-cosine pulse, sps * span taps, unit energy."""
+    n = sps * span
+    t = (np.arange(n, dtype=np.float64) - (n - 1) / 2.0) / sps
+    h = np.empty(n)
+    for i, x in enumerate(t):
+        if abs(x) < 1e-12:
+            h[i] = 1.0 - beta + 4.0 * beta / np.pi
+        elif beta > 0 and abs(abs(4.0 * beta * x) - 1.0) < 1e-9:
+            h[i] = beta / np.sqrt(2.0) * ((1 + 2 / np.pi) * np.sin(np.pi / (4 * beta)) + (1 - 2 / np.pi) * np.cos(np.pi / (4 * beta)))
+        else:
+            h[i] = (np.sin(np.pi * x * (1 - beta)) + 4 * beta * x * np.cos(np.pi * x * (1 + beta))) / (np.pi * x * (1 - (4 * beta * x) ** 2))
+    return h / np.sqrt(np.sum(h * h))
+
+
+def _lowpass_pulse(sps: int, span: int, cutoff: float, kaiser_beta: float = 6.0) -> np.ndarray:
+    """Kaiser-windowed sinc, sps * span taps, cutoff in cycles per sample."""
+    n = sps * span
+    t = np.arange(n, dtype=np.float64) - (n - 1) / 2.0
+    return 2.0 * cutoff * np.sinc(2.0 * cutoff * t) * np.kaiser(n, kaiser_beta)
+
+
+def _gaussian_frequency_pulse(sps: int, span: int, bt: float) -> np.ndarray:
+    """A rectangle of one symbol through a Gaussian filter of bandwidth-time product bt, sps * span taps, unit sum."""
+    n = sps * span
+    t = (np.arange(n, dtype=np.float64) - (n - 1) / 2.0) / sps
+    sigma = np.sqrt(np.log(2.0)) / (2.0 * np.pi * bt)
+    from math import erf
+    g = np.array([0.5 * (erf((x + 0.5) / (np.sqrt(2.0) * sigma)) - erf((x - 0.5) / (np.sqrt(2.0) * sigma))) for x in t])
+    return g / g.sum()
+
+
+def _branch_abs_sum(h: np.ndarray, sps: int) -> int:
+    a = np.abs(h[:, 0].astype(np.int64)) + np.abs(h[:, 1].astype(np.int64))
+    return int(max(a[b::sps].sum() for b in range(sps)))
+
+
+def _quantise_pulse(h, sps: int, branch_limit: float) -> np.ndarray:
+    """Complex float taps -> (n, 2) int16, scaled so that the largest branch's sum of |re| + |im| is 90 % of branch_limit."""
+    h = np.asarray(h, dtype=np.complex128)
+    a = np.abs(h.real) + np.abs(h.imag)
+    worst = max(a[b::sps].sum() for b in range(sps))
+    scaled = h * (0.9 * branch_limit / worst)
+    q = np.stack([np.rint(scaled.real), np.rint(scaled.imag)], axis=1)
+    if np.abs(q).max() > 32767:
+        q *= 32767.0 / np.abs(q).max()
+        q = np.rint(q)
+    return q.astype(np.int16)
+
+
+def _alphabet(name: str) -> np.ndarray:
+    """(M, 2) int16: the constellation at a peak component of at most _SYNTH_PEAK"""
+    P = float(_SYNTH_PEAK)
+    if name in ("BPSK", "CPFSK", "GFSK"):
+        pts = np.array([-1.0, 1.0], np.complex128) * P
+    elif name == "PAM4":
+        pts = np.array([-3.0, -1.0, 1.0, 3.0], np.complex128) * (P / 3.0)
+    elif name == "QPSK":
+        pts = P * np.exp(1j * (np.pi / 4 + np.pi / 2 * np.arange(4)))
+    elif name == "8PSK":
+        pts = P * np.exp(1j * np.pi / 4 * np.arange(8))
+    else:
+        side = {"QAM16": 4, "QAM64": 8}[name]
+        lv = (2.0 * np.arange(side) - (side - 1)) * (P / (side - 1))
+        pts = (lv[:, None] + 1j * lv[None, :]).reshape(-1)
+    return np.stack([np.rint(pts.real), np.rint(pts.imag)], axis=1).astype(np.int16)
+
+
+def synth_expected_power(cls, points, taps, table=None) -> float:
+    """The exact expected |m|^2 (I^2 + Q^2 after the mixer, before the gains) of one class record over the generator's draws:
+    independent symbols, a uniform timing offset, uniform oscillator phases; each rounding adds 1/12 per component."""
+    T = (nco_table() if table is None else np.asarray(table)).astype(np.float64)
+    T2 = float(np.mean(T[:, 0] ** 2 + T[:, 1] ** 2))
+    add = complex(int(cls["add_re"]), int(cls["add_im"]))
+    sps, span = int(cls["sps"]), int(cls["span"])
+    if int(cls["mode"]) == _cabi.SYNTH_PHASE:
+        pz = float(int(cls["amplitude"])) ** 2 * T2 / 2.0 ** 30 + 1.0 / 6.0 + abs(add) ** 2
+    else:
+        h = np.asarray(taps, np.float64).reshape(-1, 2)[int(cls["first_tap"]):int(cls["first_tap"]) + sps * span]
+        h = h[:, 0] + 1j * h[:, 1]
+        if int(cls["source"]) == _cabi.SYNTH_GAUSS:
+            mu, e2 = 0.0, SYNTH_NOISE_VARIANCE
+        else:
+            p = np.asarray(points, np.float64).reshape(-1, 2)[int(cls["first_point"]):int(cls["first_point"]) + int(cls["points"])]
+            p = p[:, 0] + 1j * p[:, 1]
+            mu, e2 = p.mean(), float(np.mean(np.abs(p) ** 2))
+        pz = 0.0
+        for b in range(sps):
+            hb = h[b::sps]
+            pz += (e2 - abs(mu) ** 2) * float(np.sum(np.abs(hb) ** 2)) / 2.0 ** 30 + abs(mu * hb.sum() / 2.0 ** 15 + add) ** 2
+        pz = pz / sps + 1.0 / 6.0
+    return pz * T2 / 2.0 ** 32 + 1.0 / 6.0
+
+
+def synth_plan(classes, points, taps, gain_sig, gain_noise, max_step: int, q: int) -> np.ndarray:
+    """mdc_iq_synth_plan (host code, no GPU): the plan blob of a recipe given as tables -- classes: _cabi.IQ_SYNTH_CLASS records;
+    points, taps: (N, 2) int16; gain_sig: (C, S) int32; gain_noise: (S) int32.  Every refusal is a _cabi.MdcError."""
+    classes = np.ascontiguousarray(classes, dtype=_cabi.IQ_SYNTH_CLASS).reshape(-1)
+    points = np.ascontiguousarray(points, dtype=np.int16).reshape(-1, 2)
+    taps = np.ascontiguousarray(taps, dtype=np.int16).reshape(-1, 2)
+    gain_sig = np.ascontiguousarray(gain_sig, dtype=np.int32)
+    gain_noise = np.ascontiguousarray(gain_noise, dtype=np.int32).reshape(-1)
+    lib = _cabi.lib()
+    nbytes = _cabi.check(lib.mdc_iq_synth_plan_bytes(classes.size, gain_noise.size, classes.ctypes.data))
+    blob = np.empty(nbytes, np.uint8)
+    _cabi.check(lib.mdc_iq_synth_plan(classes.ctypes.data, classes.size, points.ctypes.data, points.shape[0], taps.ctypes.data, taps.shape[0],
+                                      gain_sig.ctypes.data, gain_sig.size, gain_noise.ctypes.data, gain_noise.size, int(max_step), int(q),
+                                      blob.ctypes.data, nbytes))
+    return blob
+
+
+def synth_recipe(mods=RML2016_MODS, snrs_db=range(-20, 20, 2), sps: int = 8, beta: float = 0.35, span: int = 8, rms: float = 2048.0,
+                 max_cfo: float = 0.01, fsk_index: float = 0.5, gfsk_bt: float = 0.35, fm_deviation: float = 0.08,
+                 am_carrier: int = 12000) -> SynthRecipe:
+    """Design the recipe of a balanced (modulation x SNR) grid of synthesised frames (include/mdc.h, "frame synthesis"; numpy on the
+    host, no GPU).  mods: names out of RML2016_MODS, an unknown one is refused by name; snrs_db: the grid's SNR values; sps: samples
+    per symbol (for the analogue classes: per source sample); beta, span: the root-raised-cosine pulse of the linear classes (the
+    low-passes and the Gaussian frequency pulse are span symbols long too; CPFSK's rectangle is one); rms: the complex rms of
+    signal PLUS noise at every SNR, in int16 units (2048: -24 dBFS, the noise's 4.9 sigma far below the rails); max_cfo: the carrier
+    offset is drawn uniformly in +-max_cfo cycles per sample; fsk_index: modulation index of CPFSK / GFSK; gfsk_bt: GFSK's
+    bandwidth-time product; fm_deviation: WBFM's rms frequency deviation, cycles per sample; am_carrier: AM-DSB's carrier against
+    a message of 4.9 sigma <= 32767 - am_carrier.  Gains are designed from each class's exact expected power (synth_expected_power),
+    so 10 log10(P_sig / P_noise) is the nominal SNR up to the gains' rounding (SynthRecipe.snr_exact_db)."""
+    mods = tuple(mods)
+    snrs = tuple(snrs_db)
+    for m in mods:
+        if m not in RML2016_MODS:
+            raise ValueError(f"unknown modulation {m!r}: synth_recipe designs {', '.join(RML2016_MODS)}")
+    if not mods or not snrs:
+        raise ValueError("synth_recipe needs at least one modulation and one SNR")
+    sps, span = int(sps), int(span)
+    if not 0.0 <= max_cfo <= 0.25:
+        raise ValueError("max_cfo must be in 0..0.25 cycles per sample")
+    G = _cabi.SYNTH_GAUSS_MAX
+    classes = np.zeros(len(mods), _cabi.IQ_SYNTH_CLASS)
+    points, taps = [], []
+    npoints = ntaps = 0
+    for k, m in enumerate(mods):
+        c = classes[k]
+        c["sps"], c["span"], c["first_point"], c["first_tap"] = sps, span, npoints, ntaps
+        if m in ("AM-DSB", "AM-SSB", "WBFM"):
+            c["source"], c["points"] = _cabi.SYNTH_GAUSS, 0
+            add = int(am_carrier) if m == "AM-DSB" else 0
+            limit = (32767 - add) * 32768.0 / G
+            cutoff = 0.4 / sps
+            h = _lowpass_pulse(sps, span, cutoff).astype(np.complex128)
+            if m == "AM-SSB":      # the analytic low-pass: the pass band moved to 0 .. 2 cutoff (the upper sideband)
+                h = h * np.exp(2j * np.pi * cutoff * (np.arange(h.size) - (h.size - 1) / 2.0))
+            hq = _quantise_pulse(h, sps, limit)
+            if m == "WBFM":
+                c["mode"], c["amplitude"] = _cabi.SYNTH_PHASE, _SYNTH_PEAK
+                hf = hq[:, 0].astype(np.float64)
+                y_rms = np.sqrt(SYNTH_NOISE_VARIANCE * np.mean([np.sum(hf[b::sps] ** 2) for b in range(sps)])) / 32768.0
+                c["phase_factor"] = int(round(fm_deviation * 2.0 ** 32 / y_rms))
+            else:
+                c["mode"], c["add_re"] = _cabi.SYNTH_LINEAR, add
+        else:
+            a = _alphabet(m)
+            c["source"], c["points"] = _cabi.SYNTH_ALPHABET, a.shape[0]
+            points.append(a)
+            npoints += a.shape[0]
+            amax = int(np.abs(a.astype(np.int64)).max())
+            if m in ("CPFSK", "GFSK"):
+                # y = +-amax / 2 while the pulse is a rectangle: pi fsk_index per symbol is an increment of fsk_index 2^31 / sps per sample
+                c["mode"], c["amplitude"] = _cabi.SYNTH_PHASE, _SYNTH_PEAK
+                if m == "CPFSK":
+                    c["span"] = 1
+                    hq = np.stack([np.full(sps, 16384, np.int16), np.zeros(sps, np.int16)], axis=1)
+                else:
+                    g = _gaussian_frequency_pulse(sps, span, gfsk_bt) * (sps * 16384.0)
+                    hq = np.stack([np.rint(g), np.zeros(g.size)], axis=1).astype(np.int16)
+                c["phase_factor"] = int(round(fsk_index * 2.0 ** 31 / sps / (amax / 2.0)))
+            else:
+                c["mode"] = _cabi.SYNTH_LINEAR
+                hq = _quantise_pulse(_rrc_pulse(sps, span, beta), sps, 32767 * 32768.0 / amax)
+        taps.append(hq)
+        ntaps += hq.shape[0]
+    points_a = np.concatenate(points) if points else np.zeros((0, 2), np.int16)
+    taps_a = np.concatenate(taps)
+    table = nco_table()
+    power = np.array([synth_expected_power(classes[k], points_a, taps_a, table) for k in range(len(mods))])
+    q = _SYNTH_Q
+    lin = 10.0 ** (np.asarray(snrs, np.float64) / 10.0)
+    p_sig, p_noise = float(rms) ** 2 * lin / (1.0 + lin), float(rms) ** 2 / (1.0 + lin)
+    gs = np.rint(2.0 ** q * np.sqrt(p_sig[None, :] / power[:, None]))
+    gn = np.rint(2.0 ** q * np.sqrt(p_noise / (2.0 * SYNTH_NOISE_VARIANCE)))
+    if gs.max() > 2 ** 31 - 1 or gn.max() > 2 ** 31 - 1:
+        raise ValueError("rms is too large for the gains' int32")
+    gain_sig, gain_noise = gs.astype(np.int32), gn.astype(np.int32)
+    max_step = int(round(max_cfo * 2.0 ** 32))
+    blob = synth_plan(classes, points_a, taps_a, gain_sig, gain_noise, max_step, q)
+    with np.errstate(divide="ignore"):
+        exact = 10.0 * np.log10(gs ** 2 * power[:, None] / (gn[None, :] ** 2 * 2.0 * SYNTH_NOISE_VARIANCE))
+    return SynthRecipe(mods, snrs, classes, points_a, taps_a, gain_sig, gain_noise, max_step, q, blob, power, exact)
+
+
+def _synth_blob(recipe) -> np.ndarray:
+    return np.ascontiguousarray(recipe.blob if isinstance(recipe, SynthRecipe) else recipe, dtype=np.uint8)
+
+
+def synth_frames(n: int, recipe, seed: int = 2016, first_frame: int = 0, device=None, return_saturated: bool = False):
+    """n labelled frames of a recipe of synth_recipe, made on the device in one launch (mdc_iq_synth_frames): frame i is the grid's
+    frame first_frame + i -- a function of (recipe, seed, that index) alone, so calls can be split, repeated and resumed bit for
+    bit; class = index mod C, SNR entry = (index / C) mod S.  Returns (iq, labels, snr_db): the (n, 256) int16 device tensor of
+    interleaved (I, Q) samples -- reshape(-1) is an ordinary "ci16" capture --, the int32 class indices and each frame's SNR
+    value (int32 when the recipe's SNRs are whole numbers, else float32); with return_saturated also the number of components the
+    final clamp changed (one synchronising read).  Enqueues on torch's current stream."""
+    import torch
+    if not isinstance(recipe, SynthRecipe):
+        raise TypeError("recipe must be a SynthRecipe (synth_recipe)")
+    n = int(n)
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    blob = _synth_blob(recipe)
+    iq = torch.empty((n, 2 * HOP_FRAME), dtype=torch.int16, device=dev)
+    labels = torch.empty((n,), dtype=torch.int32, device=dev)
+    snr_index = torch.empty((n,), dtype=torch.int32, device=dev)
+    sat = torch.zeros((1,), dtype=torch.int64, device=dev) if return_saturated else None
+    plan_dev = torch.from_numpy(blob).to(dev)
+    with torch.cuda.device(dev):
+        _cabi.check(_cabi.lib().mdc_iq_synth_frames(blob.ctypes.data, plan_dev.data_ptr(), blob.size, int(seed) % (1 << 64), int(first_frame) % (1 << 64), n,
+                                                    iq.data_ptr() if n else None, labels.data_ptr() if n else None,
+                                                    snr_index.data_ptr() if n else None, sat.data_ptr() if sat is not None else None,
+                                                    torch.cuda.current_stream(dev).cuda_stream))
+    whole = all(float(s) == int(s) for s in recipe.snrs_db)
+    values = torch.tensor([int(s) if whole else float(s) for s in recipe.snrs_db], dtype=torch.int32 if whole else torch.float32, device=dev)
+    snr_db = values[snr_index.long()]
+    return (iq, labels, snr_db, int(sat.item())) if return_saturated else (iq, labels, snr_db)
+
+
+def synth_dataset(n: int, recipe, seed: int = 2016, level: float = DEFAULT_LEVEL, first_frame: int = 0, device=None):
+    """synth_frames through the library's normaliser (normalized_frames_from_iq at hop 128: DC removal, complex rms `level`):
+    (X float32 (n, 2, 128), labels int32, snr_db) on the device, ready for VTCNN2.fit / evaluate / confusion / accuracy_by_snr --
+    what cnn.py:42-82 selects from RML2016.10a_dict.pkl, whose vectors are energy-normalised too."""
+    iq, labels, snr_db = synth_frames(n, recipe, seed=seed, first_frame=first_frame, device=device)
+    if int(n) == 0:
+        import torch
+        return torch.empty((0, 2, HOP_FRAME), dtype=torch.float32, device=iq.device), labels, snr_db
+    return normalized_frames_from_iq(iq.reshape(-1), "ci16", level=level, hop=HOP_FRAME), labels, snr_db
