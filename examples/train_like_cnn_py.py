@@ -16,10 +16,12 @@ signal-shaped frames of tests/signals.py with a class-dependent level: a separab
     python examples/train_like_cnn_py.py [filepath.h5] [--net deployed3|deployed10|cnnpy] [--epochs 100]
     python examples/train_like_cnn_py.py filepath.h5 --dataset RML2016.10a_dict.pkl [--mods WBFM,AM-SSB,GFSK] [--snrs 2,...,18]
            [--train-fraction 0.7] [--seed 2015]
-    python examples/train_like_cnn_py.py filepath.h5 --synth [BPSK,QPSK,QAM16] [--snrs -4,0,...] [--frames 27000]
+    python examples/train_like_cnn_py.py filepath.h5 --synth [BPSK,QPSK,QAM16] [--snrs -4,0,...] [--frames 27000] [--fading [K]]
 
 --synth takes its frames from the library's own generator instead (synth_recipe / synth_dataset: a balanced modulation x SNR
 grid of modulated, noisy frames made and normalised on the device; no argument: --mods), split by the same split_indices.
+--fading sends them through synth_fading's three-path Rician channel first (K: path 0's line-of-sight over its scattered power,
+4 without an argument), so the net sees distorted constellations, as it would on RML2016.10a.
 """
 import argparse
 import os
@@ -63,12 +65,16 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=2015)
     ap.add_argument("--synth", nargs="?", const="", metavar="MODS")
     ap.add_argument("--frames", type=int, default=18900 + 8100)      # --synth: frames in all (CNN.ipynb cell 2's selection has 27,000)
+    ap.add_argument("--fading", nargs="?", type=float, const=4.0, default=None, metavar="K")      # --synth: the Rician multipath channel
     args = ap.parse_args(argv)
 
+    if args.fading is not None and args.synth is None:
+        ap.error("--fading belongs to --synth")
     if args.synth is not None:
-        from modulationdetectioncnn_amd import synth_dataset, synth_recipe
+        from modulationdetectioncnn_amd import synth_dataset, synth_fading, synth_recipe
         mods = (args.synth or args.mods).split(",")
-        recipe = synth_recipe(mods=mods, snrs_db=[int(s) for s in args.snrs.split(",")])
+        fading = synth_fading(rician_k=args.fading) if args.fading is not None else None
+        recipe = synth_recipe(mods=mods, snrs_db=[int(s) for s in args.snrs.split(",")], fading=fading)
         X, labels, _snr_db = synth_dataset(args.frames, recipe, seed=args.seed)              # device tensors; the split indexes them there
         idx = labels.cpu().numpy().astype(np.int64)
     elif args.dataset:

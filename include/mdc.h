@@ -71,7 +71,9 @@ extern "C" {
                                   mdc_iq_cf32_histogram / mdc_iq_cf32_quantize (a complex float32 capture: the exponent
                                   histogram of its components, and one exact rounding into an MDC_IQ_CI16 stream);
                                   mdc_iq_synth_plan / mdc_iq_synth_plan_bytes / mdc_iq_synth_frames, mdc_iq_synth_class (labelled
-                                  I/Q frames of a balanced modulation x SNR grid, synthesised on the device in exact integers) */
+                                  I/Q frames of a balanced modulation x SNR grid, synthesised on the device in exact integers);
+                                  mdc_iq_synth_frames_faded, mdc_iq_synth_fading, mdc_iq_synth_path (the same frames through a
+                                  frequency-selective Rician channel) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -838,7 +840,9 @@ MDC_API int mdc_iq_channelizer(const void* iq_dev, int format, int64_t pairs_in,
  *                  out = clamp((m * gain_sig[class * S + snr_index] + w * gain_noise[snr_index] + 2^(q-1)) >> q, -32768, 32767)
  *              Every component the clamp changes is counted into *saturated_dev (+=, one uint64; the caller zeroes it).
  * Stated limit: the noise is an Irwin-Hall sum of eight uniforms, not a Gaussian: excess kurtosis -0.15, no sample beyond
- * 262140 / sqrt(8 (2^32 - 1) / 12) = 4.9 sigma.  There is no multipath fading, no sample-rate drift and no carrier random walk.
+ * 262140 / sqrt(8 (2^32 - 1) / 12) = 4.9 sigma.  mdc_iq_synth_frames has no multipath fading (mdc_iq_synth_frames_faded, below, has),
+ * and neither entry has sample-rate drift or a carrier random walk: at the magnitudes the RML2016.10a generator uses, the drift moves
+ * a 128-sample frame by hundredths of a sample, and the walk stays inside the offset that max_step already draws per frame.
  *
  * mdc_iq_synth_plan (host code, no GPU) validates a recipe and writes the plan blob (position-independent: offsets from its first
  * byte; copy it anywhere, hand mdc_iq_synth_frames the same bytes in host and in device memory).  classes_host: C records, 1 <= C
@@ -875,6 +879,60 @@ MDC_API int mdc_iq_synth_plan(const mdc_iq_synth_class* classes_host, int32_t nc
 MDC_API int mdc_iq_synth_frames(const void* plan_host, const void* plan_dev, int64_t plan_bytes, uint64_t seed, uint64_t first_frame,
                                 int64_t n_frames, int16_t* iq_out_dev, int32_t* labels_dev, int32_t* snr_index_dev,
                                 uint64_t* saturated_dev, void* hip_stream);
+
+/* ---- frame synthesis through a frequency-selective Rician channel (additive in ABI 5) ------------------------------------------------
+ * mdc_iq_synth_frames_faded: the frames of mdc_iq_synth_frames, sent through P delayed paths with random complex gains before the
+ * gains and the noise.  The plan, its blob, the labels, the generator, the noise counters and the saturation count are those of
+ * mdc_iq_synth_frames, word for word; a frame stays a function of (recipe, fading record, seed, f) alone, in exact integers
+ * (the numpy restatement is tests/iq_synth_fading_ref.py).  fading_host is read and validated during the call and travels with the
+ * launch: no device copy.  With T = taps, H = T - 1:
+ *   head       the unfaded chain runs for n' = 0 .. 127 + H with its formulas unchanged and gives m_{n'}: source, pulse at p = n' + tau,
+ *              mode (PHASE's running sum runs H samples longer), mixer at phi0 + n' step.  A frame draws
+ *              (127 + H + sps - 1) / sps + span symbols, at most 159; their counters stay j = 16 + 4 k + e <= 651.
+ *   gains      per frame and path p, at the counters j = 768 + 16 p + e (free in mdc_iq_synth_frames: symbols end below 768, noise
+ *              starts at 1024): G_p = (g(d(e = 0 .. 3)), g(d(e = 4 .. 7))), the noise's own sum, and per component
+ *                  g_p = los_p + ((G_p * scatter_p + 2^17) >> 18)                      (int64 product; Q13: 8192 is a gain of one)
+ *              |G| <= 262140 < 2^18 gives |(G scatter + 2^17) >> 18| <= scatter, so with the precondition
+ *              max(|los_re|, |los_im|) + scatter <= 32767 every component of g_p fits int16.
+ *   Doppler    only if max_doppler_step > 0: psi_p = d(e = 8); nu_p = ((d(e = 9) * (2 max_doppler_step + 1)) >> 32) - max_doppler_step
+ *              (mod 2^32, as `step` is drawn); (c, s) = the oscillator table's entry (psi_p + n nu_p) >> 20 for output sample n, and
+ *                  r_p(n) = ((re g c - im g s + 2^14) >> 15, (re g s + im g c + 2^14) >> 15)
+ *              Otherwise r_p(n) = g_p and no table is read.  |re g c - im g s| <= |g| |(c, s)| <= 32767 sqrt(2) * 32768 < 2^31 (int32
+ *              is exact), and every component of r is below 46341 in absolute value (32767 sqrt(2) + 1/2 < 46341; the table's entries
+ *              have c^2 + s^2 <= 32768^2).
+ *   delay      per path T real int16 Q14 taps d_p[0 .. T-1]:  u_p(n) = (sum over k of d_p[k] * m_{n + H - k}  +  2^13) >> 14 per
+ *              component.  Precondition: sum_k |d_p[k]| <= 32767; with |m| <= 32768 per component the sum stays below 2^30 (int32 is
+ *              exact) and |u| <= 65537.  d_p[k] = 16384 at one k and 0 elsewhere is a delay of k samples, exactly.
+ *   sum        y_n = (sum over p of r_p(n) * u_p(n)  +  2^12 (1 + j)) >> 13 -- complex products, re and im accumulated in int64, ONE
+ *              rounding shift per component.  |y| <= (4 * 2 * 46341 * 65537 + 2^12) >> 13 < 2^22.
+ *   output     y_n takes m_n's place:  out = clamp((y * gain_sig + w * gain_noise + 2^(q-1)) >> q, -32768, 32767), the same noise
+ *              counters and the same count.  |y gain_sig| < 2^53 and |w gain_noise| < 2^49: the sum stays below 2^62.
+ * (The path gains are Q13 and the sum shifts by 13, where a first draft had Q14 and 14: a component of g is at most 32767 and the
+ * Irwin-Hall sum reaches 4.9 sigma, so Q14 would cap a path's scattered power at 2 (0.408)^2 = 0.33 of the whole channel's -- below
+ * the second path of the RML2016.10a profile, 0.37.  Q13 takes any path of a channel of unit power.)
+ * Stated limit: the Doppler is ONE rotating phasor per path (a frequency offset drawn per frame and path), not a sum of sinusoids
+ * with a Jakes spectrum; the scattered part of a gain is the Irwin-Hall sum above, not a Gaussian, and constant over the frame; the
+ * SNR a frame is labelled with is the AVERAGE over the fading -- a frame's own SNR varies with its gains, which is the point; no
+ * sample-rate drift and no carrier walk (see above).
+ * mdc_iq_synth_fading: 1 <= paths <= 4; 1 <= taps <= 16; max_doppler_step <= 2^30; per path p < paths the two preconditions above and
+ * scatter >= 0; delay_taps[k] = 0 for k >= taps; every field of a path p >= paths and every reserved field 0.  fading_host must not
+ * be NULL.  The record is checked first, also when n_frames == 0, so a record can be validated without a device;
+ * every refusal is MDC_EINVAL before any device call, with an error text that names the path.  All else as mdc_iq_synth_frames. */
+typedef struct mdc_iq_synth_path {
+    int16_t delay_taps[16];    /* d_p[k], real, Q14 (16384 = 1) */
+    int16_t los_re, los_im;    /* the constant (line-of-sight) part of the gain, Q13 (8192 = 1) */
+    int32_t scatter;           /* >= 0: scale of the drawn part, per component 53510 / 2^18 * scatter rms (Q13) */
+    int32_t reserved[2];       /* 0 */
+} mdc_iq_synth_path;           /* 48 bytes */
+typedef struct mdc_iq_synth_fading {
+    int32_t paths, taps;       /* P, T */
+    uint32_t max_doppler_step; /* per path, nu is drawn in -max .. max (2^32 = one cycle per sample); 0: no Doppler */
+    int32_t reserved;          /* 0 */
+    mdc_iq_synth_path path[4];
+} mdc_iq_synth_fading;         /* 208 bytes */
+MDC_API int mdc_iq_synth_frames_faded(const void* plan_host, const void* plan_dev, int64_t plan_bytes, uint64_t seed, uint64_t first_frame,
+                                      int64_t n_frames, int16_t* iq_out_dev, int32_t* labels_dev, int32_t* snr_index_dev,
+                                      uint64_t* saturated_dev, const mdc_iq_synth_fading* fading_host, void* hip_stream);
 
 /* test_Y_hat = model.predict(X_test, batch_size=batch_size)  (cnn.py:198, 237) when X_test lies in HOST memory -- a
  * numpy array, or whatever buffer a cgo / JNI / N-API caller holds: the library's own driver in front of mdc_forward.

@@ -44,7 +44,7 @@ EXPORTS = [
     "mdc_iq_line_spectra", "mdc_iq_line_spectra_rows", "mdc_iq_find_lines",
     "mdc_iq_balance", "mdc_iq_balance_stats", "mdc_iq_balance_blocks",
     "mdc_iq_cf32_histogram", "mdc_iq_cf32_quantize",
-    "mdc_iq_synth_plan_bytes", "mdc_iq_synth_plan", "mdc_iq_synth_frames",
+    "mdc_iq_synth_plan_bytes", "mdc_iq_synth_plan", "mdc_iq_synth_frames", "mdc_iq_synth_frames_faded",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
@@ -98,6 +98,14 @@ IQ_SYNTH_CLASS = np.dtype([("source", np.int32), ("points", np.int32), ("first_p
 SYNTH_MAX_CLASSES, SYNTH_MAX_SNRS, SYNTH_MAX_POINTS, SYNTH_MAX_SPS, SYNTH_MAX_SPAN, SYNTH_MAX_TAPS = 64, 64, 64, 16, 16, 128
 SYNTH_GAUSS_MAX, SYNTH_MAX_STEP, SYNTH_MAX_Q, SYNTH_MAX_FRAMES = 262140, 1 << 30, 40, 1 << 30
 SYNTH_GRID_CAP, SYNTH_GROUP_FRAMES = 2048, 4
+# mdc_iq_synth_frames_faded: the fading record of include/mdc.h (mdc_iq_synth_path, 48 B; mdc_iq_synth_fading, 208 B) and its limits;
+# delay taps are Q14 (SYNTH_FADING_TAP_ONE), path gains Q13 (SYNTH_FADING_GAIN_ONE)
+IQ_SYNTH_PATH = np.dtype([("delay_taps", np.int16, (16,)), ("los_re", np.int16), ("los_im", np.int16), ("scatter", np.int32),
+                          ("reserved", np.int32, (2,))])
+IQ_SYNTH_FADING = np.dtype([("paths", np.int32), ("taps", np.int32), ("max_doppler_step", np.uint32), ("reserved", np.int32),
+                            ("path", IQ_SYNTH_PATH, (4,))])
+SYNTH_MAX_PATHS, SYNTH_MAX_DELAY_TAPS, SYNTH_MAX_DOPPLER_STEP = 4, 16, 1 << 30
+SYNTH_FADING_TAP_ONE, SYNTH_FADING_GAIN_ONE, SYNTH_FADING_MAX_ABS_SUM = 16384, 8192, 32767
 # mdc_iq_resample: limits of include/mdc.h (taps and decimation as the DDC's; the sum |h| bound holds per BRANCH), and the kernel's
 # tiling (csrc/iq_resample.hip): a tile is ((RESAMPLE_TILE_PAIRS - ceil(T / L)) // D) * L outputs, RESAMPLE_GRID_CAP work-groups
 RESAMPLE_MAX_INTERPOLATE, RESAMPLE_MAX_DECIMATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BRANCH_ABS_SUM = 32, 256, 1024, 65535
@@ -238,7 +246,8 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_iq_cf32_histogram", [vp, i64, vp, vp]),
                        ("mdc_iq_cf32_quantize", [vp, i64, C.c_float, vp, vp, vp]),
                        ("mdc_iq_synth_plan", [vp, C.c_int32, vp, i64, vp, i64, vp, i64, vp, C.c_int32, C.c_uint32, C.c_int32, vp, i64]),
-                       ("mdc_iq_synth_frames", [vp, vp, i64, C.c_uint64, C.c_uint64, i64, vp, vp, vp, vp, vp])):
+                       ("mdc_iq_synth_frames", [vp, vp, i64, C.c_uint64, C.c_uint64, i64, vp, vp, vp, vp, vp]),
+                       ("mdc_iq_synth_frames_faded", [vp, vp, i64, C.c_uint64, C.c_uint64, i64, vp, vp, vp, vp, vp, vp])):
         fn = getattr(L, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, i32

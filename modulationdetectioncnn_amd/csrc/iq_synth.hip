@@ -18,6 +18,16 @@
 //   channel   iq_mix.h's mixer arithmetic; the gains and the rounding shift in int64 (v_mad_i64_i32).
 //   count     clamped components per lane in a register over all of the lane's frames, then shuffles, LDS, and ONE 64-bit
 //             global atomic per work-group that has something to add.
+// mdc_iq_synth_frames_faded is the kernel's second instantiation (include/mdc.h, "frame synthesis through a frequency-selective
+// Rician channel"; tests/iq_synth_fading_ref.py), the same shape and walk:
+//   head      the chain above runs for 128 + H samples, H = taps - 1 <= 15: the lanes below H take a third sample, n' = 128 + lane
+//             (up to 160 symbols per plane; PHASE: a second four-step scan over those lanes on top of the first scan's total).
+//   LDS       the mixed samples go through the wave's slice (2 x 144 int32), so a lane reads the T it needs: 27.5 KiB, five
+//             work-groups per CU.  A third work-group barrier stands between writing and reading them; waves without a frame
+//             meet it where they leave the iteration.
+//   paths     delay lines in int32 (the record's bound), taps and path count wave-uniform from the kernel arguments; lane l draws
+//             gain component l & 1 of path (l >> 1) & 3 and the wave reads the eight back; the sum over paths in int64.
+//             79 VGPRs, no scratch; the first instantiation is unchanged (59 VGPRs, 22.5 KiB).
 // The call only enqueues; vector memory for every store and atomic; no work-group waits on another.
 #include "iq_mix.h"
 #include "mdc_fmix32.h"
@@ -42,6 +52,12 @@ constexpr int kSynMaxQ = 40;
 constexpr int64_t kSynMaxFrames = (int64_t)1 << 30;
 constexpr unsigned kSynDrawStride = 0xC2B2AE35u;
 constexpr unsigned kSynDrawSymbols = 16, kSynDrawNoise = 1024;
+// mdc_iq_synth_frames_faded
+constexpr int kSynMaxPaths = 4, kSynMaxDelayTaps = 16;
+constexpr int kSynMaxSymbolsFaded = 160;         // (127 + 15 + sps - 1) / sps + span <= 142 + 16 at sps = 1
+constexpr int kSynMaxHead = 144;                 // 128 + (16 - 1) mixed samples
+constexpr unsigned kSynDrawPaths = 768;          // above the last symbol's counter (16 + 4 * 158 + 3), below the noise's
+constexpr uint32_t kSynMaxDopplerStep = 1u << 30;
 
 typedef unsigned long long u64;
 
@@ -91,10 +107,28 @@ struct SynArgs {
     int C, S, q;
 };
 
-__global__ __launch_bounds__(kSynThreads) void iq_synth_kernel(const SynArgs a, unsigned* __restrict__ out, int* __restrict__ labels,
+// the fading record as the kernel reads it (uniform loads from the arguments): taps widened, fields side by side
+struct SynFade {
+    int d[kSynMaxPaths][kSynMaxDelayTaps];
+    int los_re[kSynMaxPaths], los_im[kSynMaxPaths], scatter[kSynMaxPaths];
+    int P, T;
+    unsigned max_dop;
+};
+static_assert(sizeof(mdc_iq_synth_path) == 48 && sizeof(mdc_iq_synth_fading) == 208, "the fading record");
+template <bool FADED> struct SynKernelArgs : SynArgs {};
+template <> struct SynKernelArgs<true> : SynArgs { SynFade fd; };
+
+// FADED: mdc_iq_synth_frames_faded -- the same chain over 128 + H samples (lanes below H take a third, n' = 128 + lane), the mixed
+// samples through the wave's LDS slice, then the paths.  Everything the channel adds sits under `if constexpr (FADED)`: the other
+// instantiation is mdc_iq_synth_frames' kernel as it was.
+template <bool FADED>
+__global__ __launch_bounds__(kSynThreads) void iq_synth_kernel(const SynKernelArgs<FADED> a, unsigned* __restrict__ out, int* __restrict__ labels,
                                                                int* __restrict__ snr_index, u64* __restrict__ saturated) {
+    constexpr int kSymbols = FADED ? kSynMaxSymbolsFaded : kSynMaxSymbols;
+    constexpr int E = FADED ? 3 : 2;      // samples of the unfaded chain per lane
     __shared__ unsigned nco[kNcoEntries];
-    __shared__ int sym_re[kSynWaves][kSynMaxSymbols], sym_im[kSynWaves][kSynMaxSymbols];
+    __shared__ int sym_re[kSynWaves][kSymbols], sym_im[kSynWaves][kSymbols];
+    __shared__ int mix_re[kSynWaves][FADED ? kSynMaxHead : 1], mix_im[kSynWaves][FADED ? kSynMaxHead : 1];      // (FADED only)
     __shared__ unsigned tl[kSynWaves][kSynMaxTaps];
     __shared__ unsigned part[kSynWaves];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -106,6 +140,8 @@ __global__ __launch_bounds__(kSynThreads) void iq_synth_kernel(const SynArgs a, 
     const unsigned CS = (unsigned)(a.C * a.S);
     const long groups = (a.n + kSynWaves - 1) / kSynWaves;
     unsigned nsat = 0;
+    int H = 0;      // head samples: taps - 1
+    if constexpr (FADED) H = a.fd.T - 1;
 
     for (long g = blockIdx.x; g < groups; g += gridDim.x) {
         const long i = g * kSynWaves + wave;      // < 2^30
@@ -120,7 +156,9 @@ __global__ __launch_bounds__(kSynThreads) void iq_synth_kernel(const SynArgs a, 
             si = (int)(cell / (unsigned)a.C);
             key = syn_frame_key(a.kseed, a.first_frame + (u64)i);
             rec = a.classes[cls];
-            const int nsym = min(rec.nsym, kSynMaxSymbols), ntaps = min(rec.sps * rec.span, kSynMaxTaps);
+            int nsym = min(rec.nsym, kSynMaxSymbols);
+            if constexpr (FADED) nsym = min((kSamples - 1 + H + rec.sps - 1) / rec.sps + rec.span, kSymbols);
+            const int ntaps = min(rec.sps * rec.span, kSynMaxTaps);
             for (int k = lane; k < nsym; k += 64) {
                 const unsigned j = kSynDrawSymbols + 4u * (unsigned)k;
                 int re, im = 0;
@@ -138,15 +176,22 @@ __global__ __launch_bounds__(kSynThreads) void iq_synth_kernel(const SynArgs a, 
             for (int t = lane; t < ntaps; t += 64) tw[t] = a.taps[rec.tap0 + t];
         }
         __syncthreads();
-        if (!active) continue;      // (the barriers are above: every wave has passed both)
+        if (!active) {      // (the barriers are above: every wave has passed both)
+            if constexpr (FADED) __syncthreads();      // ... and the third, between the mixed samples and the paths, is met here
+            continue;
+        }
 
         const unsigned tau = (unsigned)(((u64)syn_draw(key, 0) * (unsigned)rec.sps) >> 32);
         const unsigned phi0 = syn_draw(key, 1);
         const unsigned step = (unsigned)(((u64)syn_draw(key, 2) * (2ull * a.max_step + 1ull)) >> 32) - a.max_step;
-        int yr[2], yi[2];
+        int yr[E], yi[E];
 #pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const unsigned p = 2u * (unsigned)lane + (unsigned)e + tau;
+        for (int e = 0; e < E; ++e) {
+            if (e == 2 && lane >= H) {      // (FADED only) no third sample: nothing is read, the increment below is 0
+                yr[e] = yi[e] = 0;
+                continue;
+            }
+            const unsigned p = (e < 2 ? 2u * (unsigned)lane + (unsigned)e : (unsigned)kSamples + (unsigned)lane) + tau;
             const unsigned m = p / (unsigned)rec.sps, b = p - m * (unsigned)rec.sps;
             const unsigned* tp = tw + b * (unsigned)rec.span;
             const int sb = (int)m + rec.span - 1;
@@ -161,7 +206,7 @@ __global__ __launch_bounds__(kSynThreads) void iq_synth_kernel(const SynArgs a, 
             yr[e] = (ar + 16384) >> 15;
             yi[e] = (ai + 16384) >> 15;
         }
-        int zr[2], zi[2];
+        int zr[E], zi[E];
         if (rec.mode == MDC_SYNTH_PHASE) {      // uniform over the wave
             const unsigned inc0 = (unsigned)yr[0] * (unsigned)rec.factor, inc1 = (unsigned)yr[1] * (unsigned)rec.factor;
             const unsigned own = inc0 + inc1;
@@ -172,9 +217,19 @@ __global__ __launch_bounds__(kSynThreads) void iq_synth_kernel(const SynArgs a, 
                 if (lane >= d) x += t;
             }
             unsigned theta = syn_draw(key, 3) + (x - own);
+            unsigned theta2 = 0;
+            if constexpr (FADED) {      // the H increments behind the 128: a second scan over the lanes below 16, on top of the first's total
+                unsigned x2 = (unsigned)yr[2] * (unsigned)rec.factor;
 #pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                theta += e == 0 ? inc0 : inc1;
+                for (int d = 1; d < kSynMaxDelayTaps; d <<= 1) {
+                    const unsigned t = __shfl_up(x2, d, 64);
+                    if (lane >= d) x2 += t;
+                }
+                theta2 = syn_draw(key, 3) + __shfl(x, 63, 64) + x2;
+            }
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                theta = e == 2 ? theta2 : theta + (e == 0 ? inc0 : inc1);
                 const unsigned cs = nco[theta >> 20];
                 const int c = (int)(short)(cs & 0xFFFFu), s = (int)(short)(cs >> 16);
                 zr[e] = ((c * rec.amp + 16384) >> 15) + rec.add_re;
@@ -182,21 +237,98 @@ __global__ __launch_bounds__(kSynThreads) void iq_synth_kernel(const SynArgs a, 
             }
         } else {
 #pragma unroll
-            for (int e = 0; e < 2; ++e) {
+            for (int e = 0; e < E; ++e) {
                 zr[e] = yr[e] + rec.add_re;
                 zi[e] = yi[e] + rec.add_im;
             }
         }
         const long gs = a.gsig[cls * a.S + si], gn = a.gnoise[si];
         const long half = 1l << (a.q - 1);
+        int fr[2] = {0, 0}, fi[2] = {0, 0};      // (FADED only) y, which takes m's place below
+        if constexpr (FADED) {
+            int* mre = mix_re[wave];
+            int* mim = mix_im[wave];
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const unsigned n = e < 2 ? 2u * (unsigned)lane + (unsigned)e : (unsigned)kSamples + (unsigned)lane;
+                const unsigned cs = nco[(phi0 + n * step) >> 20];
+                const int c = (int)(short)(cs & 0xFFFFu), s = (int)(short)(cs >> 16);
+                if (e < 2 || lane < H) {
+                    mre[n] = (zr[e] * c - zi[e] * s + 32768) >> 16;
+                    mim[n] = (zr[e] * s + zi[e] * c + 32768) >> 16;
+                }
+            }
+            __syncthreads();      // the wave's 128 + H mixed samples are in its slice (waves without a frame meet this barrier above)
+            const int P = a.fd.P, T = a.fd.T;
+            // delay lines: int32 is exact (sum |d| <= 32767, |m| <= 32768); taps and path count are uniform, the taps come from the arguments
+            int ar[kSynMaxPaths][2] = {}, ai[kSynMaxPaths][2] = {};
+            for (int k = 0; k < T; ++k) {
+                const int at = 2 * lane + H - k;
+                const int x0r = mre[at], x0i = mim[at], x1r = mre[at + 1], x1i = mim[at + 1];
+#pragma unroll
+                for (int p = 0; p < kSynMaxPaths; ++p)
+                    if (p < P) {
+                        const int d = a.fd.d[p][k];
+                        ar[p][0] += d * x0r;
+                        ai[p][0] += d * x0i;
+                        ar[p][1] += d * x1r;
+                        ai[p][1] += d * x1i;
+                    }
+            }
+            // path gains: lane l draws component l & 1 of path (l >> 1) & 3 (four draws each, not thirty-two per lane), read back below
+            const int pl = (lane >> 1) & 3, cl = lane & 1;
+            int los = 0, sc = 0;
+#pragma unroll
+            for (int p = 0; p < kSynMaxPaths; ++p)
+                if (pl == p) {
+                    los = cl ? a.fd.los_im[p] : a.fd.los_re[p];
+                    sc = a.fd.scatter[p];
+                }
+            const unsigned jp = kSynDrawPaths + 16u * (unsigned)pl;
+            const int gv = los + (int)(((long)syn_gauss(key, jp + 4u * (unsigned)cl) * sc + (1l << 17)) >> 18);
+            const int dv = (int)syn_draw(key, jp + 8u + (unsigned)cl);      // psi (component 0's lane), nu's draw (component 1's)
+            const unsigned max_dop = a.fd.max_dop;
+            long sr[2] = {0, 0}, si[2] = {0, 0};
+#pragma unroll
+            for (int p = 0; p < kSynMaxPaths; ++p)
+                if (p < P) {
+                    const int gr = __shfl(gv, 2 * p, 64), gi = __shfl(gv, 2 * p + 1, 64);
+                    const unsigned psi = (unsigned)__shfl(dv, 2 * p, 64);
+                    const unsigned nu = (unsigned)(((u64)(unsigned)__shfl(dv, 2 * p + 1, 64) * (2ull * max_dop + 1ull)) >> 32) - max_dop;
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        int rr = gr, ri = gi;
+                        if (max_dop != 0) {      // uniform over the grid
+                            const unsigned cs = nco[(psi + (2u * (unsigned)lane + (unsigned)e) * nu) >> 20];
+                            const int c = (int)(short)(cs & 0xFFFFu), s = (int)(short)(cs >> 16);
+                            rr = (gr * c - gi * s + 16384) >> 15;
+                            ri = (gr * s + gi * c + 16384) >> 15;
+                        }
+                        const int ur = (ar[p][e] + 8192) >> 14, ui = (ai[p][e] + 8192) >> 14;
+                        sr[e] += (long)rr * ur - (long)ri * ui;
+                        si[e] += (long)rr * ui + (long)ri * ur;
+                    }
+                }
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                fr[e] = (int)((sr[e] + 4096) >> 13);
+                fi[e] = (int)((si[e] + 4096) >> 13);
+            }
+        }
         unsigned o[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             const unsigned n = 2u * (unsigned)lane + (unsigned)e;
-            const unsigned cs = nco[(phi0 + n * step) >> 20];
-            const int c = (int)(short)(cs & 0xFFFFu), s = (int)(short)(cs >> 16);
-            const int mr = (zr[e] * c - zi[e] * s + 32768) >> 16;
-            const int mi = (zr[e] * s + zi[e] * c + 32768) >> 16;
+            int mr, mi;
+            if constexpr (FADED) {
+                mr = fr[e];
+                mi = fi[e];
+            } else {
+                const unsigned cs = nco[(phi0 + n * step) >> 20];
+                const int c = (int)(short)(cs & 0xFFFFu), s = (int)(short)(cs >> 16);
+                mr = (zr[e] * c - zi[e] * s + 32768) >> 16;
+                mi = (zr[e] * s + zi[e] * c + 32768) >> 16;
+            }
             const int wr = syn_gauss(key, kSynDrawNoise + 8u * n), wi = syn_gauss(key, kSynDrawNoise + 8u * n + 4u);
             const long vr = ((long)mr * gs + (long)wr * gn + half) >> a.q, vi = ((long)mi * gs + (long)wi * gn + half) >> a.q;
             const long cr = vr < -32768 ? -32768 : vr > 32767 ? 32767 : vr, ci = vi < -32768 ? -32768 : vi > 32767 ? 32767 : vi;
@@ -378,9 +510,60 @@ int mdc_iq_synth_plan(const mdc_iq_synth_class* classes_host, int32_t nclasses, 
     });
 }
 
-int mdc_iq_synth_frames(const void* plan_host, const void* plan_dev, int64_t plan_bytes, uint64_t seed, uint64_t first_frame, int64_t n_frames,
-                        int16_t* iq_out_dev, int32_t* labels_dev, int32_t* snr_index_dev, uint64_t* saturated_dev, void* hip_stream) {
-    static const char who[] = "mdc_iq_synth_frames";
+// the fading record's preconditions (include/mdc.h); on success the record as the kernel reads it
+static int synth_fading_check(const char* who, const mdc_iq_synth_fading* f, SynFade& fd) {
+    if (!f) { set_error("%s: null fading record", who); return MDC_EINVAL; }
+    if (f->paths < 1 || f->paths > kSynMaxPaths) { set_error("%s: fading: paths must be in 1..%d (got %d)", who, kSynMaxPaths, f->paths); return MDC_EINVAL; }
+    if (f->taps < 1 || f->taps > kSynMaxDelayTaps) { set_error("%s: fading: taps must be in 1..%d (got %d)", who, kSynMaxDelayTaps, f->taps); return MDC_EINVAL; }
+    if (f->max_doppler_step > kSynMaxDopplerStep) {
+        set_error("%s: fading: max_doppler_step must be at most 2^30 (got %u)", who, f->max_doppler_step);
+        return MDC_EINVAL;
+    }
+    if (f->reserved != 0) { set_error("%s: fading: reserved must be 0 (got %d)", who, f->reserved); return MDC_EINVAL; }
+    fd = SynFade{};
+    fd.P = f->paths;
+    fd.T = f->taps;
+    fd.max_dop = f->max_doppler_step;
+    for (int p = 0; p < kSynMaxPaths; ++p) {
+        const mdc_iq_synth_path& q = f->path[p];
+        if (q.reserved[0] != 0 || q.reserved[1] != 0) { set_error("%s: fading: path %d: reserved must be 0", who, p); return MDC_EINVAL; }
+        int64_t sum = 0;
+        for (int k = 0; k < kSynMaxDelayTaps; ++k) {
+            if (k >= f->taps && q.delay_taps[k] != 0) {
+                set_error("%s: fading: path %d: delay_taps[%d] must be 0 with %d taps (got %d)", who, p, k, f->taps, (int)q.delay_taps[k]);
+                return MDC_EINVAL;
+            }
+            sum += iabs(q.delay_taps[k]);
+            fd.d[p][k] = q.delay_taps[k];
+        }
+        if (p >= f->paths) {
+            if (sum != 0 || q.los_re != 0 || q.los_im != 0 || q.scatter != 0) {
+                set_error("%s: fading: path %d: every field of a path beyond the %d in use must be 0", who, p, f->paths);
+                return MDC_EINVAL;
+            }
+            continue;
+        }
+        if (sum > 32767) {
+            set_error("%s: fading: path %d: the delay taps sum to %lld in absolute value: more than 32767", who, p, (long long)sum);
+            return MDC_EINVAL;
+        }
+        if (q.scatter < 0) { set_error("%s: fading: path %d: scatter must be >= 0 (got %d)", who, p, q.scatter); return MDC_EINVAL; }
+        const int64_t los = std::max(iabs(q.los_re), iabs(q.los_im));
+        if (los + (int64_t)q.scatter > 32767) {
+            set_error("%s: fading: path %d: max(|los_re|, |los_im|) + scatter must be at most 32767 (got %lld + %d)", who, p, (long long)los, q.scatter);
+            return MDC_EINVAL;
+        }
+        fd.los_re[p] = q.los_re;
+        fd.los_im[p] = q.los_im;
+        fd.scatter[p] = q.scatter;
+    }
+    return MDC_OK;
+}
+
+// both entries: `fading` is null for mdc_iq_synth_frames
+static int synth_frames(const char* who, const void* plan_host, const void* plan_dev, int64_t plan_bytes, uint64_t seed, uint64_t first_frame,
+                        int64_t n_frames, int16_t* iq_out_dev, int32_t* labels_dev, int32_t* snr_index_dev, uint64_t* saturated_dev,
+                        const SynFade* fading, void* hip_stream) {
     if (!plan_host) { set_error("%s: null plan", who); return MDC_EINVAL; }
     if (plan_bytes < (int64_t)sizeof(SynHeader)) { set_error("%s: plan_bytes is %lld, smaller than a plan's header", who, (long long)plan_bytes); return MDC_EINVAL; }
     SynHeader h;
@@ -433,9 +616,37 @@ int mdc_iq_synth_frames(const void* plan_host, const void* plan_dev, int64_t pla
         a.S = h.S;
         a.q = h.q;
         const long groups = ((long)n_frames + kSynWaves - 1) / kSynWaves;
-        hipLaunchKernelGGL(iq_synth_kernel, dim3((unsigned)(groups < kSynGridCap ? groups : kSynGridCap)), dim3(kSynThreads), 0, s, a,
-                           reinterpret_cast<unsigned*>(iq_out_dev), labels_dev, snr_index_dev, reinterpret_cast<u64*>(saturated_dev));
+        const dim3 grid((unsigned)(groups < kSynGridCap ? groups : kSynGridCap));
+        unsigned* out = reinterpret_cast<unsigned*>(iq_out_dev);
+        u64* sat = reinterpret_cast<u64*>(saturated_dev);
+        if (fading) {
+            SynKernelArgs<true> af{};
+            static_cast<SynArgs&>(af) = a;
+            af.fd = *fading;
+            hipLaunchKernelGGL(iq_synth_kernel<true>, grid, dim3(kSynThreads), 0, s, af, out, labels_dev, snr_index_dev, sat);
+        } else {
+            SynKernelArgs<false> au{};
+            static_cast<SynArgs&>(au) = a;
+            hipLaunchKernelGGL(iq_synth_kernel<false>, grid, dim3(kSynThreads), 0, s, au, out, labels_dev, snr_index_dev, sat);
+        }
         MDC_HIP(hipGetLastError());
         return MDC_OK;
     });
+}
+
+int mdc_iq_synth_frames(const void* plan_host, const void* plan_dev, int64_t plan_bytes, uint64_t seed, uint64_t first_frame, int64_t n_frames,
+                        int16_t* iq_out_dev, int32_t* labels_dev, int32_t* snr_index_dev, uint64_t* saturated_dev, void* hip_stream) {
+    return synth_frames("mdc_iq_synth_frames", plan_host, plan_dev, plan_bytes, seed, first_frame, n_frames, iq_out_dev, labels_dev, snr_index_dev,
+                        saturated_dev, nullptr, hip_stream);
+}
+
+int mdc_iq_synth_frames_faded(const void* plan_host, const void* plan_dev, int64_t plan_bytes, uint64_t seed, uint64_t first_frame, int64_t n_frames,
+                              int16_t* iq_out_dev, int32_t* labels_dev, int32_t* snr_index_dev, uint64_t* saturated_dev,
+                              const mdc_iq_synth_fading* fading_host, void* hip_stream) {
+    static const char who[] = "mdc_iq_synth_frames_faded";
+    SynFade fd;
+    const int rc = synth_fading_check(who, fading_host, fd);
+    if (rc != MDC_OK) return rc;
+    return synth_frames(who, plan_host, plan_dev, plan_bytes, seed, first_frame, n_frames, iq_out_dev, labels_dev, snr_index_dev, saturated_dev, &fd,
+                        hip_stream);
 }

@@ -7,7 +7,7 @@ An RTL-SDR delivers unsigned 8-bit interleaved (I, Q) samples; a frame of the cl
 from __future__ import annotations
 
 import ctypes as C
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -1677,6 +1677,23 @@ class SynthRecipe(NamedTuple):
     blob: np.ndarray
     power: np.ndarray
     snr_exact_db: np.ndarray
+    fading: Optional["SynthFading"] = None      # synth_fading's design: frames go through mdc_iq_synth_frames_faded
+
+
+class SynthFading(NamedTuple):
+    """What synth_fading designs: `record`, one _cabi.IQ_SYNTH_FADING as mdc_iq_synth_frames_faded takes it, and what the design
+    knows.  path_power[p]: the exact E|g_p|^2 of path p's gain in the integer definition, in units of one (8192^2); power_sum:
+    their sum, the channel's mean power gain for a signal inside `band`; delay_deviation[p]: the worst | |D_p(f)|^2 - 1 | of path
+    p's quantised delay filter over |f| <= band cycles per sample."""
+    record: np.ndarray
+    delays: tuple
+    mags: tuple
+    rician_k: float
+    max_doppler: float
+    band: float
+    path_power: tuple
+    power_sum: float
+    delay_deviation: tuple
 
 
 def _rrc_pulse(sps: int, span: int, beta: float) -> np.ndarray:
@@ -1790,9 +1807,96 @@ def synth_plan(classes, points, taps, gain_sig, gain_noise, max_step: int, q: in
     return blob
 
 
+_irwin_hall = None
+
+
+def _irwin_hall_pmf() -> np.ndarray:
+    """P(G = v - 262140), v = 0 .. 524280: the sum of eight uniform integers on 0 .. 65535, by seven sliding-window sums."""
+    global _irwin_hall
+    if _irwin_hall is None:
+        p = np.full(65536, 1.0 / 65536.0)
+        for _ in range(7):
+            c = np.concatenate([[0.0], np.cumsum(np.concatenate([p, np.zeros(65535)]))])
+            p = (c[1:] - np.concatenate([np.zeros(65536), c[1:-65536]])) / 65536.0
+        _irwin_hall = p
+    return _irwin_hall
+
+
+def synth_scatter_moments(scatter: int):
+    """(E X, E X^2) of one drawn gain component X = (G scatter + 2^17) >> 18 of mdc_iq_synth_frames_faded, G the sum of eight
+    uniform 16-bit integers minus 262140: summed over G's whole distribution, so the rounding shift is in it."""
+    pmf = _irwin_hall_pmf()
+    x = ((np.arange(pmf.size, dtype=np.int64) - _cabi.SYNTH_GAUSS_MAX) * int(scatter) + (1 << 17)) >> 18
+    return float(pmf @ x), float(pmf @ (x * x).astype(np.float64))
+
+
+def synth_path_power(los_re: int, los_im: int, scatter: int) -> float:
+    """The exact E|g|^2 of a path's gain g = los + X (two independent components), in integer units (8192^2 is a power of one)."""
+    m1, m2 = synth_scatter_moments(scatter)
+    return float(los_re) ** 2 + float(los_im) ** 2 + 2.0 * m1 * (float(los_re) + float(los_im)) + 2.0 * m2
+
+
+def synth_fading(delays=(0.0, 0.9, 1.7), mags=(1.0, 0.8, 0.3), rician_k: float = 4.0, ntaps: int = 8, max_doppler: float = 0.0,
+                 band: float = 0.25, kaiser_beta: float = 4.0) -> SynthFading:
+    """Design a frequency-selective Rician channel for mdc_iq_synth_frames_faded (include/mdc.h; numpy on the host, no GPU).
+    delays: each path's delay in samples (fractions allowed, 0 <= delay <= (ntaps - 1) / 2), 1..4 paths; mags: the paths' relative
+    amplitudes; rician_k: path 0's line-of-sight power over its scattered power (the other paths are all scattered: Rayleigh);
+    ntaps: taps of every path's delay filter, 1..16 -- a Kaiser-windowed sinc centred at delay + (ntaps - 1) / 2, unit gain at
+    DC, in Q14; max_doppler: every path's frequency offset is drawn per frame, uniformly in +-max_doppler cycles per sample (at
+    most 0.25; 0: gains constant over a frame, no oscillator read).  The defaults are the delay profile of the RML2016.10a
+    generator's channel.  The path powers are mags^2 scaled to sum to one; what the integers then give is reported (path_power,
+    power_sum), as is each delay filter's worst deviation from unit power gain over |f| <= band (delay_deviation).  Bad
+    arguments are refused by name (ValueError)."""
+    delays, mags = tuple(float(d) for d in delays), tuple(float(m) for m in mags)
+    P, T = len(delays), int(ntaps)
+    if not 1 <= P <= _cabi.SYNTH_MAX_PATHS:
+        raise ValueError(f"delays: synth_fading takes 1..{_cabi.SYNTH_MAX_PATHS} paths (got {P})")
+    if len(mags) != P:
+        raise ValueError(f"mags: {len(mags)} magnitudes for {P} delays")
+    if not 1 <= T <= _cabi.SYNTH_MAX_DELAY_TAPS:
+        raise ValueError(f"ntaps must be in 1..{_cabi.SYNTH_MAX_DELAY_TAPS} (got {ntaps})")
+    for d in delays:
+        if not 0.0 <= d <= (T - 1) / 2.0:
+            raise ValueError(f"delays: {d} is outside 0..{(T - 1) / 2.0}, what {T} taps can centre")
+    for m in mags:
+        if not (np.isfinite(m) and m > 0.0):
+            raise ValueError(f"mags: every magnitude must be positive and finite (got {m})")
+    if not (np.isfinite(rician_k) and rician_k >= 0.0):
+        raise ValueError(f"rician_k must be >= 0 and finite (got {rician_k})")
+    if not 0.0 <= max_doppler <= 0.25:
+        raise ValueError(f"max_doppler must be in 0..0.25 cycles per sample (got {max_doppler})")
+    if not 0.0 < band <= 0.5:
+        raise ValueError(f"band must be in (0, 0.5] cycles per sample (got {band})")
+    rec = np.zeros(1, _cabi.IQ_SYNTH_FADING)
+    rec["paths"], rec["taps"], rec["max_doppler_step"] = P, T, int(round(max_doppler * 2.0 ** 32))
+    share = np.asarray(mags) ** 2 / np.sum(np.asarray(mags) ** 2)
+    one, sigma_g = float(_cabi.SYNTH_FADING_GAIN_ONE), np.sqrt(SYNTH_NOISE_VARIANCE)
+    f = np.linspace(-band, band, 257)
+    k = np.arange(T, dtype=np.float64)
+    powers, deviations = [], []
+    for p in range(P):
+        path = rec["path"][0][p]
+        h = np.sinc(k - (T - 1) / 2.0 - delays[p]) * np.kaiser(T, kaiser_beta) if T > 1 else np.ones(1)
+        d = np.rint(h / h.sum() * _cabi.SYNTH_FADING_TAP_ONE).astype(np.int64)
+        if np.abs(d).sum() > _cabi.SYNTH_FADING_MAX_ABS_SUM:
+            raise ValueError(f"delays: path {p}'s delay filter sums to {int(np.abs(d).sum())} in absolute value, more than "
+                             f"{_cabi.SYNTH_FADING_MAX_ABS_SUM}: use fewer taps or a larger kaiser_beta")
+        path["delay_taps"][:T] = d
+        gain = np.abs(np.exp(-2j * np.pi * f[:, None] * k[None, :]) @ (d / float(_cabi.SYNTH_FADING_TAP_ONE))) ** 2
+        deviations.append(float(np.abs(gain - 1.0).max()))
+        los_power = share[p] * rician_k / (rician_k + 1.0) if p == 0 else 0.0
+        los = int(round(one * np.sqrt(los_power)))
+        scatter = int(round(one * np.sqrt((share[p] - los_power) / 2.0) * 2.0 ** 18 / sigma_g))
+        if los + scatter > 32767:
+            raise ValueError(f"mags: path {p}'s gain needs |los| + scatter = {los} + {scatter}, more than 32767")
+        path["los_re"], path["scatter"] = los, scatter
+        powers.append(synth_path_power(los, 0, scatter) / one ** 2)
+    return SynthFading(rec, delays, mags, float(rician_k), float(max_doppler), float(band), tuple(powers), float(sum(powers)), tuple(deviations))
+
+
 def synth_recipe(mods=RML2016_MODS, snrs_db=range(-20, 20, 2), sps: int = 8, beta: float = 0.35, span: int = 8, rms: float = 2048.0,
                  max_cfo: float = 0.01, fsk_index: float = 0.5, gfsk_bt: float = 0.35, fm_deviation: float = 0.08,
-                 am_carrier: int = 12000) -> SynthRecipe:
+                 am_carrier: int = 12000, fading: Optional[SynthFading] = None) -> SynthRecipe:
     """Design the recipe of a balanced (modulation x SNR) grid of synthesised frames (include/mdc.h, "frame synthesis"; numpy on the
     host, no GPU).  mods: names out of RML2016_MODS, an unknown one is refused by name; snrs_db: the grid's SNR values; sps: samples
     per symbol (for the analogue classes: per source sample); beta, span: the root-raised-cosine pulse of the linear classes (the
@@ -1801,7 +1905,12 @@ def synth_recipe(mods=RML2016_MODS, snrs_db=range(-20, 20, 2), sps: int = 8, bet
     offset is drawn uniformly in +-max_cfo cycles per sample; fsk_index: modulation index of CPFSK / GFSK; gfsk_bt: GFSK's
     bandwidth-time product; fm_deviation: WBFM's rms frequency deviation, cycles per sample; am_carrier: AM-DSB's carrier against
     a message of 4.9 sigma <= 32767 - am_carrier.  Gains are designed from each class's exact expected power (synth_expected_power),
-    so 10 log10(P_sig / P_noise) is the nominal SNR up to the gains' rounding (SynthRecipe.snr_exact_db)."""
+    so 10 log10(P_sig / P_noise) is the nominal SNR up to the gains' rounding (SynthRecipe.snr_exact_db).  fading: a SynthFading
+    of synth_fading, or None: with one, synth_frames and synth_dataset send every frame through that channel
+    (mdc_iq_synth_frames_faded) between the mixer and the gains; the tables and the plan blob are the same either way, and the
+    nominal SNR is then the average over the fading (the channel's mean power gain is fading.power_sum, one by design)."""
+    if fading is not None and not isinstance(fading, SynthFading):
+        raise TypeError("fading must be a SynthFading (synth_fading) or None")
     mods = tuple(mods)
     snrs = tuple(snrs_db)
     for m in mods:
@@ -1872,7 +1981,7 @@ def synth_recipe(mods=RML2016_MODS, snrs_db=range(-20, 20, 2), sps: int = 8, bet
     blob = synth_plan(classes, points_a, taps_a, gain_sig, gain_noise, max_step, q)
     with np.errstate(divide="ignore"):
         exact = 10.0 * np.log10(gs ** 2 * power[:, None] / (gn[None, :] ** 2 * 2.0 * SYNTH_NOISE_VARIANCE))
-    return SynthRecipe(mods, snrs, classes, points_a, taps_a, gain_sig, gain_noise, max_step, q, blob, power, exact)
+    return SynthRecipe(mods, snrs, classes, points_a, taps_a, gain_sig, gain_noise, max_step, q, blob, power, exact, fading)
 
 
 def _synth_blob(recipe) -> np.ndarray:
@@ -1880,7 +1989,8 @@ def _synth_blob(recipe) -> np.ndarray:
 
 
 def synth_frames(n: int, recipe, seed: int = 2016, first_frame: int = 0, device=None, return_saturated: bool = False):
-    """n labelled frames of a recipe of synth_recipe, made on the device in one launch (mdc_iq_synth_frames): frame i is the grid's
+    """n labelled frames of a recipe of synth_recipe, made on the device in one launch (mdc_iq_synth_frames, or
+    mdc_iq_synth_frames_faded when the recipe carries a fading design): frame i is the grid's
     frame first_frame + i -- a function of (recipe, seed, that index) alone, so calls can be split, repeated and resumed bit for
     bit; class = index mod C, SNR entry = (index / C) mod S.  Returns (iq, labels, snr_db): the (n, 256) int16 device tensor of
     interleaved (I, Q) samples -- reshape(-1) is an ordinary "ci16" capture --, the int32 class indices and each frame's SNR
@@ -1899,11 +2009,15 @@ def synth_frames(n: int, recipe, seed: int = 2016, first_frame: int = 0, device=
     snr_index = torch.empty((n,), dtype=torch.int32, device=dev)
     sat = torch.zeros((1,), dtype=torch.int64, device=dev) if return_saturated else None
     plan_dev = torch.from_numpy(blob).to(dev)
+    args = (blob.ctypes.data, plan_dev.data_ptr(), blob.size, int(seed) % (1 << 64), int(first_frame) % (1 << 64), n, iq.data_ptr() if n else None,
+            labels.data_ptr() if n else None, snr_index.data_ptr() if n else None, sat.data_ptr() if sat is not None else None)
     with torch.cuda.device(dev):
-        _cabi.check(_cabi.lib().mdc_iq_synth_frames(blob.ctypes.data, plan_dev.data_ptr(), blob.size, int(seed) % (1 << 64), int(first_frame) % (1 << 64), n,
-                                                    iq.data_ptr() if n else None, labels.data_ptr() if n else None,
-                                                    snr_index.data_ptr() if n else None, sat.data_ptr() if sat is not None else None,
-                                                    torch.cuda.current_stream(dev).cuda_stream))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if recipe.fading is None:
+            _cabi.check(_cabi.lib().mdc_iq_synth_frames(*args, stream))
+        else:
+            record = np.ascontiguousarray(recipe.fading.record, dtype=_cabi.IQ_SYNTH_FADING)
+            _cabi.check(_cabi.lib().mdc_iq_synth_frames_faded(*args, record.ctypes.data, stream))
     whole = all(float(s) == int(s) for s in recipe.snrs_db)
     values = torch.tensor([int(s) if whole else float(s) for s in recipe.snrs_db], dtype=torch.int32 if whole else torch.float32, device=dev)
     snr_db = values[snr_index.long()]
