@@ -73,7 +73,10 @@ extern "C" {
                                   mdc_iq_synth_plan / mdc_iq_synth_plan_bytes / mdc_iq_synth_frames, mdc_iq_synth_class (labelled
                                   I/Q frames of a balanced modulation x SNR grid, synthesised on the device in exact integers);
                                   mdc_iq_synth_frames_faded, mdc_iq_synth_fading, mdc_iq_synth_path (the same frames through a
-                                  frequency-selective Rician channel) */
+                                  frequency-selective Rician channel);
+                                  mdc_iq_synth_scene / mdc_iq_synth_scene_bytes / mdc_iq_synth_scene_hops / mdc_iq_synth_capture /
+                                  mdc_iq_synth_capture_workspace_bytes, mdc_iq_synth_emitter (a scene of bursty and hopping
+                                  emitters rendered into one wideband capture, with the draws its truth table needs) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -933,6 +936,85 @@ typedef struct mdc_iq_synth_fading {
 MDC_API int mdc_iq_synth_frames_faded(const void* plan_host, const void* plan_dev, int64_t plan_bytes, uint64_t seed, uint64_t first_frame,
                                       int64_t n_frames, int16_t* iq_out_dev, int32_t* labels_dev, int32_t* snr_index_dev,
                                       uint64_t* saturated_dev, const mdc_iq_synth_fading* fading_host, void* hip_stream);
+
+/* ---- capture synthesis: a scene of emitters rendered into one wideband MDC_IQ_CI16 capture (additive in ABI 5) -----------------------
+ * The inverse of mdc_iq_extract: E emitters, each a class of a plan of mdc_iq_synth_plan with a rate, a carrier (or a hop set), a
+ * level and a burst schedule, summed with noise into ONE capture -- exact integers end to end, so the numpy restatement
+ * (tests/iq_synth_capture_ref.py) is held bit for bit.  Capture sample n is a function of (plan, scene, seed, n) alone.  Of the plan
+ * only the class records, alphabets and tap images are used; its gain tables, q and max_step are not.
+ *   draws      those of "frame synthesis": key = key_f with k_seed of the seed, d(j) = fmix32(key + j * 0xC2B2AE35), with f composed
+ *              per purpose (e: the emitter's index; fields do not overlap: the low part stays below 2^52):
+ *                  f = (e+1) 2^56 + 0 2^52 + (k >> 7)   symbol k >= 0 of emitter e; counters 16 + 4 (k & 127) + e', e' = 0 .. 3, used
+ *                                                       as the frames use 16 + 4 k + e' (an alphabet uses e' = 0 only)
+ *                  f = (e+1) 2^56 + 1 2^52              the emitter's constants: j = 0: tau = (d * sps) >> 32; j = 3: theta0 = d
+ *                  f = (e+1) 2^56 + 2 2^52 + w          dwell w: j = 0: hop index = (d * hops) >> 32
+ *                  f =          3 2^52 + (n >> 7)       noise of capture sample n: counters 1024 + 8 (n & 127) + 4 c + e', and g()
+ *   baseband   per emitter a stream z_i, i >= 0, at the class's sps: the source, pulse and mode lines of "frame synthesis", word for
+ *              word, at p = i + tau, with symbol indices k = p / sps + span - 1 - t unbounded above (and >= 0: no ramp-up).
+ *              MDC_SYNTH_PHASE: theta_i = theta0 + inc_0 + ... + inc_i (mod 2^32) over ALL i from 0, gated-off stretches included:
+ *              a continuous-phase emitter's phase is continuous across the whole capture.  |z| <= 32767 per component (the plan's
+ *              preconditions).
+ *   gate       start, on, period >= 0, in baseband samples.  The emitter is on at i iff i >= start and either period == 0 and
+ *              (on == 0 or i - start < on), or period > 0 and (i - start) mod period < on.  zg_i = z_i when on, else 0.  The dwell
+ *              of i is w(i) = (i - start) / period when period > 0 and i >= start, else 0.  The gate acts BEFORE the interpolation
+ *              filter, which therefore shapes the burst edges.
+ *   rate       L = interpolate, D = decimate (1 <= D <= L <= 32: an emitter is never decimated), T = ntaps real int16 Q15 taps h of
+ *              the scene's tap array, given in natural order.  For capture sample n: P = n D + T - 1, m = P / L, r = P mod L,
+ *                  acc_n = sum over i >= 0 with r + i L < T of h[r + i L] * zg_{m - i}            (re and im separately)
+ *              Every index m - i is >= 0 (i <= (T - 1 - r) / L gives m - i >= (P - T + 1) / L >= 0): no start-up ramp, no history.
+ *              Preconditions: ceil(T / L) <= 64, and for every branch r the sum over i of |h[r + i L]| <= 65535 (mdc_iq_resample's
+ *              bound): |acc| <= 32767 * 65535 < 2^31, 32-bit accumulation is exact.  u_n = clamp16((acc_n + 2^14) >> 15); clamped
+ *              components count into *saturated_dev.  Taps of frontend.design_resampler(L, D) (every branch sums to 32768) pass.
+ *   carrier    hops carriers phase_step[0 .. hops-1]; the one in use at n is that of the dwell of the LATEST baseband sample the
+ *              filter reads: h_n = hop index of w(m) (0 when hops == 1).  phi_n = phase0 + n * phase_step[h_n] (mod 2^32), referenced
+ *              to capture sample 0 whatever the schedule; (c, s) = the oscillator table's entry phi_n >> 20, and the mixer of
+ *              mdc_iq_ddc, word for word:  m_{e,n} = ((re u c - im u s + 32768) >> 16, (re u s + im u c + 32768) >> 16), |.| <= 32768.
+ *              hops > 1 requires period > 0 (a dwell is one period).
+ *   sum        per component, in int64, with w_n = g(the component's four noise draws):
+ *                  out_n = clamp(((sum over e of m_{e,n} * gain_e + w_n * gain_noise + 2^(q-1)) >> q) + dc, -32768, 32767)
+ *              Bound: 32 emitters * 32768 * 2^31 = 2^51, |w gain_noise| < 2^18 * 2^31 = 2^49, 2^(q-1) <= 2^39: |sum| < 2^52 < 2^62.
+ *              After the shift |.| < 2^51, so adding dc cannot wrap either.  Components the clamp changes are counted as well.
+ * Properties: the capture always starts at sample 0; a capture of n1 pairs is the first n1 pairs of a capture of n2 > n1 pairs, bit
+ * for bit (the count of clamped components is that of the pairs written); the same arguments give the same bits on every run; an
+ * emitter's m_{e,n} does not depend on which other emitters the scene holds, only on its own index e; E == 0 gives noise plus dc.
+ * Resuming at a sample other than 0 is out of scope: MDC_SYNTH_PHASE would need a carried phase.
+ * Truth: baseband sample i of an emitter is centred on capture sample (2 i L - (T - 1)) / (2 D) (the filter's centre, (T - 1) / 2
+ * interpolated samples); frontend.scene_truth rounds it half up, floor((2 i L - (T - 1) + D) / (2 D)), and clamps at 0.
+ *
+ * mdc_iq_synth_scene (host code, no GPU) validates a scene against its plan and writes the position-independent scene blob; hand
+ * mdc_iq_synth_capture the same bytes in host and in device memory, with the plan the scene was built for.  0 <= nemitters <= 32;
+ * taps_host: ntaps int16, 0 <= ntaps <= 32768; gain_noise >= 0; 1 <= q <= 40; per emitter: 0 <= cls < the plan's classes, 1 <=
+ * decimate <= interpolate <= 32, 1 <= ntaps <= 1024 inside taps_host, the two tap preconditions above, 1 <= hops <= 8, start, on,
+ * period in 0 .. 2^52, reserved 0.  scene_bytes must equal mdc_iq_synth_scene_bytes(nemitters, ntaps).  Every refusal is MDC_EINVAL
+ * with an error text that names the emitter.
+ * mdc_iq_synth_scene_hops (host code, no GPU): hop_index_out[i] = the hop index of dwell first_dwell + i of `emitter`, i < n.
+ * mdc_iq_synth_capture: out_dev takes n_pairs pairs (4-byte aligned); saturated_dev (8-byte aligned, +=, the caller zeroes it) may be
+ * NULL; scene_dev and plan_dev are 8-byte aligned; workspace_dev (4-byte aligned) holds at least
+ * mdc_iq_synth_capture_workspace_bytes(scene, n_pairs) bytes (0 for a scene without an MDC_SYNTH_PHASE emitter; NULL is then
+ * accepted) and needs no initialisation; 0 <= n_pairs <= 2^34; n_pairs == 0 is MDC_OK without a launch.  The call only enqueues on
+ * hip_stream (no synchronisation, no allocation, no copy: capturable in a hipGraph) and runs on the current device. */
+typedef struct mdc_iq_synth_emitter {
+    int32_t cls;               /* index into the plan's classes */
+    int32_t interpolate;       /* L, 1..32 */
+    int32_t decimate;          /* D, 1..L */
+    int32_t first_tap, ntaps;  /* the interpolation filter: taps first_tap .. first_tap + ntaps - 1 of the scene's tap array */
+    int32_t gain;              /* gain_e */
+    uint32_t phase0;           /* carrier phase at capture sample 0 */
+    int32_t hops;              /* carriers in use, 1..8 */
+    uint32_t phase_step[8];    /* the carriers (2^32 = one cycle per capture sample) */
+    int64_t start, on, period; /* burst schedule, in baseband samples */
+    int32_t reserved[2];       /* 0 */
+} mdc_iq_synth_emitter;        /* 96 bytes */
+MDC_API int64_t mdc_iq_synth_scene_bytes(int32_t nemitters, int64_t ntaps);
+MDC_API int mdc_iq_synth_scene(const void* plan_host, int64_t plan_bytes, const mdc_iq_synth_emitter* emitters_host, int32_t nemitters,
+                               const int16_t* taps_host, int64_t ntaps, int32_t gain_noise, int32_t q, int16_t dc_re, int16_t dc_im,
+                               void* scene_host, int64_t scene_bytes);
+MDC_API int mdc_iq_synth_scene_hops(const void* scene_host, int64_t scene_bytes, uint64_t seed, int32_t emitter, int64_t first_dwell,
+                                    int64_t n, int32_t* hop_index_out);
+MDC_API int64_t mdc_iq_synth_capture_workspace_bytes(const void* scene_host, int64_t scene_bytes, int64_t n_pairs);
+MDC_API int mdc_iq_synth_capture(const void* scene_host, const void* scene_dev, int64_t scene_bytes, const void* plan_host,
+                                 const void* plan_dev, int64_t plan_bytes, uint64_t seed, int64_t n_pairs, int16_t* out_dev,
+                                 uint64_t* saturated_dev, void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
 /* test_Y_hat = model.predict(X_test, batch_size=batch_size)  (cnn.py:198, 237) when X_test lies in HOST memory -- a
  * numpy array, or whatever buffer a cgo / JNI / N-API caller holds: the library's own driver in front of mdc_forward.

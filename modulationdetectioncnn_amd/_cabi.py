@@ -45,6 +45,7 @@ EXPORTS = [
     "mdc_iq_balance", "mdc_iq_balance_stats", "mdc_iq_balance_blocks",
     "mdc_iq_cf32_histogram", "mdc_iq_cf32_quantize",
     "mdc_iq_synth_plan_bytes", "mdc_iq_synth_plan", "mdc_iq_synth_frames", "mdc_iq_synth_frames_faded",
+    "mdc_iq_synth_scene_bytes", "mdc_iq_synth_scene", "mdc_iq_synth_scene_hops", "mdc_iq_synth_capture_workspace_bytes", "mdc_iq_synth_capture",
 ]
 ABI_VERSION = 5
 TRAIN_WEIGHTS, TRAIN_ADAM_M, TRAIN_ADAM_V, TRAIN_GRADIENT = 0, 1, 2, 3
@@ -106,6 +107,14 @@ IQ_SYNTH_FADING = np.dtype([("paths", np.int32), ("taps", np.int32), ("max_doppl
                             ("path", IQ_SYNTH_PATH, (4,))])
 SYNTH_MAX_PATHS, SYNTH_MAX_DELAY_TAPS, SYNTH_MAX_DOPPLER_STEP = 4, 16, 1 << 30
 SYNTH_FADING_TAP_ONE, SYNTH_FADING_GAIN_ONE, SYNTH_FADING_MAX_ABS_SUM = 16384, 8192, 32767
+# mdc_iq_synth_scene / mdc_iq_synth_capture: the emitter record of include/mdc.h (mdc_iq_synth_emitter, 96 B), its limits, and the
+# kernel's walk (csrc/iq_synth_capture.hip: one work-group per tile of SYNTH_CAPTURE_TILE pairs, at most SYNTH_CAPTURE_GRID_CAP)
+IQ_SYNTH_EMITTER = np.dtype([("cls", np.int32), ("interpolate", np.int32), ("decimate", np.int32), ("first_tap", np.int32), ("ntaps", np.int32),
+                             ("gain", np.int32), ("phase0", np.uint32), ("hops", np.int32), ("phase_step", np.uint32, (8,)), ("start", np.int64),
+                             ("on", np.int64), ("period", np.int64), ("reserved", np.int32, (2,))])
+SYNTH_SCENE_MAX_EMITTERS, SYNTH_SCENE_MAX_INTERPOLATE, SYNTH_SCENE_MAX_TAPS, SYNTH_SCENE_MAX_BRANCH_TAPS = 32, 32, 1024, 64
+SYNTH_SCENE_MAX_BRANCH_ABS_SUM, SYNTH_SCENE_MAX_HOPS, SYNTH_SCENE_MAX_TIME, SYNTH_CAPTURE_MAX_PAIRS = 65535, 8, 1 << 52, 1 << 34
+SYNTH_CAPTURE_TILE, SYNTH_CAPTURE_GRID_CAP = 1024, 4096
 # mdc_iq_resample: limits of include/mdc.h (taps and decimation as the DDC's; the sum |h| bound holds per BRANCH), and the kernel's
 # tiling (csrc/iq_resample.hip): a tile is ((RESAMPLE_TILE_PAIRS - ceil(T / L)) // D) * L outputs, RESAMPLE_GRID_CAP work-groups
 RESAMPLE_MAX_INTERPOLATE, RESAMPLE_MAX_DECIMATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BRANCH_ABS_SUM = 32, 256, 1024, 65535
@@ -247,7 +256,10 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_iq_cf32_quantize", [vp, i64, C.c_float, vp, vp, vp]),
                        ("mdc_iq_synth_plan", [vp, C.c_int32, vp, i64, vp, i64, vp, i64, vp, C.c_int32, C.c_uint32, C.c_int32, vp, i64]),
                        ("mdc_iq_synth_frames", [vp, vp, i64, C.c_uint64, C.c_uint64, i64, vp, vp, vp, vp, vp]),
-                       ("mdc_iq_synth_frames_faded", [vp, vp, i64, C.c_uint64, C.c_uint64, i64, vp, vp, vp, vp, vp, vp])):
+                       ("mdc_iq_synth_frames_faded", [vp, vp, i64, C.c_uint64, C.c_uint64, i64, vp, vp, vp, vp, vp, vp]),
+                       ("mdc_iq_synth_scene", [vp, i64, vp, C.c_int32, vp, i64, C.c_int32, C.c_int32, C.c_int16, C.c_int16, vp, i64]),
+                       ("mdc_iq_synth_scene_hops", [vp, i64, C.c_uint64, C.c_int32, i64, i64, vp]),
+                       ("mdc_iq_synth_capture", [vp, vp, i64, vp, vp, i64, C.c_uint64, i64, vp, vp, vp, i64, vp])):
         fn = getattr(L, name, None)
         if fn is not None:
             fn.argtypes, fn.restype = args, i32
@@ -261,6 +273,10 @@ def lib(variant: str = "product") -> C.CDLL:
         L.mdc_iq_extract_plan_bytes.argtypes, L.mdc_iq_extract_plan_bytes.restype = [i64, C.c_int32, vp, vp], i64
     if getattr(L, "mdc_iq_synth_plan_bytes", None) is not None:
         L.mdc_iq_synth_plan_bytes.argtypes, L.mdc_iq_synth_plan_bytes.restype = [C.c_int32, C.c_int32, vp], i64
+    if getattr(L, "mdc_iq_synth_scene_bytes", None) is not None:
+        L.mdc_iq_synth_scene_bytes.argtypes, L.mdc_iq_synth_scene_bytes.restype = [C.c_int32, i64], i64
+    if getattr(L, "mdc_iq_synth_capture_workspace_bytes", None) is not None:
+        L.mdc_iq_synth_capture_workspace_bytes.argtypes, L.mdc_iq_synth_capture_workspace_bytes.restype = [vp, i64, i64], i64
     if getattr(L, "mdc_iq_spectrogram_rows", None) is not None:
         L.mdc_iq_spectrogram_rows.argtypes, L.mdc_iq_spectrogram_rows.restype = [i64, i32, i64, i32], i64
     if getattr(L, "mdc_iq_line_spectra_rows", None) is not None:

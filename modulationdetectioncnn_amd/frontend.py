@@ -2033,3 +2033,318 @@ def synth_dataset(n: int, recipe, seed: int = 2016, level: float = DEFAULT_LEVEL
         import torch
         return torch.empty((0, 2, HOP_FRAME), dtype=torch.float32, device=iq.device), labels, snr_db
     return normalized_frames_from_iq(iq.reshape(-1), "ci16", level=level, hop=HOP_FRAME), labels, snr_db
+
+
+# ---- capture synthesis (mdc_iq_synth_scene / mdc_iq_synth_capture): a scene of emitters rendered into one wideband capture ------
+class SynthScene(NamedTuple):
+    """What synth_scene designs: the emitter records and the tap array as mdc_iq_synth_scene takes them, the scene blob, and what
+    the design knows.  Per emitter: mods (the class's name), centres (a tuple of up to 8, cycles per capture sample), bandwidth
+    (cycles per capture sample), rms (the exact expected complex rms while on, from the integer gain and the recipe's exact
+    power), level_db (that rms against the noise inside the bandwidth; +inf without noise), passband_deviation (the worst
+    | |H(f)|^2 - 1 | of the interpolation filter over the class's band).  noise_rms: what the integer gain_noise gives."""
+    recipe: "SynthRecipe"
+    emitters: np.ndarray
+    taps: np.ndarray
+    gain_noise: int
+    q: int
+    dc: tuple
+    blob: np.ndarray
+    mods: tuple
+    centres: tuple
+    bandwidth: tuple
+    rms: tuple
+    level_db: tuple
+    passband_deviation: tuple
+    noise_rms: float
+
+
+SCENE_TRUTH = np.dtype([("emitter", np.int32), ("mod", "U16"), ("label", np.int32), ("dwell", np.int64), ("first_pair", np.int64),
+                        ("stop_pair", np.int64), ("centre", np.float64), ("bandwidth", np.float64), ("level_db", np.float64),
+                        ("whole", np.bool_)])
+
+
+def synth_class_bandwidth(recipe, k: int) -> float:
+    """The occupied (two-sided) bandwidth of class k of a recipe, in cycles per BASEBAND sample.  LINEAR classes: the band around
+    the pulse's spectral centroid that holds 99 % of the pulse's energy (a root-raised-cosine of roll-off beta gives about (1 +
+    beta / 2) / sps).  PHASE classes: Carson's rule, 2 (deviation + the pulse's own 99 % half band), the deviation being
+    phase_factor times the largest |y| an alphabet gives (two standard deviations of y for a Gaussian source)."""
+    c = recipe.classes[k]
+    sps, span = int(c["sps"]), int(c["span"])
+    h = recipe.taps[int(c["first_tap"]):int(c["first_tap"]) + sps * span].astype(np.float64)
+    h = h[:, 0] + 1j * h[:, 1]
+    N = 4096
+    p = np.abs(np.fft.fftshift(np.fft.fft(h, N))) ** 2
+    f = (np.arange(N) - N // 2) / float(N)
+    centroid = int(np.clip(round(float(np.sum(f * p) / p.sum()) * N) + N // 2, 0, N - 1))
+    half = 0
+    while half < N // 2 and p[max(centroid - half, 0):centroid + half + 1].sum() < 0.99 * p.sum():
+        half += 1
+    own = (2 * half + 1) / float(N)
+    if int(c["mode"]) != _cabi.SYNTH_PHASE:
+        return min(own, 1.0)
+    branch = max(float(np.abs(h[b::sps]).sum()) for b in range(sps)) / 32768.0
+    if int(c["source"]) == _cabi.SYNTH_GAUSS:
+        y = 2.0 * np.sqrt(SYNTH_NOISE_VARIANCE * np.mean([np.sum(np.abs(h[b::sps]) ** 2) for b in range(sps)])) / 32768.0
+    else:
+        pts = recipe.points[int(c["first_point"]):int(c["first_point"]) + int(c["points"])].astype(np.float64)
+        y = float(np.abs(pts[:, 0]).max()) * branch
+    return min(2.0 * (abs(int(c["phase_factor"])) * y / 2.0 ** 32 + own / 2.0), 1.0)
+
+
+def _scene_ratio(target: float):
+    """(L, D) with 1 <= D <= L <= 32 closest to target = L / D (ties: the smaller L)"""
+    best = None
+    for L in range(1, _cabi.SYNTH_SCENE_MAX_INTERPOLATE + 1):
+        for D in range(1, L + 1):
+            if np.gcd(L, D) == 1:
+                err = abs(L / D - target)
+                if best is None or err < best[0] - 1e-15:
+                    best = (err, L, D)
+    return best[1], best[2]
+
+
+def synth_scene(recipe, emitters, noise_rms: float, q: int = _SYNTH_Q, dc=(0, 0)) -> SynthScene:
+    """Design a scene for synth_capture (include/mdc.h, "capture synthesis"; numpy on the host, no GPU).  recipe: a SynthRecipe;
+    emitters: up to 32 mappings with
+      mod                 a name in recipe.mods
+      samples_per_symbol  capture samples per symbol (>= the recipe's sps), met by the closest L / D with D <= L <= 32 -- or
+      interpolate, decimate   L and D themselves (capture samples per symbol = sps L / D)
+      centre              cycles per capture sample in [-0.5, 0.5], or a sequence of up to 8 for a hopper (needs period)
+      level_db            the emitter's power while on against the scene's noise INSIDE the emitter's bandwidth, in dB -- or
+      rms                 its complex rms while on, in int16 units
+      start, on, period   the burst schedule in CAPTURE samples (default 0, 0, 0: always on), each converted to baseband samples
+                          by D / L and rounded to the nearest (an on > 0 stays >= 1)
+      phase0              the carrier's 32-bit phase at capture sample 0 (default 0)
+    noise_rms: the complex rms of the scene's noise in int16 units (0: none; level_db then needs rms instead).  Filters are
+    design_resampler(L, D) (L == 1: the single tap 32767); equal ones are stored once.  Gains come from recipe.power[class], the
+    exact expectation; the scene reports what the rounded integers give.  Bad arguments are refused by name (ValueError)."""
+    if not isinstance(recipe, SynthRecipe):
+        raise TypeError("recipe must be a SynthRecipe (synth_recipe)")
+    emitters = list(emitters)
+    if len(emitters) > _cabi.SYNTH_SCENE_MAX_EMITTERS:
+        raise ValueError(f"emitters: a scene holds at most {_cabi.SYNTH_SCENE_MAX_EMITTERS} (got {len(emitters)})")
+    noise_rms, q = float(noise_rms), int(q)
+    if not (np.isfinite(noise_rms) and noise_rms >= 0.0):
+        raise ValueError(f"noise_rms must be >= 0 and finite (got {noise_rms})")
+    if not 1 <= q <= _cabi.SYNTH_MAX_Q:
+        raise ValueError(f"q must be in 1..{_cabi.SYNTH_MAX_Q} (got {q})")
+    dc = (int(dc[0]), int(dc[1]))
+    if not all(-32768 <= v <= 32767 for v in dc):
+        raise ValueError(f"dc must fit int16 (got {dc})")
+    gn = int(round(2.0 ** q * noise_rms / np.sqrt(2.0 * SYNTH_NOISE_VARIANCE)))
+    if gn > 2 ** 31 - 1:
+        raise ValueError("noise_rms is too large for the gain's int32 at this q")
+    noise_exact = gn * np.sqrt(2.0 * SYNTH_NOISE_VARIANCE) / 2.0 ** q
+    rec = np.zeros(len(emitters), _cabi.IQ_SYNTH_EMITTER)
+    filters, taps, ntaps = {}, [], 0
+    mods, centres, bws, rmss, levels, devs = [], [], [], [], [], []
+    known = {"mod", "samples_per_symbol", "interpolate", "decimate", "centre", "level_db", "rms", "start", "on", "period", "phase0"}
+    for k, em in enumerate(emitters):
+        who = f"emitter {k}"
+        unknown = set(em) - known
+        if unknown:
+            raise ValueError(f"{who}: unknown key(s) {sorted(unknown)}")
+        if em.get("mod") not in recipe.mods:
+            raise ValueError(f"{who}: mod {em.get('mod')!r} is not in the recipe ({', '.join(recipe.mods)})")
+        cls = recipe.mods.index(em["mod"])
+        sps = int(recipe.classes[cls]["sps"])
+        if "samples_per_symbol" in em:
+            if "interpolate" in em or "decimate" in em:
+                raise ValueError(f"{who}: give samples_per_symbol or (interpolate, decimate), not both")
+            target = float(em["samples_per_symbol"]) / sps
+            if not 1.0 <= target <= _cabi.SYNTH_SCENE_MAX_INTERPOLATE:
+                raise ValueError(f"{who}: samples_per_symbol must be in {sps}..{sps * _cabi.SYNTH_SCENE_MAX_INTERPOLATE} (got {em['samples_per_symbol']})")
+            L, D = _scene_ratio(target)
+        else:
+            L, D = int(em.get("interpolate", 1)), int(em.get("decimate", 1))
+            if not 1 <= L <= _cabi.SYNTH_SCENE_MAX_INTERPOLATE:
+                raise ValueError(f"{who}: interpolate must be in 1..{_cabi.SYNTH_SCENE_MAX_INTERPOLATE} (got {L})")
+            if not 1 <= D <= L:
+                raise ValueError(f"{who}: decimate must be in 1..interpolate = {L} (got {D})")
+        if (L, D) not in filters:
+            h = np.array([32767], np.int16) if L == 1 else design_resampler(L, D)
+            filters[L, D] = (ntaps, h)
+            taps.append(h)
+            ntaps += h.size
+        first_tap, h = filters[L, D]
+        cs = em.get("centre", 0.0)
+        cs = tuple(float(c) for c in (cs if isinstance(cs, (tuple, list, np.ndarray)) else (cs,)))
+        if not 1 <= len(cs) <= _cabi.SYNTH_SCENE_MAX_HOPS:
+            raise ValueError(f"{who}: centre takes 1..{_cabi.SYNTH_SCENE_MAX_HOPS} carriers (got {len(cs)})")
+        for c in cs:
+            if not -0.5 <= c <= 0.5:
+                raise ValueError(f"{who}: centre {c} is outside [-0.5, 0.5] cycles per sample")
+        sched = []
+        for name in ("start", "on", "period"):
+            v = float(em.get(name, 0))
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"{who}: {name} must be >= 0 (got {em.get(name)})")
+            b = int(round(v * D / L))
+            sched.append(max(b, 1) if v > 0 and name != "start" else b)
+        if len(cs) > 1 and sched[2] == 0:
+            raise ValueError(f"{who}: a hopper ({len(cs)} centres) needs a period > 0: a dwell is one period")
+        bw = synth_class_bandwidth(recipe, cls) * D / L
+        power = float(recipe.power[cls])
+        if ("level_db" in em) == ("rms" in em):
+            raise ValueError(f"{who}: give level_db or rms (one of them)")
+        if "rms" in em:
+            rms = float(em["rms"])
+        else:
+            if gn == 0:
+                raise ValueError(f"{who}: level_db is relative to the scene's noise, which is 0: give rms")
+            rms = noise_exact * np.sqrt(min(bw, 1.0) * 10.0 ** (float(em["level_db"]) / 10.0))
+        if not (np.isfinite(rms) and rms >= 0):
+            raise ValueError(f"{who}: rms must be >= 0 and finite (got {rms})")
+        gain = int(round(2.0 ** q * rms / np.sqrt(power)))
+        if gain > 2 ** 31 - 1:
+            raise ValueError(f"{who}: the level needs a gain beyond int32 at q = {q}")
+        r = rec[k]
+        r["cls"], r["interpolate"], r["decimate"], r["first_tap"], r["ntaps"], r["gain"] = cls, L, D, first_tap, h.size, gain
+        r["phase0"], r["hops"] = int(em.get("phase0", 0)) % (1 << 32), len(cs)
+        r["phase_step"][:len(cs)] = [phase_step(c) for c in cs]
+        r["start"], r["on"], r["period"] = sched
+        exact = gain * np.sqrt(power) / 2.0 ** q
+        f = np.linspace(-0.5, 0.5, 129) * synth_class_bandwidth(recipe, cls) / L      # the class's band at the interpolated rate
+        H = np.exp(-2j * np.pi * f[:, None] * np.arange(h.size)[None, :]) @ (h.astype(np.float64) / (32768.0 * L))
+        mods.append(em["mod"])
+        centres.append(cs)
+        bws.append(bw)
+        rmss.append(exact)
+        with np.errstate(divide="ignore"):
+            levels.append(float(10.0 * np.log10(exact ** 2 / (noise_exact ** 2 * min(bw, 1.0)))) if gn and exact > 0 else float("inf") if exact > 0 else float("-inf"))
+        devs.append(float(np.abs(np.abs(H) ** 2 - 1.0).max()))
+    taps_a = np.concatenate(taps) if taps else np.zeros(0, np.int16)
+    blob = synth_scene_blob(recipe.blob, rec, taps_a, gn, q, dc)
+    return SynthScene(recipe, rec, taps_a, gn, q, dc, blob, tuple(mods), tuple(centres), tuple(bws), tuple(rmss), tuple(levels), tuple(devs),
+                      float(noise_exact))
+
+
+def synth_scene_blob(plan_blob, emitters, taps, gain_noise: int, q: int, dc=(0, 0)) -> np.ndarray:
+    """mdc_iq_synth_scene (host code, no GPU): the scene blob of emitter records (_cabi.IQ_SYNTH_EMITTER) and an int16 tap array,
+    validated against the plan blob they index.  Every refusal is a _cabi.MdcError that names the emitter."""
+    plan_blob = np.ascontiguousarray(plan_blob, dtype=np.uint8)
+    emitters = np.ascontiguousarray(emitters, dtype=_cabi.IQ_SYNTH_EMITTER).reshape(-1)
+    taps = np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
+    lib = _cabi.lib()
+    nbytes = max(_cabi.check(lib.mdc_iq_synth_scene_bytes(min(emitters.size, _cabi.SYNTH_SCENE_MAX_EMITTERS), taps.size)), 0)
+    blob = np.empty(nbytes, np.uint8)
+    _cabi.check(lib.mdc_iq_synth_scene(plan_blob.ctypes.data, plan_blob.size, emitters.ctypes.data, emitters.size, taps.ctypes.data, taps.size,
+                                       int(gain_noise), int(q), int(dc[0]), int(dc[1]), blob.ctypes.data, nbytes))
+    return blob
+
+
+def synth_scene_hops(scene, seed: int, emitter: int, first_dwell: int, n: int) -> np.ndarray:
+    """mdc_iq_synth_scene_hops (host code, no GPU): the hop indices of dwells first_dwell .. first_dwell + n - 1 of an emitter."""
+    blob = np.ascontiguousarray(scene.blob if isinstance(scene, SynthScene) else scene, dtype=np.uint8)
+    out = np.empty(int(n), np.int32)
+    _cabi.check(_cabi.lib().mdc_iq_synth_scene_hops(blob.ctypes.data, blob.size, int(seed) % (1 << 64), int(emitter), int(first_dwell), int(n),
+                                                    out.ctypes.data))
+    return out
+
+
+def synth_capture(n_pairs: int, scene, seed: int = 2016, device=None, return_saturated: bool = False):
+    """The first n_pairs pairs of a scene of synth_scene, rendered on the device (mdc_iq_synth_capture): a flat int16 device tensor
+    of 2 n_pairs interleaved (I, Q) samples, an ordinary "ci16" capture for scan_iq / detect_iq / spectrogram.  A function of
+    (scene, seed) alone; a shorter capture is a prefix of a longer one, bit for bit.  With return_saturated also the number of
+    components a clamp changed (one synchronising read).  Enqueues on torch's current stream."""
+    import torch
+    if not isinstance(scene, SynthScene):
+        raise TypeError("scene must be a SynthScene (synth_scene)")
+    n = int(n_pairs)
+    if n < 0:
+        raise ValueError("n_pairs must be >= 0")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    blob, plan = np.ascontiguousarray(scene.blob, dtype=np.uint8), _synth_blob(scene.recipe)
+    lib = _cabi.lib()
+    wbytes = _cabi.check(lib.mdc_iq_synth_capture_workspace_bytes(blob.ctypes.data, blob.size, n))
+    out = torch.empty((2 * n,), dtype=torch.int16, device=dev)
+    work = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
+    sat = torch.zeros((1,), dtype=torch.int64, device=dev) if return_saturated else None
+    scene_dev, plan_dev = torch.from_numpy(blob).to(dev), torch.from_numpy(plan).to(dev)
+    with torch.cuda.device(dev):
+        _cabi.check(lib.mdc_iq_synth_capture(blob.ctypes.data, scene_dev.data_ptr(), blob.size, plan.ctypes.data, plan_dev.data_ptr(), plan.size,
+                                             int(seed) % (1 << 64), n, out.data_ptr() if n else None, sat.data_ptr() if sat is not None else None,
+                                             work.data_ptr(), wbytes, torch.cuda.current_stream(dev).cuda_stream))
+    return (out, int(sat.item())) if return_saturated else out
+
+
+def scene_pair(i, interpolate: int, decimate: int, ntaps: int):
+    """The capture pair on which baseband sample i of an emitter is centred (include/mdc.h: the interpolation filter's centre,
+    (ntaps - 1) / 2 interpolated samples): floor((2 i L - (T - 1) + D) / (2 D)), rounded half up, clamped at 0."""
+    i = np.asarray(i, np.int64)
+    return np.maximum((2 * i * int(interpolate) - (int(ntaps) - 1) + int(decimate)) // (2 * int(decimate)), 0)
+
+
+def scene_truth(scene, n_pairs: int, seed: int = 2016) -> np.ndarray:
+    """What a capture of synth_capture(n_pairs, scene, seed) holds (host only, no GPU): one SCENE_TRUTH record per (emitter, dwell)
+    whose on-time meets the capture -- emitter, mod, label (the class index), dwell, [first_pair, stop_pair) (clipped to the
+    capture), centre (the dwell's carrier: the hop draws are mdc_iq_synth_scene_hops'), bandwidth (cycles per capture sample,
+    synth_class_bandwidth at the emitter's rate), level_db, and whole: the dwell's on-time ends inside the capture.  An emitter
+    without a period has one record.  Baseband indices become capture pairs by scene_pair: a burst is on from the pair its
+    first baseband sample is centred on up to (not including) the pair its first off sample is centred on; the filter's and the
+    pulse's tails reach further on both sides."""
+    if not isinstance(scene, SynthScene):
+        raise TypeError("scene must be a SynthScene (synth_scene)")
+    n = int(n_pairs)
+    rows = []
+    for k, em in enumerate(scene.emitters):
+        L, D, T = int(em["interpolate"]), int(em["decimate"]), int(em["ntaps"])
+        start, on, period = int(em["start"]), int(em["on"]), int(em["period"])
+        count = ((n - 1) * D + T - 1) // L + 1 if n > 0 else 0          # baseband samples the capture reads
+        if count <= start:
+            continue
+        if period == 0:
+            dwells, first, stop = np.zeros(1, np.int64), np.array([start], np.int64), np.array([start + on if on else -1], np.int64)
+        else:
+            if on == 0:
+                continue
+            dwells = np.arange((count - 1 - start) // period + 1, dtype=np.int64)
+            first = start + dwells * period
+            stop = first + min(on, period)
+        first_pair = scene_pair(first, L, D, T)
+        stop_pair = np.where(stop < 0, n + 1, scene_pair(np.maximum(stop, 0), L, D, T))
+        whole = stop_pair <= n
+        keep = (first_pair < n) & (np.minimum(stop_pair, n) > first_pair)
+        hops = synth_scene_hops(scene, seed, k, 0, dwells.size) if int(em["hops"]) > 1 else np.zeros(dwells.size, np.int32)
+        for j in np.flatnonzero(keep):
+            rows.append((k, scene.mods[k], int(em["cls"]), int(dwells[j]), int(first_pair[j]), int(min(stop_pair[j], n)),
+                         scene.centres[k][int(hops[j])], scene.bandwidth[k], scene.level_db[k], bool(whole[j])))
+    return np.array(rows, dtype=SCENE_TRUTH)
+
+
+def score_detections(records, truth, min_overlap: float = 0.5, classes=None):
+    """Score detect_iq's records against scene_truth's (host code, numpy only).  A truth dwell is FOUND when some detection's
+    [first_pair, stop_pair) covers at least min_overlap of the dwell's pairs and the detection's centre lies inside the dwell's
+    band, |centre - truth centre| <= bandwidth / 2 (frequencies compared modulo one cycle per sample).  A detection that finds no
+    dwell is FALSE.  Returns a dict: found (pairs (truth index, detection index): per dwell the matching detection with the
+    largest overlap), missed (truth indices), false (detection indices), and confusion, an integer matrix [truth label, detected
+    label] over the found pairs whose detection has a label >= 0 (classes rows and columns; default: the largest label + 1),
+    with accuracy, its trace over its sum (nan when empty)."""
+    truth = np.asarray(truth, dtype=SCENE_TRUTH)
+    recs = list(records)
+    if not 0.0 < float(min_overlap) <= 1.0:
+        raise ValueError(f"min_overlap must be in (0, 1] (got {min_overlap})")
+    d_first = np.array([int(r["first_pair"]) for r in recs], np.int64)
+    d_stop = np.array([int(r["stop_pair"]) for r in recs], np.int64)
+    d_centre = np.array([float(r["centre"]) for r in recs], np.float64)
+    d_label = np.array([int(r.get("label", -1)) for r in recs], np.int64)
+    found, missed, matched = [], [], np.zeros(len(recs), bool)
+    for t, row in enumerate(truth):
+        length = int(row["stop_pair"] - row["first_pair"])
+        overlap = np.minimum(d_stop, row["stop_pair"]) - np.maximum(d_first, row["first_pair"])
+        df = np.abs((d_centre - row["centre"] + 0.5) % 1.0 - 0.5)
+        ok = (overlap >= min_overlap * length) & (overlap > 0) & (df <= row["bandwidth"] / 2.0)
+        matched |= ok
+        if ok.any():
+            found.append((t, int(np.flatnonzero(ok)[np.argmax(overlap[ok])])))
+        else:
+            missed.append(t)
+    labels = [int(truth["label"][t]) for t, d in found] + [int(d_label[d]) for t, d in found]
+    C = int(classes) if classes is not None else (max(labels) + 1 if labels else 0)
+    confusion = np.zeros((C, C), np.int64)
+    for t, d in found:
+        if 0 <= d_label[d] < C and 0 <= truth["label"][t] < C:
+            confusion[int(truth["label"][t]), int(d_label[d])] += 1
+    total = int(confusion.sum())
+    return dict(found=found, missed=missed, false=[int(i) for i in np.flatnonzero(~matched)], confusion=confusion,
+                accuracy=float(np.trace(confusion)) / total if total else float("nan"))
