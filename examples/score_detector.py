@@ -11,8 +11,11 @@ bins at different times -- or one emitter per --emitter flag:
 
 (samples per symbol and the schedule in capture samples; several centres make a hopper).  Weights come from --weights (a Keras
 .h5 file whose classes are the recipe's modulations in order), or from a short fit on synth_dataset of the same recipe.
+--net vtcnn2 classifies with the canonical VT-CNN2 instead of cnn.py's small net: its dense head is fitted to the recipe's classes
+with VTCNN2.fit_head for --head-epochs epochs (the conv layers stay as --weights or the synthetic initialisation gives them).
 
     python examples/score_detector.py [--pairs 524288] [--noise-rms 300] [--seed 2016] [--emitter ...] [--weights FILE] [--epochs 3] [--scan]
+                                      [--net cnnpy|vtcnn2] [--head-epochs 3]
 """
 import argparse
 import os
@@ -46,8 +49,24 @@ def parse_emitter(text):
     return em
 
 
+def head_tuned_vtcnn2(recipe, args):
+    """The canonical VT-CNN2 with its dense head fitted to the recipe's classes (VTCNN2.fit_head; the conv layers are frozen)."""
+    if args.weights:
+        model = VTCNN2.from_h5(args.weights)
+    else:
+        model = VTCNN2.synthetic(Topology.vtcnn2(len(recipe.mods)), seed=args.seed)
+    if args.head_epochs <= 0:
+        return model
+    frames = min(args.frames, 1 << 14)      # 2^14 rows of 10,560 features: 0.7 GB
+    X, labels, _ = frontend.synth_dataset(frames, recipe, seed=args.seed + 1)
+    out = model.fit_head(X, labels, batch_size=1024, epochs=args.head_epochs, classes=len(recipe.mods), seed=args.seed, patience=None)
+    return out if isinstance(out, VTCNN2) else model
+
+
 def trained_model(recipe, args):
     from modulationdetectioncnn_amd.training import to_onehot
+    if args.net == "vtcnn2":
+        return head_tuned_vtcnn2(recipe, args)
     topo = Topology.cnnpy(10, 10, len(recipe.mods))      # cnn.py's net: the trainer takes any number of classes for it
     model = VTCNN2.synthetic(topo, seed=args.seed)
     if args.weights:
@@ -70,6 +89,8 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--frames", type=int, default=1 << 15, help="frames of the short fit")
     ap.add_argument("--min-overlap", type=float, default=0.5)
+    ap.add_argument("--net", choices=("cnnpy", "vtcnn2"), default="cnnpy", help="the classifier: cnn.py's small net (fit) or VT-CNN2 (fit_head)")
+    ap.add_argument("--head-epochs", type=int, default=3, help="--net vtcnn2: epochs of the head fit (0: classify with the weights as they are)")
     ap.add_argument("--scan", action="store_true", help="score scan_iq's emitters (one record per emitter, no time axis) instead of detect_iq's")
     args = ap.parse_args(argv)
     emitters = [parse_emitter(t) for t in args.emitter] or default_emitters()

@@ -76,7 +76,9 @@ extern "C" {
                                   frequency-selective Rician channel);
                                   mdc_iq_synth_scene / mdc_iq_synth_scene_bytes / mdc_iq_synth_scene_hops / mdc_iq_synth_capture /
                                   mdc_iq_synth_capture_workspace_bytes, mdc_iq_synth_emitter (a scene of bursty and hopping
-                                  emitters rendered into one wideband capture, with the draws its truth table needs) */
+                                  emitters rendered into one wideband capture, with the draws its truth table needs);
+                                  mdc_head_trainer_* / mdc_head_train_batch (head training: the dense layers of VT-CNN2 on
+                                  precomputed feature rows) */
 
 /* error codes (negative errno values) */
 #define MDC_OK        0
@@ -1143,6 +1145,52 @@ MDC_API int mdc_trainer_read(mdc_trainer* t, int reset, double* train_loss_sum, 
                      int64_t* eval_frames, int64_t* iterations, void* hip_stream);
 
 MDC_API void mdc_trainer_destroy(mdc_trainer* t);
+
+/* ---- head training: the dense layers of VT-CNN2 (or of any net that ends the same way) on precomputed feature rows --------
+ * mdc_trainer_create refuses MDC_KIND_VTCNN2.  Of its 2,830,427 parameters 2,706,443 sit in dense1 (10,560 x 256) and dense2
+ * (256 x C); with the two conv layers frozen no gradient flows back through the Flatten, and what is left to train is
+ *     features (K) -> Dense(H, relu) -> Dense(C) -> softmax
+ * over the rows that mdc_forward(..., MDC_TAP_FLAT) delivers at every dtype: transfer learning.  VT-CNN2 is (K, H, C) =
+ * (10560, 256, C); the bounds are K a multiple of 32 in 32..16384, H a multiple of 32 in 32..256, C in 2..16.  f32.
+ * Everything the "training" block above says holds here word for word unless stated otherwise: the loss (Keras 2.4's
+ * categorical cross-entropy on the softmax OUTPUT, q = p / sum(p) clipped to [1e-7, 1 - 1e-7], mean over `count`; the clip
+ * passes no gradient outside its interval, the ReLU none where z1 <= 0; target rows may be any distribution), TensorFlow 2.4's
+ * Adam with its step count on the device, apply = 0, the MDC_TRAIN_* tensor kinds, the skipped-and-counted out-of-range index
+ * that makes the next read return MDC_EINVAL, enqueue-only batches (no synchronisation, no allocation, no copy: capturable in a
+ * hipGraph), bit-identical steps (fixed-order reductions, no float atomics -- also where the kernels split a batch over `count`
+ * or over K), one stream at a time per trainer.
+ * The training forward of one row f (feat_dev: f32 rows (n_rows, K), row-major, 16-byte aligned, the caller's device buffer):
+ *     a = f * s0;  z1 = a W1 + b1;  h = relu(z1) * s1;  z2 = h W2 + b2;  p = softmax(z2)
+ * with s0 = s1 = 1 unless Dropout is on (mdc_head_trainer_set_dropout): then each is keep / (1 - rate) from the generator that
+ * mdc_trainer_set_dropout states, frame = the row's index in feat_dev, site 0 = the features (e = index in the row), site 1 =
+ * the hidden units.  Backward: dW1 = a^T dz1, db1 = sum dz1, dW2 = h^T dz2, db2 = sum dz2; there is no feature gradient.
+ * Evaluation has no Dropout; besides the loss sum and the row count it counts the rows whose arg-max of p equals the arg-max
+ * of their target row (the lowest index on a tie, both sides).
+ * Layer 0 is dense1 (kernel K x H, bias H), layer 1 dense2 (kernel H x C, bias C): Keras' (in, out) layouts.
+ * A training batch is five launches (Z1 partial products, the row kernel, dW1 partial products, the small gradients, reduce +
+ * Adam) and, with apply != 0, a one-thread sixth that advances the step count; an evaluation is three. */
+typedef struct mdc_head_trainer mdc_head_trainer;   /* opaque: f32 master weights, Adam state, all scratch for max_batch rows */
+
+/* All device memory is allocated here; 1 <= max_batch <= 65536 bounds `count` of every later call. */
+MDC_API int mdc_head_trainer_create(int features, int hidden, int classes, int64_t max_batch, int device, mdc_head_trainer** out);
+MDC_API int mdc_head_trainer_set_adam(mdc_head_trainer* t, float lr, float beta1, float beta2, float eps);
+/* Dropout(rate_features) in front of dense1 and Dropout(rate_hidden) behind it, each in [0, 1); 0 = off (the default). */
+MDC_API int mdc_head_trainer_set_dropout(mdc_head_trainer* t, float rate_features, float rate_hidden, uint32_t seed);
+MDC_API int mdc_head_trainer_set_tensor(mdc_head_trainer* t, int which, int layer, const float* kernel_host, size_t kernel_elems,
+                                const float* bias_host, size_t bias_elems, void* hip_stream);
+MDC_API int mdc_head_trainer_get_tensor(mdc_head_trainer* t, int which, int layer, float* kernel_host, size_t kernel_elems,
+                                float* bias_host, size_t bias_elems, void* hip_stream);
+MDC_API int mdc_head_trainer_set_iterations(mdc_head_trainer* t, int64_t iterations, void* hip_stream);
+/* One step on the rows order_dev[first .. first + count) of (feat_dev, y_dev); y_dev: f32 target rows (n_rows, C).
+ * count <= max_batch.  A batch before both layers' MDC_TRAIN_WEIGHTS are set is MDC_ESTATE. */
+MDC_API int mdc_head_train_batch(mdc_head_trainer* t, const float* feat_dev, const float* y_dev, int64_t n_rows, const int32_t* order_dev,
+                         int64_t first, int64_t count, int apply, void* hip_stream);
+MDC_API int mdc_head_trainer_evaluate(mdc_head_trainer* t, const float* feat_dev, const float* y_dev, int64_t n_rows, const int32_t* order_dev,
+                              int64_t first, int64_t count, void* hip_stream);
+/* As mdc_trainer_read, plus eval_correct; reset != 0 zeroes the five statistics (not `iterations`). */
+MDC_API int mdc_head_trainer_read(mdc_head_trainer* t, int reset, double* train_loss_sum, int64_t* train_rows, double* eval_loss_sum,
+                          int64_t* eval_rows, int64_t* eval_correct, int64_t* iterations, void* hip_stream);
+MDC_API void mdc_head_trainer_destroy(mdc_head_trainer* t);
 
 MDC_API const char* mdc_last_error(void);
 MDC_API void mdc_destroy(mdc_model* m);

@@ -31,6 +31,8 @@ EXPORTS = [
     "mdc_trainer_create", "mdc_trainer_num_layers", "mdc_trainer_layer_sizes", "mdc_trainer_set_adam", "mdc_trainer_set_dropout", "mdc_trainer_set_tensor",
     "mdc_trainer_get_tensor", "mdc_trainer_set_iterations", "mdc_train_batch", "mdc_trainer_evaluate", "mdc_trainer_read",
     "mdc_trainer_destroy",
+    "mdc_head_trainer_create", "mdc_head_trainer_set_adam", "mdc_head_trainer_set_dropout", "mdc_head_trainer_set_tensor", "mdc_head_trainer_get_tensor",
+    "mdc_head_trainer_set_iterations", "mdc_head_train_batch", "mdc_head_trainer_evaluate", "mdc_head_trainer_read", "mdc_head_trainer_destroy",
     "mdc_forward_checked", "mdc_predict_host_checked",
     "mdc_iq_u8_windows_norm", "mdc_predict_host_iq_u8_norm",
     "mdc_iq_windows", "mdc_iq_windows_norm", "mdc_predict_host_iq", "mdc_predict_host_iq_norm",
@@ -299,6 +301,22 @@ def lib(variant: str = "product") -> C.CDLL:
     L.mdc_trainer_read.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64), vp]
     L.mdc_trainer_destroy.argtypes = [vp]
     L.mdc_trainer_destroy.restype = None
+    # head training (getattr with a default, as above: tools/ab_libs.py loads builds from before these entries)
+    dp = C.POINTER(C.c_double)
+    for name, args in (("mdc_head_trainer_create", [i32, i32, i32, i64, i32, C.POINTER(vp)]),
+                       ("mdc_head_trainer_set_adam", [vp, C.c_float, C.c_float, C.c_float, C.c_float]),
+                       ("mdc_head_trainer_set_dropout", [vp, C.c_float, C.c_float, C.c_uint32]),
+                       ("mdc_head_trainer_set_tensor", [vp, i32, i32, fp, sz, fp, sz, vp]),
+                       ("mdc_head_trainer_get_tensor", [vp, i32, i32, fp, sz, fp, sz, vp]),
+                       ("mdc_head_trainer_set_iterations", [vp, i64, vp]),
+                       ("mdc_head_train_batch", [vp, vp, vp, i64, vp, i64, i64, i32, vp]),
+                       ("mdc_head_trainer_evaluate", [vp, vp, vp, i64, vp, i64, i64, vp]),
+                       ("mdc_head_trainer_read", [vp, i32, dp, C.POINTER(i64), dp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp])):
+        fn = getattr(L, name, None)
+        if fn is not None:
+            fn.argtypes, fn.restype = args, i32
+    if getattr(L, "mdc_head_trainer_destroy", None) is not None:
+        L.mdc_head_trainer_destroy.argtypes, L.mdc_head_trainer_destroy.restype = [vp], None
     for name in ("mdc_create", "mdc_num_layers", "mdc_layer_sizes", "mdc_set_weights", "mdc_finalize",
                  "mdc_forward", "mdc_set_profiling", "mdc_profile_slots", "mdc_profile_read", "mdc_profile_reset",
                  "mdc_forward_q612", "mdc_confusion", "mdc_iq_u8_to_frames", "mdc_set_fp8_input_absmax", "mdc_forward_iq_u8",

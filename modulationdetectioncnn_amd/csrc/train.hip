@@ -29,8 +29,7 @@
 //                    finish bumps it, after all have read it), so a captured hipGraph of an epoch replays correctly.
 // The batch of the reference (1,024 frames x 2,334 parameters) is launch-latency bound on this chip; that is why a step
 // is two launches and an epoch needs no host round trip but the final read of the loss.
-#include "dense_chain_common.h"      // mdc_internal.h, f32x4, row_allreduce (the 16-lane DPP butterflies of the softmax head)
-#include "mdc_fmix32.h"
+#include "train_common.h"           // dense_chain_common.h, fmix32, the Dropout generator, frame_index, wave_allsum
 
 #include <cmath>
 #include <cstddef>
@@ -66,7 +65,6 @@ namespace mdc {
 namespace {
 
 constexpr int kMaxWaves = 1024;      // partial gradient vectors per batch
-constexpr float kKerasEps = 1e-7f;   // K.epsilon()
 
 struct TrainState {
     long long iterations;      // Adam's `iter` (optimizer_weights/Adam/iter:0 of the .h5): completed updates
@@ -77,40 +75,6 @@ struct TrainState {
     unsigned tickets;          // work-groups of the running reduce + Adam launch that have read `iterations` (the last one bumps it)
     unsigned bad_indices;      // frames skipped because their index (order_dev's, or first + i) lay outside [0, n_frames): mdc_trainer_read reports them
 };
-
-// The optional Dropout's counter-based generator (include/mdc.h, mdc_trainer_set_dropout; oracle/oracle_train.py restates it):
-// keep an element iff fmix32(k_frame + element * 0xC2B2AE35) >= thr, k_frame = fmix32(k_step ^ (frame * 0x85EBCA6B + site)),
-// k_step = fmix32(seed + 0x9E3779B9 * (step + 1)); step = Adam's iteration count, read from the device (a replayed hipGraph
-// draws new masks at every step), frame = the frame's index in the data set (a frame's mask does not depend on its batch).
-struct DropArgs { unsigned seed, thr; float inv; };      // (fmix32: mdc_fmix32.h)
-__device__ __forceinline__ unsigned drop_step_key(const DropArgs& d, const TrainState* st) {
-    return fmix32(d.seed + 0x9E3779B9u * (unsigned)(st->iterations + 1));
-}
-__device__ __forceinline__ unsigned drop_frame_key(unsigned kstep, long frame, unsigned site) {
-    return fmix32(kstep ^ ((unsigned)frame * 0x85EBCA6Bu + site));
-}
-__device__ __forceinline__ bool drop_keep(unsigned kframe, unsigned element, unsigned thr) {
-    return fmix32(kframe + element * 0xC2B2AE35u) >= thr;
-}
-
-// The frame a batch position names, or -1 if that is no frame of the caller's buffers (a shuffle index out of range): such a
-// position is SKIPPED -- all-zero samples and targets contribute nothing to loss or gradient below -- and counted, once, by the
-// lane `count_it` names; mdc_trainer_read turns the count into an error.  An unchecked index would be a GPU fault instead.
-__device__ __forceinline__ long frame_index(const int* __restrict__ order, long first, int i, long n_frames, TrainState* st, bool count_it) {
-    const long idx = order ? (long)order[first + i] : first + i;
-    if ((unsigned long)idx < (unsigned long)n_frames) return idx;
-    if (count_it) atomicAdd(&st->bad_indices, 1u);
-    return -1;
-}
-
-// Sum over the wave, the same bits in every lane: the DPP butterfly over each 16-lane row (no LDS crossbar: __shfl_xor compiles to
-// ds_bpermute_b32, six dependent LDS round trips per sum), then the four row sums through scalar registers in a fixed order.
-__device__ __forceinline__ float wave_allsum(float v) {
-    v = row_allreduce(v, [](float a, float b) { return a + b; });
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16)),
-                r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return (r0 + r1) + (r2 + r3);
-}
 
 // softmax -> Keras categorical_crossentropy on the probabilities -> gradient w.r.t. the softmax INPUT.  y: the target row.
 template <int CMAX>
@@ -599,13 +563,13 @@ __global__ __launch_bounds__(1024) void train_adam_kernel(const float* __restric
             const float gmean = gsum / (float)count;
             grad[i] = gmean;
             if (mode == 2) {
-                const float t = (float)(it0 + 1);            // this update's number; `iterations` is bumped by the last work-group to finish
-                const float alpha = lr * sqrtf(1.f - powf(beta2, t)) / (1.f - powf(beta1, t));
-                const float mi = m[i] + (gmean - m[i]) * (1.f - beta1);
-                const float vi = v[i] + (gmean * gmean - v[i]) * (1.f - beta2);
+                // this update's number is it0 + 1; `iterations` is bumped by the last work-group to finish
+                const float alpha = adam_alpha(lr, beta1, beta2, it0 + 1);
+                float mi = m[i], vi = v[i], wi = params[i];
+                adam_update(gmean, mi, vi, wi, alpha, beta1, beta2, eps);
                 m[i] = mi;
                 v[i] = vi;
-                params[i] -= (mi * alpha) / (sqrtf(vi) + eps);
+                params[i] = wi;
             }
         }
     }

@@ -279,6 +279,77 @@ class VTCNN2:
         self._release()                     # the inference engine re-packs the new weights on its next use
         return hist
 
+    def head_features(self, X, chunk: int = 4096):
+        """The Flatten rows (n, 10560) float32 of X on the device, through THIS model's engine at its own dtype
+        (``forward_device(tap="flat")``), `chunk` frames at a time: what fit_head trains on."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device_index)
+        n = int(X.shape[0])
+        feat = torch.empty((n,) + self.tap_shape("flat"), dtype=torch.float32, device=dev)
+        for s in range(0, n, int(chunk)):
+            xs = X[s:s + chunk]
+            if not isinstance(xs, torch.Tensor):
+                xs = torch.from_numpy(np.ascontiguousarray(np.asarray(xs), dtype=np.float32))
+            xs = xs.to(device=dev, dtype=torch.float32).contiguous()
+            self.forward_device(xs, tap="flat", tap_out=feat[s:s + xs.shape[0]])
+        return feat
+
+    def fit_head(self, X, Y, batch_size: int = 1024, epochs: int = 100, validation_data=None, dropout: Tuple[float, float] = (0.5, 0.5),
+                 classes: Optional[int] = None, feature_budget_bytes: int = 32 << 30, patience: Optional[int] = 5,
+                 checkpoint: Optional[str] = None, shuffle: bool = True, seed: Optional[int] = None, verbose: int = 0, lr: float = 1e-3,
+                 beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-7, dropout_seed: int = 0, **kw):
+        """Fine-tune VT-CNN2's dense layers (dense1 10560 x 256, dense2 256 x C: 2,706,443 of its 2,830,427 parameters) with the two
+        conv layers frozen: transfer learning on the MI355X (csrc/head_train.hip; ``fit`` and ``Trainer`` do not train this net).
+        The features of X and of the validation set are computed ONCE, through this model's own engine at its own dtype
+        (head_features), so the head is tuned on what the deployed precision delivers; they must fit feature_budget_bytes.  Then
+        HeadTrainer.fit runs on them (batch_size, epochs, validation_data, patience, shuffle, seed, ``permutations=``,
+        ``callbacks=`` as ``fit`` takes them; dropout = the DeepSig definition's Dropout(0.5) in front of and behind dense1) and the
+        new dense weights are written back; the conv tensors are untouched, bit for bit.  Returns the history (also kept as
+        ``head_history``), with ``val_accuracy`` beside ``val_loss``.
+        classes=C' other than the topology's (a "noise" class, a twelfth modulation): dense2 is replaced by a fresh Glorot layer
+        (numpy Generator(seed)), dense1 is kept, and the call returns a NEW model with Topology.vtcnn2(C') that holds the fitted
+        head -- its history is its ``head_history``; this model is left as it was.
+        checkpoint: the full model's Keras .h5 at every improvement of val_loss, without optimiser state."""
+        from .formats.h5mini import write_keras_h5
+        from .training import HeadTrainer
+        if self.topology.kind != "vtcnn2":
+            raise ValueError(f"fit_head trains the dense head of the vtcnn2 topology, not {self.topology.kind!r}")
+        if self._weights is None:
+            raise RuntimeError("set or load weights (or VTCNN2.synthetic) before fit_head()")
+        K = int(np.prod(self.tap_shape("flat")))
+        rows = int(X.shape[0]) + (int(validation_data[0].shape[0]) if validation_data is not None else 0)
+        need = rows * K * 4
+        if need > int(feature_budget_bytes):
+            raise ValueError(f"the features of {rows} frames take {need} bytes, more than feature_budget_bytes = {int(feature_budget_bytes)}: "
+                             "fit on fewer frames or raise the budget")
+        Cn = self.topology.classes if classes is None else int(classes)
+        conv1, conv2, dense1, dense2 = self._weights
+        target = self
+        if Cn != self.topology.classes:
+            from .topology import glorot_uniform
+            dense2 = (glorot_uniform(np.random.default_rng(seed), (self.topology.hidden, Cn), self.topology.hidden, Cn), np.zeros(Cn, np.float32))
+            target = VTCNN2(Topology.vtcnn2(Cn), device=self.device_index, dtype=self.dtype, fp8_input_absmax=self.fp8_input_absmax,
+                            fp8_bf16_features=self.fp8_bf16_features, fp8_feature_absmax=self._fp8_feature_absmax, _lib_variant=self._lib_variant)
+            target.set_weights([conv1, conv2, dense1, dense2])
+        feat = self.head_features(X)
+        val = None
+        if validation_data is not None:
+            val = (self.head_features(validation_data[0]), validation_data[1])
+        tr = HeadTrainer(K, self.topology.hidden, Cn, [dense1, dense2], device=self.device_index, max_batch=int(batch_size), lr=lr, beta1=beta1,
+                         beta2=beta2, eps=eps, dropout=dropout, dropout_seed=dropout_seed, _lib_variant=self._lib_variant)
+        try:
+            def save(filepath):      # the whole model with the head as it is now; no optimiser state (save() of an unfitted model)
+                write_keras_h5(filepath, target.topology, [conv1, conv2] + tr.get_weights(), optimizer=None, adam={})
+            hist = tr.fit(feat, Y, batch_size=batch_size, epochs=epochs, validation_data=val, patience=patience, checkpoint=checkpoint,
+                          shuffle=shuffle, seed=seed, verbose=verbose, save=save, **kw)
+            head = tr.get_weights()
+        finally:
+            tr.close()
+        target._weights = [conv1, conv2] + head
+        target._release()                   # the inference engine re-packs the new weights on its next use
+        target.head_history = hist
+        return hist if target is self else target
+
     def save(self, filepath: str) -> None:
         """``model.save(filepath)``: Keras 2.4 full-model HDF5 (formats/h5mini.write_keras_h5); Adam's state is included when
         this model has been fitted."""
