@@ -46,7 +46,12 @@ Add --batched for a busy band: all boxes are then extracted in one launch and cl
 bit; frontend.extract, detect_iq(batched=True)) instead of a few launches and one synchronisation per box.  Add --refine to
 take each box's symbol rate and carrier from its spectral lines instead of its width and centroid (detect_iq(refine=True);
 with --batched all boxes' line spectra come from one frontend.line_spectra and one frontend.find_lines); two more columns, as
-with --scan --refine.
+with --scan --refine.  Add --floor cfar where the noise floor is neither flat nor still -- a coloured front-end, an AGC or gain
+step, a neighbour keying up: every cell is then held against an order statistic of the cells AROUND it (frontend.cfar_floor,
+2-D order-statistic CFAR on the device; --cfar TR,TB,GR,GB,RANK sets the training window, the guard and the rank) instead of one
+level per bin for the whole capture:
+
+    python examples/classify_capture.py capture.bin --format ci16 --detections --floor cfar --cfar 8,32,2,8,0.5
 
 A band with a channel raster -- PMR / LMR, GSM, FM broadcast, ISM sub-bands -- is split into all its M evenly spaced channels in
 one pass instead (frontend.channelize, a polyphase filter bank on the device; VTCNN2.predict_channels), one line per channel:
@@ -223,16 +228,22 @@ def synthetic_hopper(fmt="ci16", seed=1, pairs=1 << 19):
 
 
 def detections(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, level=7.8e-3, squelch=-60.0, batched=False, refine=False,
-               balance=False):
+               balance=False, floor="flat", cfar=None):
     """Print one line per detection of the capture (VTCNN2.detect_iq: boxes in time and frequency) and return the records: the
     box's span in input pairs, centre and width (Hz with rate, else cycles per sample), the peak over the threshold, the plan and
     the label.  batched: all boxes in one extraction launch and one forward (needs hop == 128); the same records.  refine: symbol
     rate and carrier from each box's spectral lines (detect_iq's refine=True), as two more columns -- the symbol rate ("-" where no
     line was found) and the refined centre.  balance: correct the receiver's DC offset and I/Q imbalance first (detect_iq's
-    balance=True)."""
+    balance=True).  floor: detect_iq's noise floor -- "flat", "per-bin" or "cfar", the local order-statistic floor per cell, with
+    cfar = (train_rows, train_bins, guard_rows, guard_bins, rank) or None for the defaults; the peak column is then dB above the
+    local floor's threshold."""
     more = dict(refine=True) if refine else {}
     if balance:
         more["balance"] = True
+    if floor != "flat":
+        more["floor"] = floor
+    if cfar is not None:
+        more["cfar"] = cfar
     found = model.detect_iq(iq[:iq.size // 2 * 2], fmt, nfft=nfft, threshold_db=threshold_db, hop=hop, level=level, squelch_dbfs=squelch,
                             batched=batched, **more)
     k, unit = (rate, "Hz") if rate else (1.0, "cyc/sample")
@@ -357,6 +368,11 @@ def main():
                          "time and frequency; uses --nfft and --threshold")
     ap.add_argument("--batched", action="store_true",
                     help="with --detections: extract all boxes in one launch and classify them in one forward (the same lines; needs --hop 128)")
+    ap.add_argument("--floor", choices=["flat", "per-bin", "cfar"], default="flat",
+                    help="with --detections: the noise floor -- one level for the band, every bin's median over time, or a local "
+                         "order-statistic floor per cell (follows a coloured front-end and a gain step)")
+    ap.add_argument("--cfar", default=None, metavar="TR,TB,GR,GB,RANK",
+                    help="with --floor cfar: training rows and bins, guard rows and bins, rank in [0, 1] (default 8,32,2,8,0.5)")
     ap.add_argument("--balance", action="store_true",
                     help="with --scan, --detections or --channels: remove the receiver's DC offset and I/Q imbalance, estimated from the "
                          "capture, first (an uncalibrated zero-IF receiver lists every strong emitter's mirror image as an emitter)")
@@ -370,7 +386,8 @@ def main():
         else:
             model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
         detections(model, iq, a.format, nfft=a.nfft, threshold_db=a.threshold, rate=a.rate if a.rate != 1.0 else None, hop=a.hop, level=a.level,
-                   squelch=a.squelch, batched=a.batched, refine=a.refine, balance=a.balance)
+                   squelch=a.squelch, batched=a.batched, refine=a.refine, balance=a.balance, floor=a.floor,
+                   cfar=None if a.cfar is None else tuple(float(v) for v in a.cfar.split(",")))
         return
     if a.channels:
         iq, a.format = load(a, lambda fmt: synthetic_raster(fmt, a.channels))

@@ -92,6 +92,8 @@ def main(argv=None):
     ap.add_argument("--net", choices=("cnnpy", "vtcnn2"), default="cnnpy", help="the classifier: cnn.py's small net (fit) or VT-CNN2 (fit_head)")
     ap.add_argument("--head-epochs", type=int, default=3, help="--net vtcnn2: epochs of the head fit (0: classify with the weights as they are)")
     ap.add_argument("--scan", action="store_true", help="score scan_iq's emitters (one record per emitter, no time axis) instead of detect_iq's")
+    ap.add_argument("--floor", choices=("flat", "per-bin", "cfar"), default="flat",
+                    help="detect_iq's noise floor: one level, every bin's median over time, or a local order-statistic floor per cell")
     args = ap.parse_args(argv)
     emitters = [parse_emitter(t) for t in args.emitter] or default_emitters()
     mods = tuple(dict.fromkeys(list(MODS) + [e["mod"] for e in emitters]))
@@ -103,7 +105,7 @@ def main(argv=None):
     if args.scan:
         records = [dict(r, first_pair=0, stop_pair=args.pairs) for r in model.scan_iq(iq, "ci16", nfft=NFFT, avg=AVG)]
     else:
-        records = model.detect_iq(iq, "ci16", nfft=NFFT, avg=AVG, batched=True)
+        records = model.detect_iq(iq, "ci16", nfft=NFFT, avg=AVG, floor=args.floor, batched=True)
     score = frontend.score_detections(records, truth, min_overlap=args.min_overlap, classes=len(mods))
     hit = dict(score["found"])
     print(f"{args.pairs} pairs, {len(scene.emitters)} emitters, {saturated} clamped components; {len(truth)} truth dwells, {len(records)} detections")

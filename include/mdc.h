@@ -61,6 +61,7 @@ extern "C" {
                                   mdc_iq_spectrum_quantiles (order statistics of a spectrogram along time, per bin);
                                   mdc_iq_spectrogram_components / mdc_iq_spectrogram_components_workspace, mdc_iq_component
                                   (connected components of a thresholded spectrogram: boxes in time and frequency);
+                                  mdc_iq_spectrogram_cfar (a local order-statistic noise floor per cell, and the ratio to it);
                                   mdc_iq_extract / mdc_iq_extract_plan / mdc_iq_extract_plan_bytes, mdc_iq_extract_job,
                                   mdc_iq_extract_filter (K stretches of a capture through mdc_iq_resample's chain in one launch);
                                   mdc_iq_line_spectra / mdc_iq_line_spectra_rows, mdc_iq_line_job (the line spectra of K stretches
@@ -760,6 +761,38 @@ MDC_API int64_t mdc_iq_spectrogram_components_workspace(int64_t rows, int nfft);
 MDC_API int mdc_iq_spectrogram_components(const float* power_dev, int64_t rows, int nfft, const float* thresh_dev, int reach_rows,
                                           int reach_bins, int32_t* labels_dev, mdc_iq_component* comps_dev, int64_t capacity,
                                           int64_t* count_dev, void* work_dev, void* hip_stream);
+
+/* ---- spectrogram CFAR: a local order-statistic noise floor for every cell, and the ratio to it (additive in ABI 5) ----------
+ * One threshold per bin for the whole capture follows neither a floor that moves in time (an AGC or gain step, a pulsed wideband
+ * interferer) nor, where it is every bin's median over time, a continuous emitter on a coloured front-end.  The textbook answer
+ * is a floor taken per CELL from the cells around it (2-D order-statistic CFAR): mdc_iq_spectrogram_cfar computes it for every
+ * cell in one call, and the cell's ratio to it, which mdc_iq_spectrogram_components takes in the spectrogram's place (with a
+ * threshold that is a plain factor).  The numpy restatement is tests/iq_cfar_ref.py.  Normatively, for power_dev = rows * nfft
+ * floats, rows contiguous, in the natural DFT order mdc_iq_spectrogram writes:
+ *   centred    column c = (k + nfft/2) mod nfft of natural bin k, mdc_iq_spectrogram_components' convention.  The band is NOT
+ *              circular: natural bins nfft/2 - 1 and nfft/2 are the two ends (c = nfft - 1 and 0).
+ *   training   the training set T of cell (r, c): all cells (r', c') of the spectrogram with |r' - r| <= train_rows and
+ *              |c' - c| <= train_bins, minus those with |r' - r| <= guard_rows and |c' - c| <= guard_bins (the cell itself is
+ *              always in the guard).  At the borders the window is cut off -- not wrapped, not padded --, so n = |T| varies; it
+ *              is an integer function of (r, c, rows, nfft) alone.
+ *   floor      the n 32-bit patterns of T are ordered ascending AS UNSIGNED INTEGERS, mdc_iq_spectrum_quantiles' order (the
+ *              numeric order for everything a spectrogram produces; sign-bit and NaN patterns are ordered by the same rule, which
+ *              is defined and memory-safe, if of no numeric use).  floor_dev[r*nfft + k] is the pattern at position
+ *              ((n - 1) * rank_permille) / 1000 (0-based; the integer floor, taken in 64 bits): rank_permille 500 is the lower
+ *              median, 0 the minimum, 1000 the maximum.  n == 0 gives +Inf.  Nothing is interpolated: the floor is an element of
+ *              the spectrogram, the same bits on every run and on every machine.
+ *   ratio      ratio_dev[r*nfft + k] = power_dev[r*nfft + k] / floor, ONE correctly rounded IEEE float32 division (no
+ *              reciprocal, no fast-math).  0/0 and Inf/Inf are NaN, which mdc_iq_spectrogram_components reads as off; x/0, x > 0,
+ *              is +Inf, which it reads as on; x / +Inf is 0: off.  Every NaN result is stored as the pattern 0x7FC00000 (IEEE
+ *              leaves a NaN's sign and payload to the machine), so the ratio too is the same bits everywhere.
+ * rows >= 1 and rows * nfft <= 2^31 - 1; nfft: a power of two in 64..4096; 0 <= guard_rows <= train_rows <= 16;
+ * 0 <= guard_bins <= train_bins <= 128; (train_rows, train_bins) != (guard_rows, guard_bins); 0 <= rank_permille <= 1000.
+ * floor_dev and ratio_dev hold rows * nfft floats each; either may be NULL (that output is not written), and both NULL is MDC_OK
+ * with nothing launched (power_dev may then be NULL too).  Neither may overlap power_dev; all three are 4-byte aligned.  Every
+ * argument error is MDC_EINVAL before any device call.  The call only enqueues on hip_stream (no synchronisation, no allocation,
+ * no copy, no workspace: capturable in a hipGraph) and runs on the current device; no work-group waits for another. */
+MDC_API int mdc_iq_spectrogram_cfar(const float* power_dev, int64_t rows, int nfft, int train_rows, int train_bins, int guard_rows,
+                                    int guard_bins, int rank_permille, float* floor_dev, float* ratio_dev, void* hip_stream);
 
 /* ---- channelizer: all M evenly spaced channels of a capture in one pass (additive in ABI 5) ---------------------------------
  * A band with a channel raster (PMR / LMR, GSM, FM broadcast, ISM sub-bands) wants every channel at once.  M calls of mdc_iq_ddc

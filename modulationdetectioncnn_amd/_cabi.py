@@ -43,6 +43,7 @@ EXPORTS = [
     "mdc_iq_channelizer", "mdc_iq_channelizer_out_count",
     "mdc_iq_spectrum_quantiles",
     "mdc_iq_spectrogram_components", "mdc_iq_spectrogram_components_workspace",
+    "mdc_iq_spectrogram_cfar",
     "mdc_iq_line_spectra", "mdc_iq_line_spectra_rows", "mdc_iq_find_lines",
     "mdc_iq_balance", "mdc_iq_balance_stats", "mdc_iq_balance_blocks",
     "mdc_iq_cf32_histogram", "mdc_iq_cf32_quantize",
@@ -151,6 +152,10 @@ COMPONENTS_MAX_REACH, COMPONENTS_MAX_CELLS = 4, 2 ** 31 - 1
 COMPONENTS_TILE_ROWS, COMPONENTS_TILE_COLS, COMPONENTS_CHUNK = 32, 64, 1024
 IQ_COMPONENT = np.dtype([("row_first", np.int32), ("row_stop", np.int32), ("bin_first", np.int32), ("bin_stop", np.int32),
                          ("cells", np.int32), ("peak", np.float32), ("peak_row", np.int32), ("peak_bin", np.int32)])
+# mdc_iq_spectrogram_cfar: limits of include/mdc.h, and the kernel's tile (csrc/iq_cfar.hip: kCfarTileRows x kCfarTileCols cells per
+# work-group, CFAR_LANE_CELLS consecutive rows of a column per lane)
+CFAR_MAX_TRAIN_ROWS, CFAR_MAX_TRAIN_BINS = 16, 128
+CFAR_TILE_ROWS, CFAR_TILE_COLS, CFAR_LANE_CELLS = 16, 64, 4
 # mdc_iq_channelizer: limits of include/mdc.h (channels a power of two in MIN..MAX, decimate <= channels, ntaps <= 16 per channel,
 # per-residue sum |h| <= 65535), and the kernel's tiling (csrc/iq_channelizer.hip: kChanGridCap, chan_tile_steps): a work-group
 # owns channelizer_tile_steps(channels) consecutive output steps, at most CHANNELIZER_GRID_CAP work-groups; more tiles are
@@ -250,6 +255,7 @@ def lib(variant: str = "product") -> C.CDLL:
                        ("mdc_iq_channelizer", [vp, i32, i64, i64, i32, i32, vp, i32, i32, vp, i64, vp]),
                        ("mdc_iq_spectrum_quantiles", [vp, i64, i32, vp, i32, vp, vp]),
                        ("mdc_iq_spectrogram_components", [vp, i64, i32, vp, i32, i32, vp, vp, i64, vp, vp, vp]),
+                       ("mdc_iq_spectrogram_cfar", [vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
                        ("mdc_iq_line_spectra", [vp, i32, i64, vp, vp, i64, vp, i32, i32, i64, i32, vp, C.c_float, vp, i64, vp, vp]),
                        ("mdc_iq_find_lines", [vp, i64, i32, vp, vp, vp, vp]),
                        ("mdc_iq_balance_stats", [vp, i32, i64, i64, vp, i64, vp]),

@@ -194,7 +194,7 @@ def scan_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_d
 def detect_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold_db: float = 6.0, floor: str = "flat", reach_rows: int = 2,
               reach_bins: int = 3, min_rows: int = 3, min_bins: int = 3, hop: int = 128, level: float = 7.8e-3,
               squelch_dbfs: Optional[float] = None, dc_guard: int = 1, batched: bool = False, refine: bool = False, min_line_db: float = 8.0,
-              line_nfft: int = 1024, line_avg: int = 8, balance=False):
+              line_nfft: int = 1024, line_avg: int = 8, balance=False, cfar=None):
     """A wideband capture in, "what transmitted when, where, and what modulation" out: the scan in two dimensions, for
     frequency hoppers, emitters that share bins at different times and single packets, which scan_iq's one-dimensional
     searches miss or mangle.  The capture's spectrogram (frontend.spectrogram, as scan_iq builds it: nfft bins, segments nfft //
@@ -234,19 +234,40 @@ def detect_iq(self, iq, sample_format, nfft: int = 1024, avg: int = 8, threshold
     refined shifts and ratios: the same spectra from the same entries, so both forms agree bit for bit.  refine=False is the
     plan alone, and its record has none of the five keys.
     balance: as scan_iq's -- True, or a coefficients tuple, corrects the capture's DC offset and I/Q imbalance first
-    (frontend.balance) and the records gain image_rejection_db; False (the default) changes nothing and adds no key."""
+    (frontend.balance) and the records gain image_rejection_db; False (the default) changes nothing and adds no key.
+    floor="cfar" detects against a LOCAL noise floor instead of one number per bin for the whole capture: ratio =
+    frontend.cfar_floor(spec, *cfar, return_ratio=True)[1] divides every cell by an order statistic of the cells around it
+    (mdc_iq_spectrogram_cfar, include/mdc.h), thresh = frontend.cfar_threshold(nfft, threshold_db, dc_guard) is the plain factor
+    10^(threshold_db / 10) with the DC guard, and found = frontend.find_detections(ratio, thresh, ...); everything behind
+    `found` is the code above, loop or batched, with or without refine.  It follows a coloured front-end AND a floor that moves
+    in time (a gain step, a pulsed wideband interferer), and a continuous emitter does not become its own floor as under
+    "per-bin".  cfar: the five parameters (train_rows, train_bins, guard_rows, guard_bins, rank) as a tuple or a dict with
+    those keys (missing ones take the defaults); None: frontend.cfar_floor's defaults (8, 32, 2, 8, 0.5).  The record changes
+    its meaning in three places: peak_db is dB above the LOCAL floor at the peak, snr_db = peak_db - threshold_db, and centre is
+    the centroid of the ratio's excess over the factor.  The method's known limit is self-masking: an emitter that fills more
+    than the share 1 - rank of its own training window lifts its own floor -- at the defaults one wider than about 40 bins
+    that is on in every row of the window; such an emitter needs a wider train_bins, or "flat".  cfar= with another floor is a
+    ValueError; "flat" and "per-bin" run exactly as before."""
     import torch
     from . import frontend as F
     fmt = F.sample_format_id(sample_format)
     if batched and hop != 128:
         raise ValueError(f"batched=True needs hop == 128 (got {hop}): windows at another hop would straddle two detections")
+    if cfar is not None and floor != "cfar":
+        raise ValueError(f"cfar= goes with floor='cfar' (got floor={floor!r})")
+    cfar_args = F.cfar_parameters(cfar) if floor == "cfar" else None
     as_numpy = not isinstance(iq, torch.Tensor)
     dev, fmt, balanced = _capture(iq, fmt, balance, f"cuda:{self.device_index}")
     spec = F.spectrogram(dev, fmt, nfft=nfft, avg=avg)
     if spec.shape[0] == 0:
         raise ValueError(f"the capture is too short for one row of {avg} segments of {nfft} pairs")
-    thresh = F.detection_threshold(spec, threshold_db, dc_guard, floor)
-    found = F.find_detections(spec, thresh, reach_rows, reach_bins, min_rows, min_bins, avg=avg)
+    if floor == "cfar":
+        ratio = F.cfar_floor(spec, *cfar_args, return_ratio=True)[1]
+        thresh = F.cfar_threshold(nfft, threshold_db, dc_guard, device=ratio.device)
+        found = F.find_detections(ratio, thresh, reach_rows, reach_bins, min_rows, min_bins, avg=avg)
+    else:
+        thresh = F.detection_threshold(spec, threshold_db, dc_guard, floor)
+        found = F.find_detections(spec, thresh, reach_rows, reach_bins, min_rows, min_bins, avg=avg)
     if batched:
         plans, extras = [p[:3] for p in F.channel_plans([(d.centre, d.bandwidth) for d in found])], None
         if refine and found:

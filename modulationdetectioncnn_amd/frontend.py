@@ -1599,6 +1599,90 @@ def detection_threshold(spec, threshold_db: float = 6.0, dc_guard: int = 1, floo
     return thresh
 
 
+# ---- a local noise floor (mdc_iq_spectrogram_cfar): 2-D order-statistic CFAR, for a floor that moves in time and in frequency ------
+CFAR_DEFAULTS = dict(train_rows=8, train_bins=32, guard_rows=2, guard_bins=8, rank=0.5)
+
+
+def cfar_parameters(cfar=None):
+    """detect_iq's cfar= as the tuple (train_rows, train_bins, guard_rows, guard_bins, rank): None gives CFAR_DEFAULTS, a dict
+    overrides them by key (ValueError for an unknown key), a sequence must hold all five in that order."""
+    if cfar is None:
+        cfar = {}
+    if isinstance(cfar, dict):
+        unknown = sorted(set(cfar) - set(CFAR_DEFAULTS))
+        if unknown:
+            raise ValueError(f"cfar: unknown key(s) {unknown}; the keys are {list(CFAR_DEFAULTS)}")
+        values = [cfar.get(k, v) for k, v in CFAR_DEFAULTS.items()]
+    else:
+        values = list(cfar)
+        if len(values) != 5:
+            raise ValueError(f"cfar must hold (train_rows, train_bins, guard_rows, guard_bins, rank) (got {len(values)} values)")
+    return int(values[0]), int(values[1]), int(values[2]), int(values[3]), float(values[4])
+
+
+def cfar_floor(spec, train_rows: int = 8, train_bins: int = 32, guard_rows: int = 2, guard_bins: int = 8, rank: float = 0.5,
+               return_ratio: bool = False, device=None):
+    """A local noise floor for every cell of a spectrogram, on the device (mdc_iq_spectrogram_cfar, include/mdc.h: 2-D
+    order-statistic CFAR).  spec: the (rows, nfft) float32 tensor of spectrogram (a host tensor or array is moved to the device).
+    The training set of a cell is the rectangle of +-train_rows rows and +-train_bins CENTRED columns around it, cut off at the
+    spectrogram's borders (the band is not circular), minus the guard rectangle of +-guard_rows and +-guard_bins, which holds
+    the cell itself and keeps an emitter's own skirt out of its floor; the floor is the training set's element at position
+    floor((n - 1) * rank_permille / 1000) of its ascending order, rank_permille = round(1000 * rank) -- rank 0.5 the lower
+    median --, an element of the spectrogram, never an interpolation; +inf where the training set is empty.  Returns the (rows,
+    nfft) float32 floor in natural positions, or with return_ratio (floor, ratio), ratio = spec / floor in one float32 division (0/0 and inf/inf: NaN, stored as
+    0x7FC00000, which find_detections reads as off; x/0: +inf, on; x/inf: 0, off):
+    the spectrogram in units of its local floor, which find_detections takes with cfar_threshold's plain factor.  Known limit
+    (self-masking): an emitter that fills more than the share 1 - rank of its own training window lifts its own floor; at the
+    defaults that is one wider than about 40 bins and on in every row of the window.  ValueError / TypeError -- before anything
+    touches a device -- for a shape that is not (rows, nfft) with nfft a power of two in 64..4096, no rows, more than 2^31 - 1
+    cells, parameters outside 0 <= guard_rows <= train_rows <= 16 and 0 <= guard_bins <= train_bins <= 128, a guard that is the
+    whole window, or a rank outside [0, 1].  Enqueues on torch's current stream without synchronising."""
+    import torch
+    rows, nfft = _check_spectrogram_shape(spec)
+    if rows < 1:
+        raise ValueError("the spectrogram has no rows")
+    if rows * nfft > _cabi.COMPONENTS_MAX_CELLS:
+        raise ValueError(f"at most {_cabi.COMPONENTS_MAX_CELLS} cells (got {rows} x {nfft})")
+    tr, tb, gr, gb = int(train_rows), int(train_bins), int(guard_rows), int(guard_bins)
+    if not (0 <= gr <= tr <= _cabi.CFAR_MAX_TRAIN_ROWS and 0 <= gb <= tb <= _cabi.CFAR_MAX_TRAIN_BINS):
+        raise ValueError(f"0 <= guard_rows <= train_rows <= {_cabi.CFAR_MAX_TRAIN_ROWS} and 0 <= guard_bins <= train_bins <= "
+                         f"{_cabi.CFAR_MAX_TRAIN_BINS} (got train ({train_rows!r}, {train_bins!r}), guard ({guard_rows!r}, {guard_bins!r}))")
+    if (tr, tb) == (gr, gb):
+        raise ValueError(f"the guard ({gr}, {gb}) is the whole training window: no training cells")
+    if not 0.0 <= float(rank) <= 1.0:      # (a NaN fails both comparisons)
+        raise ValueError(f"rank must lie in [0, 1] (got {rank!r})")
+    permille = int(round(1000.0 * float(rank)))
+    t = _float32_tensor(spec, "spec")
+    if not t.is_cuda:
+        t = t.to(device if device is not None else "cuda:0")
+    t = t.contiguous()
+    floor = torch.empty((rows, nfft), dtype=torch.float32, device=t.device)
+    ratio = torch.empty((rows, nfft), dtype=torch.float32, device=t.device) if return_ratio else None
+    with torch.cuda.device(t.device):
+        _cabi.check(_cabi.lib().mdc_iq_spectrogram_cfar(t.data_ptr(), rows, nfft, tr, tb, gr, gb, permille, floor.data_ptr(),
+                                                        ratio.data_ptr() if return_ratio else None,
+                                                        torch.cuda.current_stream(t.device).cuda_stream))
+    return (floor, ratio) if return_ratio else floor
+
+
+def cfar_threshold(nfft: int, threshold_db: float = 6.0, dc_guard: int = 1, device=None):
+    """The threshold that goes with cfar_floor's ratio: an (nfft,) float32 device tensor in natural DFT order that holds
+    10^(threshold_db / 10), detection_threshold's float32 factor, and +inf in the bins within dc_guard of bin 0 (both sides;
+    dc_guard < 0: none), detection_threshold's rule."""
+    import torch
+    nfft = int(nfft)
+    if not (_cabi.SPECTROGRAM_MIN_NFFT <= nfft <= _cabi.SPECTROGRAM_MAX_NFFT and nfft & (nfft - 1) == 0):
+        raise ValueError(f"nfft must be a power of two in {_cabi.SPECTROGRAM_MIN_NFFT}..{_cabi.SPECTROGRAM_MAX_NFFT} (got {nfft})")
+    factor = float(np.float32(10.0 ** (float(threshold_db) / 10.0)))
+    if not np.isfinite(factor):
+        raise ValueError(f"threshold_db must be finite (got {threshold_db!r})")
+    dev = device if device is not None else "cuda:0"
+    thresh = torch.full((nfft,), factor, dtype=torch.float32, device=dev)
+    if int(dc_guard) >= 0:
+        thresh[torch.arange(-int(dc_guard), int(dc_guard) + 1, device=dev) % nfft] = float("inf")
+    return thresh
+
+
 def detections_from_components(spec, thresh, records, count: int, min_rows: int = 3, min_bins: int = 3, nfft_hop=None, avg: int = 1):
     """The host half of find_detections: spectrogram_components' records -> a list of Detection(first_row, stop_row, first_bin,
     stop_bin, cells, centre, bandwidth, peak_db, snr_db, first_pair, stop_pair), ordered by (first_pair, centre); float64.
