@@ -18,27 +18,22 @@
 //   6 head_step_kernel   apply != 0: iterations += 1, after launch 5 has read it everywhere.
 // Stores are vector stores; no work-group waits for another or signals one; every register array is indexed by unrolled constants.
 #include "train_common.h"
+#include "train_host.h"             // the parameter bank and the entry bodies shared with train.hip
 
 #include <cmath>
 #include <cstddef>
-#include <cstring>
 #include <new>
 
-struct mdc_head_trainer {
-    int K = 0, H = 0, C = 0, BN = 32, device = 0;
+struct mdc_head_trainer : mdc::ParamBank {      // two layers: (W1, b1), (W2, b2); d_state: HeadState
+    int K = 0, H = 0, C = 0, BN = 32;
     int64_t max_batch = 0;
     int dw1_slices = 0;          // partial dW1 tensors d_dw1part holds
     size_t z1_floats = 0;        // floats d_z1part holds
-    size_t off_k[2]{}, off_b[2]{}, nk[2]{}, nb[2]{}, P = 0;
-    bool have[2]{};
-    float lr = 1e-3f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-7f;
     float rate0 = 0.f, rate1 = 0.f;
     unsigned drop_seed = 0;
-    float *d_params = nullptr, *d_m = nullptr, *d_v = nullptr, *d_grad = nullptr;
     float *d_z1part = nullptr, *d_dw1part = nullptr, *d_small = nullptr;      // partial sums of launches 1, 3 and 4
     float *d_h = nullptr, *d_dz1 = nullptr, *d_dz2 = nullptr, *d_loss = nullptr;      // per batch position
     int* d_hit = nullptr;
-    void* d_state = nullptr;
 };
 
 namespace mdc {
@@ -63,6 +58,7 @@ struct HeadState {
     long long eval_correct;
     unsigned bad_indices;      // batch positions skipped because their index lay outside [0, n_rows)
 };
+static_assert(offsetof(HeadState, iterations) == 0, "bank_set_iterations writes the record's first field");
 
 struct HeadPlan { int tiles_m, slices, chunks_per, slices2, rows_per2, small; };
 
@@ -528,42 +524,20 @@ int head_launch(mdc_head_trainer* t, const float* f, const float* y, int64_t n_r
     return head_launch_bn<32>(t, f, y, n_rows, order, first, (int)count, mode, s);
 }
 
-int head_check_batch(const char* what, mdc_head_trainer* t, const float* f, const float* y, int64_t n_rows, const int32_t* order, int64_t first, int64_t count) {
-    if (!t) { set_error("%s: null trainer", what); return MDC_EINVAL; }
-    for (int l = 0; l < 2; ++l)
-        if (!t->have[l]) { set_error("%s: layer %d has no weights (mdc_head_trainer_set_tensor)", what, l); return MDC_ESTATE; }
-    if (first < 0 || count < 0) { set_error("%s: negative range", what); return MDC_EINVAL; }
-    if (count > t->max_batch) { set_error("%s: count %lld exceeds the trainer's max_batch %lld", what, (long long)count, (long long)t->max_batch); return MDC_EINVAL; }
-    if (count > 0 && (!f || !y)) { set_error("%s: null features or targets", what); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(f) & 15) != 0) { set_error("%s: features must be 16-byte aligned", what); return MDC_EINVAL; }
-    if (n_rows < 0) { set_error("%s: negative n_rows", what); return MDC_EINVAL; }
-    if (first > ((int64_t)1 << 40)) { set_error("%s: first out of range", what); return MDC_EINVAL; }
-    // without a shuffle the positions ARE the rows: checked here; with one, its VALUES are checked on the device (frame_index)
-    if (!order && first + count > n_rows) {
-        set_error("%s: rows [%lld, %lld) outside the %lld of the buffers", what, (long long)first, (long long)(first + count), (long long)n_rows);
-        return MDC_EINVAL;
-    }
-    return MDC_OK;
-}
-
-float* head_vec(mdc_head_trainer* t, int which) {
-    switch (which) {
-        case MDC_TRAIN_WEIGHTS: return t->d_params;
-        case MDC_TRAIN_ADAM_M:  return t->d_m;
-        case MDC_TRAIN_ADAM_V:  return t->d_v;
-        case MDC_TRAIN_GRADIENT: return t->d_grad;
-        default: return nullptr;
-    }
-}
-
-int head_tensor_args(const char* what, mdc_head_trainer* t, int layer, const void* k, size_t nk, const void* b, size_t nb) {
-    if (!t || !k || !b) { set_error("%s: null argument", what); return MDC_EINVAL; }
-    if (layer < 0 || layer > 1) { set_error("%s: layer %d out of range 0..1", what, layer); return MDC_EINVAL; }
-    if (nk != t->nk[layer] || nb != t->nb[layer]) {
-        set_error("%s: layer %d holds kernel %zu / bias %zu elements, got %zu / %zu", what, layer, t->nk[layer], t->nb[layer], nk, nb);
-        return MDC_EINVAL;
-    }
-    return MDC_OK;
+// mdc_head_train_batch (mode 1: gradient only, 2: gradient + Adam) and mdc_head_trainer_evaluate (mode 0) behind their names
+int batch_entry(const char* who, mdc_head_trainer* t, const float* f, const float* y, int64_t n_rows, const int32_t* order, int64_t first, int64_t count,
+                int mode, void* hip_stream) {
+    return guarded(who, [&]() -> int {
+        int rc = bank_check_batch(who, t, "features", "rows", f, y, n_rows, order, first, count);
+        if (rc != MDC_OK) return rc;
+        // the head's own bounds: all scratch was allocated for max_batch rows
+        if (count > t->max_batch) { set_error("%s: count %lld exceeds the trainer's max_batch %lld", who, (long long)count, (long long)t->max_batch); return MDC_EINVAL; }
+        if (first > ((int64_t)1 << 40)) { set_error("%s: first out of range", who); return MDC_EINVAL; }
+        if (count == 0) return MDC_OK;
+        DeviceScope dev(t->device);
+        if (!device_selected(who, dev)) return MDC_EIO;
+        return head_launch(t, f, y, n_rows, order, first, count, mode, static_cast<hipStream_t>(hip_stream));
+    });
 }
 
 }  // namespace
@@ -582,26 +556,18 @@ int mdc_head_trainer_create(int features, int hidden, int classes, int64_t max_b
         if (hidden < 32 || hidden > kHeadHmax || hidden % 32 != 0) { set_error("mdc_head_trainer_create: hidden must be a multiple of 32 in 32..256 (got %d)", hidden); return MDC_EINVAL; }
         if (classes < 2 || classes > kHeadCmax) { set_error("mdc_head_trainer_create: classes must lie in 2..16 (got %d)", classes); return MDC_EINVAL; }
         if (max_batch < 1 || max_batch > 65536) { set_error("mdc_head_trainer_create: max_batch must lie in 1..65536 (got %lld)", (long long)max_batch); return MDC_EINVAL; }
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MDC_ENODEV; }
-        if (device < 0 || device >= ndev) { set_error("device %d out of range (have %d)", device, ndev); return MDC_ENODEV; }
-        hipDeviceProp_t prop;
-        MDC_HIP(hipGetDeviceProperties(&prop, device));
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-            set_error("device %d is %s; libmdc.so carries gfx950 (MI355X) code only", device, prop.gcnArchName);
-            return MDC_ENODEV;
-        }
+        int rc = check_device(device);      // (behind the argument checks: a bad shape is MDC_EINVAL on a machine without a GPU too)
+        if (rc != MDC_OK) return rc;
         mdc_head_trainer* t = new (std::nothrow) mdc_head_trainer();
         if (!t) { set_error("out of host memory"); return MDC_ENOMEM; }
         t->K = features; t->H = hidden; t->C = classes; t->max_batch = max_batch; t->device = device;
         t->BN = hidden % 128 == 0 ? 128 : (hidden % 64 == 0 ? 64 : 32);
+        t->nlayers = 2;
         t->nk[0] = (size_t)features * hidden;  t->nb[0] = hidden;
         t->nk[1] = (size_t)hidden * classes;   t->nb[1] = classes;
-        size_t off = 0;
-        for (int l = 0; l < 2; ++l) { t->off_k[l] = off; off += t->nk[l]; t->off_b[l] = off; off += t->nb[l]; }
-        t->P = off;
+        t->layout();
         DeviceScope dev(device);
-        if (!dev.ok) { set_error("mdc_head_trainer_create: cannot select device %d", device); delete t; return MDC_EIO; }
+        if (!device_selected("mdc_head_trainer_create", dev)) { delete t; return MDC_EIO; }
         // scratch for the largest batch: launch 1 writes slices x tiles x (128 x BN) floats, and head_plan keeps slices x tiles at or
         // under max(kHeadTarget, tiles).  Launch 3 writes slices2 partial dW1, and slices2 is NOT monotone in count (96 rows are
         // three one-stage slices, 128 rows two two-stage ones): its bound over every count <= max_batch is the cap or the stages
@@ -612,22 +578,18 @@ int mdc_head_trainer_create(int features, int hidden, int classes, int64_t max_b
         const size_t tiles = (size_t)pm.tiles_m * (hidden / t->BN);
         const size_t z1f = (tiles > (size_t)kHeadTarget ? tiles : (size_t)kHeadTarget) * kHeadBM * t->BN;
         t->z1_floats = z1f;
-        const size_t pb = t->P * sizeof(float), mb = (size_t)max_batch;
+        const size_t mb = (size_t)max_batch;
         auto fail = [&](int code) { mdc_head_trainer_destroy(t); return code; };
-        if (hipMalloc(&t->d_params, pb) != hipSuccess || hipMalloc(&t->d_m, pb) != hipSuccess || hipMalloc(&t->d_v, pb) != hipSuccess ||
-            hipMalloc(&t->d_grad, pb) != hipSuccess || hipMalloc(&t->d_z1part, z1f * sizeof(float)) != hipSuccess ||
+        rc = t->alloc("mdc_head_trainer_create", sizeof(HeadState));
+        if (rc != MDC_OK) return fail(rc);
+        if (hipMalloc(&t->d_z1part, z1f * sizeof(float)) != hipSuccess ||
             hipMalloc(&t->d_dw1part, (size_t)t->dw1_slices * t->nk[0] * sizeof(float)) != hipSuccess ||
             hipMalloc(&t->d_small, (size_t)kSmallSlices * kSmallStride * sizeof(float)) != hipSuccess ||
             hipMalloc(&t->d_h, mb * hidden * sizeof(float)) != hipSuccess || hipMalloc(&t->d_dz1, mb * hidden * sizeof(float)) != hipSuccess ||
             hipMalloc(&t->d_dz2, mb * kHeadCmax * sizeof(float)) != hipSuccess || hipMalloc(&t->d_loss, mb * sizeof(float)) != hipSuccess ||
-            hipMalloc(&t->d_hit, mb * sizeof(int)) != hipSuccess || hipMalloc(&t->d_state, sizeof(HeadState)) != hipSuccess) {
+            hipMalloc(&t->d_hit, mb * sizeof(int)) != hipSuccess) {
             set_error("mdc_head_trainer_create: out of device memory");
             return fail(MDC_ENOMEM);
-        }
-        if (hipMemset(t->d_params, 0, pb) != hipSuccess || hipMemset(t->d_m, 0, pb) != hipSuccess || hipMemset(t->d_v, 0, pb) != hipSuccess ||
-            hipMemset(t->d_grad, 0, pb) != hipSuccess || hipMemset(t->d_state, 0, sizeof(HeadState)) != hipSuccess) {
-            set_error("mdc_head_trainer_create: hipMemset failed");
-            return fail(MDC_EIO);
         }
         *out = t;
         return MDC_OK;
@@ -635,13 +597,7 @@ int mdc_head_trainer_create(int features, int hidden, int classes, int64_t max_b
 }
 
 int mdc_head_trainer_set_adam(mdc_head_trainer* t, float lr, float beta1, float beta2, float eps) {
-    if (!t) { set_error("null trainer"); return MDC_EINVAL; }
-    if (!(lr > 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f)) {
-        set_error("mdc_head_trainer_set_adam: need lr > 0, 0 <= beta < 1, eps >= 0");
-        return MDC_EINVAL;
-    }
-    t->lr = lr; t->beta1 = beta1; t->beta2 = beta2; t->eps = eps;
-    return MDC_OK;
+    return bank_set_adam("mdc_head_trainer_set_adam", t, lr, beta1, beta2, eps);
 }
 
 int mdc_head_trainer_set_dropout(mdc_head_trainer* t, float rate_features, float rate_hidden, uint32_t seed) {
@@ -657,97 +613,45 @@ int mdc_head_trainer_set_dropout(mdc_head_trainer* t, float rate_features, float
 int mdc_head_trainer_set_tensor(mdc_head_trainer* t, int which, int layer, const float* kernel_host, size_t kernel_elems, const float* bias_host,
                                 size_t bias_elems, void* hip_stream) {
     return guarded("mdc_head_trainer_set_tensor", [&]() -> int {
-        int rc = head_tensor_args("mdc_head_trainer_set_tensor", t, layer, kernel_host, kernel_elems, bias_host, bias_elems);
-        if (rc != MDC_OK) return rc;
-        float* vec = head_vec(t, which);
-        if (!vec || which == MDC_TRAIN_GRADIENT) { set_error("mdc_head_trainer_set_tensor: `which` must be MDC_TRAIN_WEIGHTS, _ADAM_M or _ADAM_V"); return MDC_EINVAL; }
-        DeviceScope dev(t->device);
-        if (!dev.ok) { set_error("mdc_head_trainer_set_tensor: cannot select device %d", t->device); return MDC_EIO; }
-        hipStream_t s = static_cast<hipStream_t>(hip_stream);
-        MDC_HIP(hipMemcpyAsync(vec + t->off_k[layer], kernel_host, kernel_elems * sizeof(float), hipMemcpyHostToDevice, s));
-        MDC_HIP(hipMemcpyAsync(vec + t->off_b[layer], bias_host, bias_elems * sizeof(float), hipMemcpyHostToDevice, s));
-        MDC_HIP(hipStreamSynchronize(s));      // the host buffers are the caller's again on return
-        if (which == MDC_TRAIN_WEIGHTS) t->have[layer] = true;
-        return MDC_OK;
+        return bank_set_tensor("mdc_head_trainer_set_tensor", t, which, layer, kernel_host, kernel_elems, bias_host, bias_elems, static_cast<hipStream_t>(hip_stream));
     });
 }
 
 int mdc_head_trainer_get_tensor(mdc_head_trainer* t, int which, int layer, float* kernel_host, size_t kernel_elems, float* bias_host, size_t bias_elems,
                                 void* hip_stream) {
     return guarded("mdc_head_trainer_get_tensor", [&]() -> int {
-        int rc = head_tensor_args("mdc_head_trainer_get_tensor", t, layer, kernel_host, kernel_elems, bias_host, bias_elems);
-        if (rc != MDC_OK) return rc;
-        float* vec = head_vec(t, which);
-        if (!vec) { set_error("mdc_head_trainer_get_tensor: unknown tensor kind %d", which); return MDC_EINVAL; }
-        DeviceScope dev(t->device);
-        if (!dev.ok) { set_error("mdc_head_trainer_get_tensor: cannot select device %d", t->device); return MDC_EIO; }
-        hipStream_t s = static_cast<hipStream_t>(hip_stream);
-        MDC_HIP(hipMemcpyAsync(kernel_host, vec + t->off_k[layer], kernel_elems * sizeof(float), hipMemcpyDeviceToHost, s));
-        MDC_HIP(hipMemcpyAsync(bias_host, vec + t->off_b[layer], bias_elems * sizeof(float), hipMemcpyDeviceToHost, s));
-        MDC_HIP(hipStreamSynchronize(s));
-        return MDC_OK;
+        return bank_get_tensor("mdc_head_trainer_get_tensor", t, which, layer, kernel_host, kernel_elems, bias_host, bias_elems, static_cast<hipStream_t>(hip_stream));
     });
 }
 
 int mdc_head_trainer_set_iterations(mdc_head_trainer* t, int64_t iterations, void* hip_stream) {
     return guarded("mdc_head_trainer_set_iterations", [&]() -> int {
-        if (!t || iterations < 0) { set_error("mdc_head_trainer_set_iterations: bad argument"); return MDC_EINVAL; }
-        DeviceScope dev(t->device);
-        if (!dev.ok) { set_error("mdc_head_trainer_set_iterations: cannot select device %d", t->device); return MDC_EIO; }
-        hipStream_t s = static_cast<hipStream_t>(hip_stream);
-        long long v = iterations;
-        MDC_HIP(hipMemcpyAsync(&static_cast<HeadState*>(t->d_state)->iterations, &v, sizeof(v), hipMemcpyHostToDevice, s));
-        MDC_HIP(hipStreamSynchronize(s));
-        return MDC_OK;
+        return bank_set_iterations("mdc_head_trainer_set_iterations", t, iterations, static_cast<hipStream_t>(hip_stream));
     });
 }
 
 int mdc_head_train_batch(mdc_head_trainer* t, const float* feat_dev, const float* y_dev, int64_t n_rows, const int32_t* order_dev, int64_t first,
                          int64_t count, int apply, void* hip_stream) {
-    return guarded("mdc_head_train_batch", [&]() -> int {
-        int rc = head_check_batch("mdc_head_train_batch", t, feat_dev, y_dev, n_rows, order_dev, first, count);
-        if (rc != MDC_OK) return rc;
-        if (count == 0) return MDC_OK;
-        DeviceScope dev(t->device);
-        if (!dev.ok) { set_error("mdc_head_train_batch: cannot select device %d", t->device); return MDC_EIO; }
-        return head_launch(t, feat_dev, y_dev, n_rows, order_dev, first, count, apply ? 2 : 1, static_cast<hipStream_t>(hip_stream));
-    });
+    return batch_entry("mdc_head_train_batch", t, feat_dev, y_dev, n_rows, order_dev, first, count, apply ? 2 : 1, hip_stream);
 }
 
 int mdc_head_trainer_evaluate(mdc_head_trainer* t, const float* feat_dev, const float* y_dev, int64_t n_rows, const int32_t* order_dev, int64_t first,
                               int64_t count, void* hip_stream) {
-    return guarded("mdc_head_trainer_evaluate", [&]() -> int {
-        int rc = head_check_batch("mdc_head_trainer_evaluate", t, feat_dev, y_dev, n_rows, order_dev, first, count);
-        if (rc != MDC_OK) return rc;
-        if (count == 0) return MDC_OK;
-        DeviceScope dev(t->device);
-        if (!dev.ok) { set_error("mdc_head_trainer_evaluate: cannot select device %d", t->device); return MDC_EIO; }
-        return head_launch(t, feat_dev, y_dev, n_rows, order_dev, first, count, 0, static_cast<hipStream_t>(hip_stream));
-    });
+    return batch_entry("mdc_head_trainer_evaluate", t, feat_dev, y_dev, n_rows, order_dev, first, count, 0, hip_stream);
 }
 
 int mdc_head_trainer_read(mdc_head_trainer* t, int reset, double* train_loss_sum, int64_t* train_rows, double* eval_loss_sum, int64_t* eval_rows,
                           int64_t* eval_correct, int64_t* iterations, void* hip_stream) {
     return guarded("mdc_head_trainer_read", [&]() -> int {
-        if (!t) { set_error("null trainer"); return MDC_EINVAL; }
-        DeviceScope dev(t->device);
-        if (!dev.ok) { set_error("mdc_head_trainer_read: cannot select device %d", t->device); return MDC_EIO; }
-        hipStream_t s = static_cast<hipStream_t>(hip_stream);
         HeadState h{};
-        MDC_HIP(hipMemcpyAsync(&h, t->d_state, sizeof(h), hipMemcpyDeviceToHost, s));
-        MDC_HIP(hipStreamSynchronize(s));
+        int rc = bank_read_state("mdc_head_trainer_read", t, reset, &h, sizeof(h), offsetof(HeadState, train_rows), static_cast<hipStream_t>(hip_stream));
+        if (rc != MDC_OK) return rc;
         if (train_loss_sum) *train_loss_sum = h.train_loss;
         if (train_rows) *train_rows = h.train_rows;
         if (eval_loss_sum) *eval_loss_sum = h.eval_loss;
         if (eval_rows) *eval_rows = h.eval_rows;
         if (eval_correct) *eval_correct = h.eval_correct;
         if (iterations) *iterations = h.iterations;
-        if (reset) {
-            // zero everything behind `iterations` (which is optimizer state, not a statistic)
-            MDC_HIP(hipMemsetAsync(reinterpret_cast<char*>(t->d_state) + offsetof(HeadState, train_rows), 0,
-                                   sizeof(HeadState) - offsetof(HeadState, train_rows), s));
-            MDC_HIP(hipStreamSynchronize(s));
-        }
         if (h.bad_indices) {      // (the statistics above are those of the rows that WERE addressable)
             set_error("mdc_head_trainer_read: %u batch positions named rows outside [0, n_rows) -- skipped, not trained on; check order_dev", h.bad_indices);
             return MDC_EINVAL;
@@ -760,8 +664,8 @@ void mdc_head_trainer_destroy(mdc_head_trainer* t) {
     if (!t) return;
     {
         DeviceScope dev(t->device);
-        for (void* p : {(void*)t->d_params, (void*)t->d_m, (void*)t->d_v, (void*)t->d_grad, (void*)t->d_z1part, (void*)t->d_dw1part, (void*)t->d_small,
-                        (void*)t->d_h, (void*)t->d_dz1, (void*)t->d_dz2, (void*)t->d_loss, (void*)t->d_hit, t->d_state})
+        t->release();
+        for (void* p : {(void*)t->d_z1part, (void*)t->d_dw1part, (void*)t->d_small, (void*)t->d_h, (void*)t->d_dz1, (void*)t->d_dz2, (void*)t->d_loss, (void*)t->d_hit})
             if (p) (void)hipFree(p);
     }
     delete t;

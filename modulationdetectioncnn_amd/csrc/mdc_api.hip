@@ -30,6 +30,19 @@ int upload(mdc_model* m, int idx, const void* host, size_t bytes) {
     return MDC_OK;
 }
 
+int check_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MDC_ENODEV; }
+    if (device < 0 || device >= ndev) { set_error("device %d out of range (have %d)", device, ndev); return MDC_ENODEV; }
+    hipDeviceProp_t prop;
+    MDC_HIP(hipGetDeviceProperties(&prop, device));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+        set_error("device %d is %s; libmdc.so carries gfx950 (MI355X) code only", device, prop.gcnArchName);
+        return MDC_ENODEV;
+    }
+    return MDC_OK;
+}
+
 ProfScope::ProfScope(const mdc_model* mm, int slot_, hipStream_t s_) : m(const_cast<mdc_model*>(mm)), slot(slot_), s(s_) {
     if (!m->profiling) return;
     if (hipEventCreate(&start) != hipSuccess) { start = nullptr; return; }
@@ -118,15 +131,7 @@ int mdc_create(const mdc_topology* topo, int device, mdc_model** out) {
             set_error("mdc_create: MDC_OPT_FP8_BF16_FEATURES applies to MDC_KIND_VTCNN2 only");
             return MDC_EINVAL;
         }
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MDC_ENODEV; }
-        if (device < 0 || device >= ndev) { set_error("device %d out of range (have %d)", device, ndev); return MDC_ENODEV; }
-        hipDeviceProp_t prop;
-        MDC_HIP(hipGetDeviceProperties(&prop, device));
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-            set_error("device %d is %s; libmdc.so carries gfx950 (MI355X) code only", device, prop.gcnArchName);
-            return MDC_ENODEV;
-        }
+        if (int dc = check_device(device); dc != MDC_OK) return dc;
         mdc_model* m = new (std::nothrow) mdc_model();
         if (!m) { set_error("out of host memory"); return MDC_ENOMEM; }
         m->topo = *topo;

@@ -192,6 +192,9 @@ struct DeviceScope {
     DeviceScope& operator=(const DeviceScope&) = delete;
 };
 
+// What every *_create asks of its device before it allocates anything: it exists and is a gfx950, else MDC_ENODEV (mdc_api.hip)
+int check_device(int device);
+
 // ---- host-buffer driver: host_path.hip ----------------------------------------------------
 int predict_host(mdc_model* m, const float* x_host, int64_t n, float* probs_host, int32_t* labels_host, int64_t chunk_frames);
 int predict_host_checked(mdc_model* m, const float* x_host, int64_t n, float* probs_host, int32_t* labels_host, uint8_t* nonfinite_host,

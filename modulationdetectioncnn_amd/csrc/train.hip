@@ -30,34 +30,21 @@
 // The batch of the reference (1,024 frames x 2,334 parameters) is launch-latency bound on this chip; that is why a step
 // is two launches and an epoch needs no host round trip but the final read of the loss.
 #include "train_common.h"           // dense_chain_common.h, fmix32, the Dropout generator, frame_index, wave_allsum
+#include "train_host.h"             // the parameter bank and the entry bodies shared with head_train.hip
 
 #include <cmath>
 #include <cstddef>
-#include <cstring>
 #include <new>
 #include <vector>
 
-struct mdc_trainer {
+struct mdc_trainer : mdc::ParamBank {      // (d_state: TrainState)
     mdc_topology topo{};
-    int device = 0;
-    int nlayers = 0;
-    size_t nk[4]{}, nb[4]{};
-    size_t off_k[4]{}, off_b[4]{};      // offsets into the flat parameter vector (Keras layouts, layer by layer: kernel, bias)
-    size_t P = 0;
-    bool have[4]{};
-    float lr = 1e-3f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-7f;      // keras.optimizers.Adam() defaults = the .h5 files' training_config
     float drop_rate = 0.f;       // optional Dropout(rate) behind the conv activations (and cnn.py's Dense(D)): 0 = the reference's nets
     unsigned drop_seed = 0;
-    // device state
-    float* d_params = nullptr;   // [P] master weights
-    float* d_m = nullptr;        // [P] Adam first moment
-    float* d_v = nullptr;        // [P] Adam second moment
-    float* d_grad = nullptr;     // [P] gradient of the last batch's mean loss
     float* d_partials = nullptr; // [kMaxWaves][Pint]
     size_t Pint = 0;             // floats per partial gradient vector: P for the deployed nets, the MFMA kernel's internal layout for cnn.py's
     int* d_map = nullptr;        // [P][3]: the (up to three) entries of a partial vector that sum to parameter i (-1 = none)
     double* d_loss_partials = nullptr;   // [kMaxWaves]
-    void* d_state = nullptr;     // TrainState
 };
 
 namespace mdc {
@@ -75,6 +62,7 @@ struct TrainState {
     unsigned tickets;          // work-groups of the running reduce + Adam launch that have read `iterations` (the last one bumps it)
     unsigned bad_indices;      // frames skipped because their index (order_dev's, or first + i) lay outside [0, n_frames): mdc_trainer_read reports them
 };
+static_assert(offsetof(TrainState, iterations) == 0, "bank_set_iterations writes the record's first field");
 
 // softmax -> Keras categorical_crossentropy on the probabilities -> gradient w.r.t. the softmax INPUT.  y: the target row.
 template <int CMAX>
@@ -704,22 +692,17 @@ int launch_batch(mdc_trainer* t, const float* x, const float* y, int64_t n_frame
     return MDC_OK;
 }
 
-int check_batch_args(const char* what, mdc_trainer* t, const float* x, const float* y, int64_t n_frames, const int32_t* order, int64_t first,
-                     int64_t count) {
-    if (!t) { set_error("%s: null trainer", what); return MDC_EINVAL; }
-    for (int l = 0; l < t->nlayers; ++l)
-        if (!t->have[l]) { set_error("%s: layer %d has no weights (mdc_trainer_set_weights)", what, l); return MDC_ESTATE; }
-    if (first < 0 || count < 0) { set_error("%s: negative range", what); return MDC_EINVAL; }
-    if (count > (int64_t)1 << 30) { set_error("%s: at most 2^30 frames per call", what); return MDC_EINVAL; }
-    if (count > 0 && (!x || !y)) { set_error("%s: null frames or targets", what); return MDC_EINVAL; }
-    if ((reinterpret_cast<uintptr_t>(x) & 15) != 0) { set_error("%s: frames must be 16-byte aligned", what); return MDC_EINVAL; }
-    if (n_frames < 0) { set_error("%s: negative n_frames", what); return MDC_EINVAL; }
-    // without a shuffle the positions ARE the frames: checked here; with one, its VALUES are checked on the device (frame_index)
-    if (!order && first + count > n_frames) {
-        set_error("%s: frames [%lld, %lld) outside the %lld of the buffers", what, (long long)first, (long long)(first + count), (long long)n_frames);
-        return MDC_EINVAL;
-    }
-    return MDC_OK;
+// mdc_train_batch (mode 1: gradient only, 2: gradient + Adam) and mdc_trainer_evaluate (mode 0) behind their names
+int batch_entry(const char* who, mdc_trainer* t, const float* x, const float* y, int64_t n_frames, const int32_t* order, int64_t first, int64_t count,
+                int mode, void* hip_stream) {
+    return guarded(who, [&]() -> int {
+        int rc = bank_check_batch(who, t, "frames", "frames", x, y, n_frames, order, first, count);
+        if (rc != MDC_OK) return rc;
+        if (count == 0) return MDC_OK;
+        DeviceScope dev(t->device);
+        if (!device_selected(who, dev)) return MDC_EIO;
+        return launch_batch(t, x, y, n_frames, order, first, count, mode, static_cast<hipStream_t>(hip_stream));
+    });
 }
 
 }  // namespace
@@ -735,36 +718,23 @@ int mdc_trainer_create(const mdc_topology* topo, int device, mdc_trainer** out) 
         if (!topo || !out) { set_error("mdc_trainer_create: null argument"); return MDC_EINVAL; }
         *out = nullptr;
         for (int i = 0; i < 4; ++i) if (topo->reserved[i] != 0) { set_error("mdc_trainer_create: reserved[] must be 0"); return MDC_EINVAL; }
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available"); return MDC_ENODEV; }
-        if (device < 0 || device >= ndev) { set_error("device %d out of range (have %d)", device, ndev); return MDC_ENODEV; }
-        hipDeviceProp_t prop;
-        MDC_HIP(hipGetDeviceProperties(&prop, device));
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-            set_error("device %d is %s; libmdc.so carries gfx950 (MI355X) code only", device, prop.gcnArchName);
-            return MDC_ENODEV;
-        }
+        int rc = check_device(device);
+        if (rc != MDC_OK) return rc;
         mdc_trainer* t = new (std::nothrow) mdc_trainer();
         if (!t) { set_error("out of host memory"); return MDC_ENOMEM; }
         t->topo = *topo;
         t->device = device;
-        int rc = trainer_layout(t);
+        rc = trainer_layout(t);
         if (rc != MDC_OK) { delete t; return rc; }
         DeviceScope dev(device);
-        if (!dev.ok) { set_error("mdc_trainer_create: cannot select device %d", device); delete t; return MDC_EIO; }
-        const size_t pb = t->P * sizeof(float);
+        if (!device_selected("mdc_trainer_create", dev)) { delete t; return MDC_EIO; }
         auto fail = [&](int code) { mdc_trainer_destroy(t); return code; };
-        if (hipMalloc(&t->d_params, pb) != hipSuccess || hipMalloc(&t->d_m, pb) != hipSuccess || hipMalloc(&t->d_v, pb) != hipSuccess ||
-            hipMalloc(&t->d_grad, pb) != hipSuccess || hipMalloc(&t->d_partials, t->Pint * sizeof(float) * kMaxWaves) != hipSuccess ||
-            hipMalloc(&t->d_map, t->P * 3 * sizeof(int)) != hipSuccess ||
-            hipMalloc(&t->d_loss_partials, sizeof(double) * kMaxWaves) != hipSuccess || hipMalloc(&t->d_state, sizeof(TrainState)) != hipSuccess) {
+        rc = t->alloc("mdc_trainer_create", sizeof(TrainState));
+        if (rc != MDC_OK) return fail(rc);
+        if (hipMalloc(&t->d_partials, t->Pint * sizeof(float) * kMaxWaves) != hipSuccess || hipMalloc(&t->d_map, t->P * 3 * sizeof(int)) != hipSuccess ||
+            hipMalloc(&t->d_loss_partials, sizeof(double) * kMaxWaves) != hipSuccess) {
             set_error("mdc_trainer_create: out of device memory");
             return fail(MDC_ENOMEM);
-        }
-        if (hipMemset(t->d_params, 0, pb) != hipSuccess || hipMemset(t->d_m, 0, pb) != hipSuccess || hipMemset(t->d_v, 0, pb) != hipSuccess ||
-            hipMemset(t->d_grad, 0, pb) != hipSuccess || hipMemset(t->d_state, 0, sizeof(TrainState)) != hipSuccess) {
-            set_error("mdc_trainer_create: hipMemset failed");
-            return fail(MDC_EIO);
         }
         const std::vector<int> map = trainer_map(t);
         if (hipMemcpy(t->d_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
@@ -789,13 +759,7 @@ int mdc_trainer_layer_sizes(const mdc_trainer* t, int layer, size_t* kernel_elem
 }
 
 int mdc_trainer_set_adam(mdc_trainer* t, float lr, float beta1, float beta2, float eps) {
-    if (!t) { set_error("null trainer"); return MDC_EINVAL; }
-    if (!(lr > 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f)) {
-        set_error("mdc_trainer_set_adam: need lr > 0, 0 <= beta < 1, eps >= 0");
-        return MDC_EINVAL;
-    }
-    t->lr = lr; t->beta1 = beta1; t->beta2 = beta2; t->eps = eps;
-    return MDC_OK;
+    return bank_set_adam("mdc_trainer_set_adam", t, lr, beta1, beta2, eps);
 }
 
 int mdc_trainer_set_dropout(mdc_trainer* t, float rate, uint32_t seed) {
@@ -806,120 +770,47 @@ int mdc_trainer_set_dropout(mdc_trainer* t, float rate, uint32_t seed) {
     return MDC_OK;
 }
 
-// which: 0 weights, 1 Adam m, 2 Adam v, 3 gradient of the last batch
-static float* trainer_vec(mdc_trainer* t, int which) {
-    switch (which) {
-        case MDC_TRAIN_WEIGHTS: return t->d_params;
-        case MDC_TRAIN_ADAM_M:  return t->d_m;
-        case MDC_TRAIN_ADAM_V:  return t->d_v;
-        case MDC_TRAIN_GRADIENT: return t->d_grad;
-        default: return nullptr;
-    }
-}
-
 int mdc_trainer_set_tensor(mdc_trainer* t, int which, int layer, const float* kernel_host, size_t kernel_elems, const float* bias_host,
                            size_t bias_elems, void* hip_stream) {
     return guarded("mdc_trainer_set_tensor", [&]() -> int {
-        if (!t || !kernel_host || !bias_host) { set_error("mdc_trainer_set_tensor: null argument"); return MDC_EINVAL; }
-        if (layer < 0 || layer >= t->nlayers) { set_error("mdc_trainer_set_tensor: layer %d out of range 0..%d", layer, t->nlayers - 1); return MDC_EINVAL; }
-        float* vec = trainer_vec(t, which);
-        if (!vec || which == MDC_TRAIN_GRADIENT) { set_error("mdc_trainer_set_tensor: `which` must be MDC_TRAIN_WEIGHTS, _ADAM_M or _ADAM_V"); return MDC_EINVAL; }
-        if (kernel_elems != t->nk[layer] || bias_elems != t->nb[layer]) {
-            set_error("mdc_trainer_set_tensor: layer %d expects kernel %zu / bias %zu elements, got %zu / %zu", layer, t->nk[layer], t->nb[layer],
-                      kernel_elems, bias_elems);
-            return MDC_EINVAL;
-        }
-        DeviceScope dev(t->device);
-        if (!dev.ok) { set_error("mdc_trainer_set_tensor: cannot select device %d", t->device); return MDC_EIO; }
-        hipStream_t s = static_cast<hipStream_t>(hip_stream);
-        MDC_HIP(hipMemcpyAsync(vec + t->off_k[layer], kernel_host, kernel_elems * sizeof(float), hipMemcpyHostToDevice, s));
-        MDC_HIP(hipMemcpyAsync(vec + t->off_b[layer], bias_host, bias_elems * sizeof(float), hipMemcpyHostToDevice, s));
-        MDC_HIP(hipStreamSynchronize(s));      // the host buffers are the caller's again on return
-        if (which == MDC_TRAIN_WEIGHTS) t->have[layer] = true;
-        return MDC_OK;
+        return bank_set_tensor("mdc_trainer_set_tensor", t, which, layer, kernel_host, kernel_elems, bias_host, bias_elems, static_cast<hipStream_t>(hip_stream));
     });
 }
 
 int mdc_trainer_get_tensor(mdc_trainer* t, int which, int layer, float* kernel_host, size_t kernel_elems, float* bias_host, size_t bias_elems,
                            void* hip_stream) {
     return guarded("mdc_trainer_get_tensor", [&]() -> int {
-        if (!t || !kernel_host || !bias_host) { set_error("mdc_trainer_get_tensor: null argument"); return MDC_EINVAL; }
-        if (layer < 0 || layer >= t->nlayers) { set_error("mdc_trainer_get_tensor: layer %d out of range 0..%d", layer, t->nlayers - 1); return MDC_EINVAL; }
-        float* vec = trainer_vec(t, which);
-        if (!vec) { set_error("mdc_trainer_get_tensor: unknown tensor kind %d", which); return MDC_EINVAL; }
-        if (kernel_elems != t->nk[layer] || bias_elems != t->nb[layer]) {
-            set_error("mdc_trainer_get_tensor: layer %d holds kernel %zu / bias %zu elements, asked for %zu / %zu", layer, t->nk[layer], t->nb[layer],
-                      kernel_elems, bias_elems);
-            return MDC_EINVAL;
-        }
-        DeviceScope dev(t->device);
-        if (!dev.ok) { set_error("mdc_trainer_get_tensor: cannot select device %d", t->device); return MDC_EIO; }
-        hipStream_t s = static_cast<hipStream_t>(hip_stream);
-        MDC_HIP(hipMemcpyAsync(kernel_host, vec + t->off_k[layer], kernel_elems * sizeof(float), hipMemcpyDeviceToHost, s));
-        MDC_HIP(hipMemcpyAsync(bias_host, vec + t->off_b[layer], bias_elems * sizeof(float), hipMemcpyDeviceToHost, s));
-        MDC_HIP(hipStreamSynchronize(s));
-        return MDC_OK;
+        return bank_get_tensor("mdc_trainer_get_tensor", t, which, layer, kernel_host, kernel_elems, bias_host, bias_elems, static_cast<hipStream_t>(hip_stream));
     });
 }
 
 int mdc_trainer_set_iterations(mdc_trainer* t, int64_t iterations, void* hip_stream) {
     return guarded("mdc_trainer_set_iterations", [&]() -> int {
-        if (!t || iterations < 0) { set_error("mdc_trainer_set_iterations: bad argument"); return MDC_EINVAL; }
-        DeviceScope dev(t->device);
-        if (!dev.ok) { set_error("mdc_trainer_set_iterations: cannot select device %d", t->device); return MDC_EIO; }
-        hipStream_t s = static_cast<hipStream_t>(hip_stream);
-        long long v = iterations;
-        MDC_HIP(hipMemcpyAsync(&static_cast<TrainState*>(t->d_state)->iterations, &v, sizeof(v), hipMemcpyHostToDevice, s));
-        MDC_HIP(hipStreamSynchronize(s));
-        return MDC_OK;
+        return bank_set_iterations("mdc_trainer_set_iterations", t, iterations, static_cast<hipStream_t>(hip_stream));
     });
 }
 
 int mdc_train_batch(mdc_trainer* t, const float* x_dev, const float* y_dev, int64_t n_frames, const int32_t* order_dev, int64_t first,
                     int64_t count, int apply, void* hip_stream) {
-    return guarded("mdc_train_batch", [&]() -> int {
-        int rc = check_batch_args("mdc_train_batch", t, x_dev, y_dev, n_frames, order_dev, first, count);
-        if (rc != MDC_OK) return rc;
-        if (count == 0) return MDC_OK;
-        DeviceScope dev(t->device);
-        if (!dev.ok) { set_error("mdc_train_batch: cannot select device %d", t->device); return MDC_EIO; }
-        return launch_batch(t, x_dev, y_dev, n_frames, order_dev, first, count, apply ? 2 : 1, static_cast<hipStream_t>(hip_stream));
-    });
+    return batch_entry("mdc_train_batch", t, x_dev, y_dev, n_frames, order_dev, first, count, apply ? 2 : 1, hip_stream);
 }
 
 int mdc_trainer_evaluate(mdc_trainer* t, const float* x_dev, const float* y_dev, int64_t n_frames, const int32_t* order_dev, int64_t first,
                          int64_t count, void* hip_stream) {
-    return guarded("mdc_trainer_evaluate", [&]() -> int {
-        int rc = check_batch_args("mdc_trainer_evaluate", t, x_dev, y_dev, n_frames, order_dev, first, count);
-        if (rc != MDC_OK) return rc;
-        if (count == 0) return MDC_OK;
-        DeviceScope dev(t->device);
-        if (!dev.ok) { set_error("mdc_trainer_evaluate: cannot select device %d", t->device); return MDC_EIO; }
-        return launch_batch(t, x_dev, y_dev, n_frames, order_dev, first, count, 0, static_cast<hipStream_t>(hip_stream));
-    });
+    return batch_entry("mdc_trainer_evaluate", t, x_dev, y_dev, n_frames, order_dev, first, count, 0, hip_stream);
 }
 
 int mdc_trainer_read(mdc_trainer* t, int reset, double* train_loss_sum, int64_t* train_frames, double* eval_loss_sum, int64_t* eval_frames,
                      int64_t* iterations, void* hip_stream) {
     return guarded("mdc_trainer_read", [&]() -> int {
-        if (!t) { set_error("null trainer"); return MDC_EINVAL; }
-        DeviceScope dev(t->device);
-        if (!dev.ok) { set_error("mdc_trainer_read: cannot select device %d", t->device); return MDC_EIO; }
-        hipStream_t s = static_cast<hipStream_t>(hip_stream);
         TrainState h{};
-        MDC_HIP(hipMemcpyAsync(&h, t->d_state, sizeof(h), hipMemcpyDeviceToHost, s));
-        MDC_HIP(hipStreamSynchronize(s));
+        int rc = bank_read_state("mdc_trainer_read", t, reset, &h, sizeof(h), offsetof(TrainState, train_frames), static_cast<hipStream_t>(hip_stream));
+        if (rc != MDC_OK) return rc;
         if (train_loss_sum) *train_loss_sum = h.train_loss;
         if (train_frames) *train_frames = h.train_frames;
         if (eval_loss_sum) *eval_loss_sum = h.eval_loss;
         if (eval_frames) *eval_frames = h.eval_frames;
         if (iterations) *iterations = h.iterations;
-        if (reset) {
-            // zero the four accumulators behind `iterations` (which is optimizer state, not a statistic)
-            MDC_HIP(hipMemsetAsync(reinterpret_cast<char*>(t->d_state) + offsetof(TrainState, train_frames), 0,
-                                   sizeof(TrainState) - offsetof(TrainState, train_frames), s));
-            MDC_HIP(hipStreamSynchronize(s));
-        }
         if (h.bad_indices) {      // (the statistics above are those of the frames that WERE addressable)
             set_error("mdc_trainer_read: %u batch positions named frames outside [0, n_frames) -- skipped, not trained on; check order_dev", h.bad_indices);
             return MDC_EINVAL;
@@ -932,7 +823,8 @@ void mdc_trainer_destroy(mdc_trainer* t) {
     if (!t) return;
     {
         DeviceScope dev(t->device);
-        for (void* p : {(void*)t->d_params, (void*)t->d_m, (void*)t->d_v, (void*)t->d_grad, (void*)t->d_partials, (void*)t->d_loss_partials, t->d_state, (void*)t->d_map})
+        t->release();
+        for (void* p : {(void*)t->d_partials, (void*)t->d_loss_partials, (void*)t->d_map})
             if (p) (void)hipFree(p);
     }
     delete t;

@@ -1,7 +1,8 @@
 // What the two training files share (train.hip: the nets the reference trains; head_train.hip: the dense head of VT-CNN2):
 // the Dropout mask generator that include/mdc.h states under mdc_trainer_set_dropout, the checked batch index, the wave sum
 // whose result is the same bits in every lane, and TensorFlow's Adam update.  `St` is the file's device state record: it has
-// `iterations` (Adam's step count) and `bad_indices`.
+// `iterations` (Adam's step count) and `bad_indices`.  This is the device half; the host half of what they share -- the parameter
+// bank and the bodies of the set / get / read entries -- is train_host.h / train_host.hip.
 #pragma once
 #include "dense_chain_common.h"      // mdc_internal.h, f32x4, row_allreduce (the 16-lane DPP butterflies)
 #include "mdc_fmix32.h"

@@ -51,6 +51,32 @@ def test_trainer_entry_points_validate_their_arguments_without_gpu():
     L.mdc_trainer_destroy(None)
 
 
+def test_head_trainer_entry_points_validate_their_arguments_without_gpu():
+    """The head trainer's half of the shared host code (csrc/train_host.hip), and both creates' argument checks, which come
+    before the device check: -22 here, where there is no device, not MDC_ENODEV."""
+    L = _cabi.lib()
+    L.mdc_last_error.restype = ctypes.c_char_p
+    assert L.mdc_head_train_batch(None, None, None, 1, None, 0, 1, 1, None) == -22 and b"null trainer" in L.mdc_last_error()
+    assert L.mdc_head_trainer_evaluate(None, None, None, 1, None, 0, 1, None) == -22 and b"null trainer" in L.mdc_last_error()
+    assert L.mdc_head_trainer_set_adam(None, 1e-3, 0.9, 0.999, 1e-7) == -22
+    assert L.mdc_head_trainer_set_dropout(None, 0.5, 0.5, 0) == -22
+    one = (ctypes.c_float * 1)()
+    assert L.mdc_head_trainer_set_tensor(None, _cabi.TRAIN_WEIGHTS, 0, one, 1, one, 1, None) == -22 and b"null" in L.mdc_last_error()
+    assert L.mdc_head_trainer_get_tensor(None, _cabi.TRAIN_WEIGHTS, 0, one, 1, one, 1, None) == -22 and b"null" in L.mdc_last_error()
+    assert L.mdc_head_trainer_set_iterations(None, 0, None) == -22
+    assert L.mdc_head_trainer_read(None, 0, None, None, None, None, None, None, None) == -22 and b"null trainer" in L.mdc_last_error()
+    L.mdc_head_trainer_destroy(None)
+    h = ctypes.c_void_p()
+    assert L.mdc_head_trainer_create(10560, 256, 11, 1024, 0, None) == -22 and b"null" in L.mdc_last_error()
+    for features, hidden, classes, max_batch, word in ((33, 256, 11, 1024, b"features"), (10560, 16, 11, 1024, b"hidden"), (10560, 256, 1, 1024, b"classes"),
+                                                       (10560, 256, 11, 0, b"max_batch")):
+        assert L.mdc_head_trainer_create(features, hidden, classes, max_batch, 0, ctypes.byref(h)) == -22 and word in L.mdc_last_error(), word
+        assert not h.value
+    topo = _cabi.MdcTopology(_cabi.KIND_DEPLOYED, 3, 0, 3, (ctypes.c_int32 * 4)(0, 1, 0, 0))
+    assert L.mdc_trainer_create(ctypes.byref(topo), 0, ctypes.byref(h)) == -22 and b"reserved" in L.mdc_last_error()
+    assert not h.value
+
+
 def test_product_library_has_one_kernel_per_role_and_never_reads_the_environment():
     """the measured-slower alternates (hipcc-scheduled bf16 conv, one-barrier dense1, the deployed nets'
     f32-MFMA dense layer) live in libmdc_alt.so only, and nothing in libmdc.so can call getenv -- the symbol is not even

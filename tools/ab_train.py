@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""ON THE GPU BOX: A/B of two BUILDS of the library on the training step (csrc/train.hip) in one run: interleaved child
-processes; per net (T1, T2, T4) the time of one 1,024-frame step (gradient + Adam launches) replayed from a hipGraph of 19
-steps (an epoch of the reference's 18,900 frames), the eager time, and a hash of the weights after those steps (a change
-that only moves loads and stores must leave it unchanged).
+"""ON THE GPU BOX: A/B of two BUILDS of the library on the training step (csrc/train.hip, csrc/head_train.hip) in one run:
+interleaved child processes; per net (T1, T2, T4) and for VT-CNN2's dense head (10560, 256, 11) the time of one 1,024-sample
+step replayed from a hipGraph of 19 steps (an epoch of the reference's 18,900 frames), the eager time, and a hash of the
+weights after those steps (a change that only moves loads and stores, or host code, must leave it unchanged).
     cp modulationdetectioncnn_amd/libmdc.so tools/ab_prev.so        # before rebuilding
-    gpurun -- 'python tools/ab_train.py tools/ab_prev.so [rounds = 3]'"""
+    python tools/ab_train.py tools/ab_prev.so [rounds = 3]"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 other = os.path.abspath(sys.argv[1])
@@ -17,13 +17,23 @@ if sys.argv[1] != "current":
     _cabi.LIB_PATHS["product"] = sys.argv[1]
 import torch, numpy as np
 from modulationdetectioncnn_amd import Topology, synthetic_frames, synthetic_weights
-from modulationdetectioncnn_amd.training import Trainer
+from modulationdetectioncnn_amd.training import HeadTrainer, Trainer
 n, batch = 18900, 1024
-for name, topo in (("T1", Topology.deployed(3)), ("T2", Topology.deployed(10)), ("T4", Topology.cnnpy(10, 10, 5))):
-    x = synthetic_frames(n, seed=2016, device="cuda:0") * (40.0 if topo.kind == "cnnpy" else 1.0)
-    lab = torch.randint(0, topo.classes, (n,), device="cuda:0", generator=torch.Generator("cuda:0").manual_seed(1))
-    tr = Trainer(topo, synthetic_weights(topo, seed=2016), device=0)
-    xd, yd = tr._frames(x), tr._targets(lab, n)
+def cases():
+    for name, topo in (("T1", Topology.deployed(3)), ("T2", Topology.deployed(10)), ("T4", Topology.cnnpy(10, 10, 5))):
+        x = synthetic_frames(n, seed=2016, device="cuda:0") * (40.0 if topo.kind == "cnnpy" else 1.0)
+        lab = torch.randint(0, topo.classes, (n,), device="cuda:0", generator=torch.Generator("cuda:0").manual_seed(1))
+        tr = Trainer(topo, synthetic_weights(topo, seed=2016), device=0)
+        yield name, tr, tr._frames(x), tr._targets(lab, n)
+    K, H, Cn = 10560, 256, 11                                # VT-CNN2's dense head on feature rows
+    f = torch.rand(n, K, device="cuda:0", generator=torch.Generator("cuda:0").manual_seed(3))
+    lab = torch.randint(0, Cn, (n,), device="cuda:0", generator=torch.Generator("cuda:0").manual_seed(1))
+    rng = np.random.default_rng(2016)
+    w = [((0.01 * rng.standard_normal((K, H))).astype(np.float32), np.zeros(H, np.float32)),
+         ((0.05 * rng.standard_normal((H, Cn))).astype(np.float32), np.zeros(Cn, np.float32))]
+    tr = HeadTrainer(K, H, Cn, w, device=0, max_batch=batch)
+    yield "head", tr, tr._rows(f), tr._targets(lab, n)
+for name, tr, xd, yd in cases():
     order = torch.randperm(n, device="cuda:0", generator=torch.Generator("cuda:0").manual_seed(2)).to(torch.int32)
     def epoch():
         for s in range(0, n, batch):
