@@ -53,6 +53,14 @@ level per bin for the whole capture:
 
     python examples/classify_capture.py capture.bin --format ci16 --detections --floor cfar --cfar 8,32,2,8,0.5
 
+A recording that does not fit on the device -- minutes of a wideband receiver -- takes --stream CHUNK_PAIRS on top of that: the file
+is read CHUNK_PAIRS pairs at a time (never more than one chunk on the host), every chunk is pushed into VTCNN2.detect_stream, and
+each box is printed when it has closed.  The boxes are those of the run without --stream, bit for bit, whatever the chunk size;
+only the local floor allows that, so --stream is an error without --detections --floor cfar.  --max-rows bounds what is held for
+an emitter that never pauses (its box is then cut, and the line says so):
+
+    python examples/classify_capture.py long.bin --format ci16 --detections --floor cfar --stream 1048576
+
 A band with a channel raster -- PMR / LMR, GSM, FM broadcast, ISM sub-bands -- is split into all its M evenly spaced channels in
 one pass instead (frontend.channelize, a polyphase filter bank on the device; VTCNN2.predict_channels), one line per channel:
 
@@ -261,6 +269,54 @@ def detections(model, iq, fmt, nfft=1024, threshold_db=6.0, rate=None, hop=128, 
     return found
 
 
+def file_chunks(path, fmt, chunk_pairs, full_scale=None):
+    """--stream: the capture file, chunk_pairs pairs at a time -- never more than one chunk on the host.  "cf32" chunks are
+    quantised on the device with the fixed --full-scale (frontend.quantize_cf32 is stateless per chunk with one)."""
+    dtype = np.dtype("<f4") if fmt == "cf32" else np.dtype(DTYPES[fmt])
+    with open(path, "rb") as f:
+        while True:
+            x = np.fromfile(f, dtype, 2 * chunk_pairs)
+            if x.size < 2:
+                return
+            x = x[:x.size // 2 * 2]
+            if fmt == "cf32":
+                from modulationdetectioncnn_amd import frontend
+                x = frontend.quantize_cf32(x, full_scale=full_scale).reshape(-1)
+            yield x
+
+
+def stream_detections(model, chunks, fmt, nfft=1024, threshold_db=6.0, rate=None, level=7.8e-3, squelch=-60.0, refine=False, cfar=None,
+                      max_rows=4096):
+    """detections(..., batched=True, floor="cfar") for a capture that arrives as an iterable of chunks (VTCNN2.detect_stream):
+    the same lines, each printed when its box has closed -- in order of closing, not of first pair -- and the count at the end.
+    A box that max_rows cut short (an emitter that never pauses) is marked with a trailing `cut`."""
+    k, unit = (rate, "Hz") if rate else (1.0, "cyc/sample")
+    print(f"{'first pair':>12s} {'stop pair':>12s} {'centre':>12s} {'bandwidth':>12s} {'peak dB':>8s} {'L/D':>7s} {'windows':>8s} {'open':>6s} {'label':>6s}"
+          + (f" {'symbol rate':>12s} {'refined':>12s}" if refine else ""))
+    found, held = [], 0
+
+    def show(records):
+        for d in records:
+            labels = np.asarray(d["labels"].cpu() if hasattr(d["labels"], "cpu") else d["labels"])
+            more = ""
+            if refine:
+                symbol = "-" if d["symbol_rate"] is None else f"{d['symbol_rate'] * k:.6g}"
+                more = f" {symbol:>12s} {(d['centre'] + d['carrier_offset']) * k:12.8g}"
+            print(f"{d['first_pair']:12d} {d['stop_pair']:12d} {d['centre'] * k:12.6g} {d['bandwidth'] * k:12.6g} {d['snr_db']:8.1f} "
+                  f"{str(d['interpolate']) + '/' + str(d['decimate']):>7s} {d['windows']:8d} {int((labels >= 0).sum()):6d} {d['label']:6d}{more}"
+                  + (" cut" if d["cut"] else ""), flush=True)
+            found.append(d)
+
+    fmt = "ci16" if fmt == "cf32" else fmt
+    with model.detect_stream(fmt, nfft=nfft, threshold_db=threshold_db, level=level, squelch_dbfs=squelch, refine=refine, cfar=cfar, max_rows=max_rows) as s:
+        for chunk in chunks:
+            show(s.push(chunk))
+            held = max(held, s.pairs_held)
+        show(s.close())
+    print(f"{len(found)} detections ({unit}) in {s.pairs_seen} pairs; at most {held} pairs held between chunks")
+    return found
+
+
 def synthetic_raster(fmt="ci16", channels=16, seed=1, pairs=1 << 16):
     """QPSK with a root-raised-cosine pulse (beta 0.35), 8 samples per symbol at the channelizer's default output rate 2 / M, on the
     raster's channels 3 and M - 5, rms 0.05 of full scale each, over noise of rms 0.002."""
@@ -378,7 +434,36 @@ def main():
                          "capture, first (an uncalibrated zero-IF receiver lists every strong emitter's mirror image as an emitter)")
     ap.add_argument("--imbalance", action="store_true",
                     help="with --scan and no capture file: the synthetic band as a receiver 1 dB / 5 degrees out of balance delivers it")
+    ap.add_argument("--stream", type=int, default=0, metavar="CHUNK_PAIRS",
+                    help="with --detections --floor cfar: read the capture this many pairs at a time and print every box when it has closed "
+                         "(VTCNN2.detect_stream: the same boxes, for a recording that does not fit on the device, or a receiver)")
+    ap.add_argument("--max-rows", type=int, default=4096,
+                    help="with --stream: spectrogram rows after which a box that is still open is cut (an emitter that never pauses)")
     a = ap.parse_args()
+    if a.stream:
+        if a.stream < 0 or not a.detections or a.floor != "cfar":
+            ap.error("--stream CHUNK_PAIRS goes with --detections --floor cfar: only the local floor can be computed a chunk at a time "
+                     "(the 'flat' and 'per-bin' floors are quantiles over the whole capture)")
+        if a.balance:
+            ap.error("--stream cannot take --balance: the coefficients would be estimated from the whole capture")
+        if a.hop != 128:
+            ap.error("--stream needs --hop 128, as --batched does")
+        if a.format == "cf32" and a.full_scale is None:
+            ap.error("--stream with --format cf32 needs --full-scale: a gain measured per chunk would change from chunk to chunk")
+    if a.detections and a.stream:
+        if a.capture:
+            chunks = file_chunks(a.capture, a.format, a.stream, a.full_scale)
+        else:
+            iq, a.format = load(a, synthetic_hopper)
+            chunks = (iq[at:at + 2 * a.stream] for at in range(0, iq.size // 2 * 2, 2 * a.stream))
+        if a.weights is None:
+            model = VTCNN2.synthetic("deployed3")
+        else:
+            model = VTCNN2.from_npz(a.weights) if a.weights.endswith(".npz") else VTCNN2.from_h5(a.weights)
+        stream_detections(model, chunks, a.format, nfft=a.nfft, threshold_db=a.threshold, rate=a.rate if a.rate != 1.0 else None, level=a.level,
+                          squelch=a.squelch, refine=a.refine, cfar=None if a.cfar is None else tuple(float(v) for v in a.cfar.split(",")),
+                          max_rows=a.max_rows)
+        return
     if a.detections:
         iq, a.format = load(a, synthetic_hopper)
         if a.weights is None:

@@ -1,6 +1,7 @@
 """The capture pipelines scan_iq, detect_iq and predict_channels as functions of a model: they use its predict_iq, device_index
 and topology.classes, the rest is the frontend's pieces in order.  VTCNN2 binds the three as methods, hence `self`.  torch and
-the frontend are imported at the first call, not with the package."""
+the frontend are imported at the first call, not with the package.  detect_stream, bound the same way, is detect_iq for a capture
+that arrives in chunks: DetectStream runs the same pieces per chunk, _StreamCore keeps the books."""
 from __future__ import annotations
 
 from typing import Optional
@@ -390,3 +391,269 @@ def predict_channels(self, iq, sample_format, channels: int, decimate: Optional[
     if as_numpy:
         return probs.cpu().numpy(), labels.cpu().numpy(), dbfs.cpu().numpy(), label.cpu().numpy()
     return probs, labels, dbfs, label
+
+
+# ---- detect_iq on a capture that arrives in chunks: the bookkeeping (no arithmetic), and the stream that runs it on the device ----
+class _StreamCore:
+    """detect_stream's bookkeeping: which spectrogram rows exist, which ratio rows are final, which components are closed, which
+    were emitted, from which row on anything is still needed -- and nothing else.  It owns three sequences it only slices and
+    joins (the raw components, 2 per pair; the spectrogram's rows; the ratio's rows) and calls five injected functions for all
+    arithmetic: spectrogram(pairs) -> the rows of a stretch that starts on a row boundary; ratio(spec) -> the CFAR ratio of a
+    slab of rows; components(ratio) -> records with row_first, row_stop, bin_first, bin_stop (frontend.spectrogram_components');
+    classify(ratio, pairs, records) -> the records' dicts, rows and pairs counted from the window's first row; cat(a, b) -> a
+    followed by b (a is None at the start).  DetectStream injects the device functions, tests/test_capture_stream.py the numpy
+    restatements.  Rows are global (from the stream's start) throughout:
+      S     spectrogram rows that exist: row r reads pairs [r R, r R + R + nfft/2), R = avg nfft / 2 (frontend.burst_pairs)
+      F     ratio rows that are final: F = S - train_rows while the stream is open (the CFAR window of row r reads rows r -
+            train_rows .. r + train_rows, cut off only at the slab's borders), F = S once it is closed
+      t0    the first row anything still depends on: raw pairs from t0 R on and ratio rows [t0, F) are held
+      mark  the F (or the forced cut) of the previous round: a component with row_stop + reach_rows <= mark was emitted then or
+            earlier, whole or as part of a larger one, and is skipped -- the emit-once rule
+    A component is closed when row_stop + reach_rows <= F: an on-cell links to rows at most reach_rows away (include/mdc.h,
+    "spectrogram components"), the component's last row is row_stop - 1, so the last row that could still join it is row_stop
+    - 1 + reach_rows, and that row is final iff it is < F.  A closed component lies whole inside [t0, F) -- it was open from its
+    first row on, and t0 never passes an open component's first row -- so its record is the whole capture's."""
+
+    def __init__(self, nfft, avg, train_rows, reach_rows, min_rows, min_bins, max_rows, spectrogram, ratio, components, classify, cat):
+        self.nfft, self.avg, self.hop, self.R = int(nfft), int(avg), int(nfft) // 2, int(avg) * (int(nfft) // 2)
+        self.train_rows, self.reach_rows, self.min_rows, self.min_bins, self.max_rows = int(train_rows), int(reach_rows), int(min_rows), int(min_bins), int(max_rows)
+        if self.max_rows < 1:
+            raise ValueError(f"max_rows must be >= 1 (got {max_rows!r})")
+        self._spectrogram, self._ratio, self._components, self._classify, self._cat = spectrogram, ratio, components, classify, cat
+        self.pairs_seen = self.S = self.F = self.t0 = self.mark = 0
+        self.pair0 = self.spec0 = 0      # the first pair of self.pairs, the first row of self.spec; self.ratio starts at t0
+        self.pairs = self.spec = self.ratio = None
+        self.closed = False
+
+    @property
+    def pairs_held(self):
+        return self.pairs_seen - self.pair0
+
+    @property
+    def pairs_bound(self):
+        """pairs_held never exceeds this after a push: F - t0 <= max_rows, S - F <= train_rows, and fewer than R + nfft/2 pairs
+        wait for their row"""
+        return (self.max_rows + self.train_rows + 1) * self.R + self.hop - 1
+
+    def rows_of(self, pairs):
+        """frontend.spectrogram_rows(pairs, nfft, nfft // 2, avg)"""
+        return 0 if pairs < self.nfft else ((pairs - self.nfft) // self.hop + 1) // self.avg
+
+    def push(self, chunk, pairs):
+        """chunk: `pairs` more pairs (2 * pairs components, in the sequence type the injected functions take)"""
+        if self.closed:
+            raise ValueError("push after close: the stream has ended")
+        if pairs:
+            self.pairs = self._cat(self.pairs, chunk)
+            self.pairs_seen += int(pairs)
+        return self._advance()
+
+    def close(self):
+        if self.closed:
+            return []
+        self.closed = True
+        out = self._advance()
+        self.abandon()
+        return out
+
+    def abandon(self):
+        """closed, and nothing held"""
+        self.closed = True
+        self.pairs = self.spec = self.ratio = None
+        self.pair0 = self.pairs_seen
+
+    def _advance(self):
+        R, T = self.R, self.train_rows
+        S = self.rows_of(self.pairs_seen)
+        if S > self.S:      # rows [self.S, S): from a slice that starts on a row boundary and holds exactly their pairs
+            new = self._spectrogram(self.pairs[2 * (self.S * R - self.pair0):2 * (S * R + self.hop - self.pair0)])
+            if len(new) != S - self.S:
+                raise RuntimeError(f"the spectrogram of rows [{self.S}, {S}) came back with {len(new)} rows")
+            self.spec, self.S = self._cat(self.spec, new), S
+        F = self.S if self.closed else max(self.S - T, 0)
+        if F > self.F:      # rows [self.F, F) of the ratio: the interior of a slab that reaches train_rows rows back and ahead
+            lo, hi = max(self.F - T, 0), min(F + T, self.S)
+            slab = self._ratio(self.spec[lo - self.spec0:hi - self.spec0])
+            self.ratio, self.F = self._cat(self.ratio, slab[self.F - lo:F - lo]), F
+            keep = max(F - T, 0)
+            self.spec, self.spec0 = self.spec[keep - self.spec0:], keep
+        out = self._emit()
+        self.pairs, self.pair0 = (None, self.pairs_seen) if self.pairs is None else (self.pairs[2 * (self.t0 * R - self.pair0):], self.t0 * R)
+        out.sort(key=lambda r: (r["first_pair"], r["centre"]))
+        return out
+
+    def _emit(self):
+        """The rounds of one advance.  A round looks at the window [t0, E), E = min(F, t0 + max_rows): a larger step is taken in
+        pieces, so that closing, t0 and the forced cuts depend on the rows alone and not on how they arrived."""
+        out, M, reach = [], self.max_rows, self.reach_rows
+        while self.ratio is not None:
+            t0, E = self.t0, min(self.F, self.t0 + M)
+            if E <= t0 or (E == self.mark and E == self.F and not self.closed):
+                break      # no rows, or nothing new since the last round
+            last = self.closed and E == self.F
+            window = self.ratio[:E - t0]
+            recs = self._components(window)
+            first, stop = np.asarray(recs["row_first"], np.int64) + t0, np.asarray(recs["row_stop"], np.int64) + t0
+            fresh = stop + reach > self.mark
+            shut = fresh & (np.full(stop.shape, last) | (stop + reach <= E))
+            open_ = fresh & ~shut
+            t0_next = int(first[open_].min()) if open_.any() else E
+            # forced cut: an open component holds all max_rows rows of the window (t0 cannot move) and rows beyond it are final
+            forced = not last and E < self.F and t0_next + M <= E
+            big = (stop - first >= self.min_rows) & (np.asarray(recs["bin_stop"], np.int64) - np.asarray(recs["bin_first"], np.int64) >= self.min_bins)
+            for sel, cut in ((shut & big, False), (open_ & big, True)) if forced else ((shut & big, False),):
+                if sel.any():
+                    for r in self._classify(window, self.pairs[2 * (t0 * self.R - self.pair0):], recs[sel]):
+                        out.append(dict(r, first_row=r["first_row"] + t0, stop_row=r["stop_row"] + t0, first_pair=r["first_pair"] + t0 * self.R,
+                                        stop_pair=r["stop_pair"] + t0 * self.R, cut=cut))
+            if forced:
+                t0_next = E
+            self.mark = E
+            self.ratio, self.t0 = self.ratio[t0_next - t0:], t0_next
+            if E == self.F:
+                break
+        if self.ratio is not None and len(self.ratio) == 0:
+            self.ratio = None
+        return out
+
+
+class DetectStream:
+    """detect_iq(floor="cfar", batched=True) on a capture that arrives in chunks (VTCNN2.detect_stream makes one).  push(chunk)
+    takes any number of pairs -- a fraction of a spectrogram row, none, many rows -- as a numpy array or a device tensor in the
+    stream's sample format and returns the records of every detection that CLOSED with this chunk; close() treats the end of
+    the stream as the end of the capture and returns the rest (a second close() returns []; leaving the `with` block closes the
+    stream and drops what it holds, so call close() yourself for its records); push after close is a ValueError.  The records
+    of all calls together are detect_iq's of the concatenated capture, key for key and bit for bit, however the capture was
+    cut into chunks -- first_row, stop_row, first_pair and stop_pair count from the stream's start; probs, labels and
+    window_dbfs are numpy arrays when the chunk of the call that returns them was one -- plus one key, cut (below).  Two
+    differences: a stream that ends before its first row gives [] where detect_iq raises, and max_rows.
+    Why chunks can be exact: a spectrogram row reads only its own pairs, so new rows come from a slice that
+    starts on a row boundary; the CFAR window is cut off only at the borders of what it is given, so a ratio row is final once
+    train_rows rows after it exist, computed from a slab that reaches train_rows rows back; a component cannot grow once
+    row_stop + reach_rows <= the final rows, is emitted in the round in which that first holds, and components smaller than
+    min_rows / min_bins are dropped only then; extraction and refinement start their oscillators at each detection's first
+    pair, so they run on the retained pairs with rebased offsets.  Per push: one spectrogram over the new rows, one CFAR over
+    them plus 2 train_rows, one labelling of the retained rows (its count read back: the one synchronisation) and, when
+    something closed, detect_iq's batched extraction and forward.
+    pairs_seen: pairs pushed so far; rows_final: ratio rows that can no longer change; pairs_held: raw pairs retained on the
+    device -- from the first row of the oldest detection still open.  max_rows bounds it against an emitter that never
+    pauses: when more than max_rows rows from that row on are final, those max_rows rows are closed as if the capture ended
+    there, every detection in them is emitted -- cut=True for one that touches their last reach_rows rows, the ones the cut
+    goes through; cut=False for every other record -- and what follows becomes a new detection.  This is the one departure
+    from the whole capture's records, and it depends on the rows alone, not on the chunking.  After every call pairs_held <=
+    pairs_bound = (max_rows + train_rows + 1) * avg * nfft / 2 + nfft / 2 - 1: at most max_rows final rows are held, train_rows
+    rows wait for rows after them, and fewer than one row's avg * nfft / 2 + nfft / 2 pairs wait for the rest of their row;
+    during a push the chunk comes on top, and the joined buffer is a copy, so the peak is twice that."""
+
+    def __init__(self, model, sample_format, nfft: int = 1024, avg: int = 8, threshold_db: float = 6.0, floor: str = "cfar", reach_rows: int = 2,
+                 reach_bins: int = 3, min_rows: int = 3, min_bins: int = 3, level: float = 7.8e-3, squelch_dbfs: Optional[float] = None,
+                 dc_guard: int = 1, refine: bool = False, min_line_db: float = 8.0, line_nfft: int = 1024, line_avg: int = 8, balance=False,
+                 cfar=None, max_rows: int = 4096):
+        from . import frontend as F
+        if floor != "cfar":
+            raise ValueError(f"a stream takes floor='cfar' only (got {floor!r}): the 'flat' and 'per-bin' floors are quantiles over the whole "
+                             "capture, which no chunked run can reproduce")
+        if balance is True:
+            raise ValueError("balance=True estimates the coefficients from the whole capture, which a stream never holds: estimate them on "
+                             "a first stretch (frontend.balance_stats, frontend.design_balance) and pass the coefficients tuple")
+        self._fmt = F.sample_format_id(sample_format)      # "cu8", "ci8", "ci16": a cf32 chunk goes through frontend.quantize_cf32 first
+        self._cfar = F.cfar_parameters(cfar)
+        if not 0 <= self._cfar[0] <= _cabi.CFAR_MAX_TRAIN_ROWS:
+            raise ValueError(f"train_rows must be in 0..{_cabi.CFAR_MAX_TRAIN_ROWS} (got {self._cfar[0]})")
+        if not 0 <= int(reach_rows) <= _cabi.COMPONENTS_MAX_REACH:
+            raise ValueError(f"reach_rows must be in 0..{_cabi.COMPONENTS_MAX_REACH} (got {reach_rows!r})")
+        F.spectrogram_rows(0, nfft, int(nfft) // 2, avg)      # nfft and avg are checked here, before any chunk
+        self._model, self._device = model, f"cuda:{model.device_index}"
+        self._coeffs = None if balance is False or balance is None else balance
+        self._dev_fmt = self._fmt if self._coeffs is None else _cabi.IQ_CI16
+        self._balanced = {} if self._coeffs is None else dict(image_rejection_db=None)
+        self._nfft, self._avg, self._reach, self._thresh_args, self._thresh = int(nfft), int(avg), (int(reach_rows), int(reach_bins)), (threshold_db, dc_guard), None
+        self._level, self._squelch, self._refine, self._line = level, squelch_dbfs, bool(refine), (min_line_db, line_nfft, line_avg)
+        self._as_numpy, self._ratios = False, {}      # _ratios: bandwidth -> (L, D) of frontend.channel_plan (a box has one of nfft widths)
+        self._core =_StreamCore(nfft, avg, self._cfar[0], reach_rows, min_rows, min_bins, max_rows, self._spectrogram, self._ratio,
+                                 self._components, self._classify, self._cat)
+
+    pairs_seen = property(lambda self: self._core.pairs_seen)
+    pairs_held = property(lambda self: self._core.pairs_held)
+    pairs_bound = property(lambda self: self._core.pairs_bound)
+    rows_final = property(lambda self: self._core.F)
+
+    # the five functions of _StreamCore, on the device
+    @staticmethod
+    def _cat(a, b):
+        import torch
+        return b.clone() if a is None else torch.cat((a, b))      # (a clone: the first chunk may be the caller's own tensor)
+
+    def _spectrogram(self, pairs):
+        from . import frontend as F
+        return F.spectrogram(pairs, self._dev_fmt, nfft=self._nfft, avg=self._avg)
+
+    def _ratio(self, spec):
+        from . import frontend as F
+        return F.cfar_floor(spec, *self._cfar, return_ratio=True)[1]
+
+    def _threshold(self, device):
+        from . import frontend as F
+        if self._thresh is None:
+            self._thresh = F.cfar_threshold(self._nfft, *self._thresh_args, device=device)
+        return self._thresh
+
+    def _components(self, ratio, capacity: int = 65536):
+        from . import frontend as F
+        _, records, count = F.spectrogram_components(ratio, self._threshold(ratio.device), *self._reach, capacity)
+        if count > capacity:
+            raise ValueError(f"the retained rows hold {count} components, capacity is {capacity}: raise the threshold")
+        return records
+
+    def _classify(self, ratio, pairs, records):
+        from . import frontend as F
+        found = F.detections_from_components(ratio, self._threshold(ratio.device), records, len(records), 1, 1, None, self._avg)
+        for d in found:      # frontend.channel_plans, with its search per distinct bandwidth made once per stream, not once per push
+            if d.bandwidth not in self._ratios:
+                self._ratios[d.bandwidth] = F.channel_plans([(d.centre, d.bandwidth)])[0][1:3]
+        plans, extras = [(-float(d.centre),) + self._ratios[d.bandwidth] for d in found], None
+        if self._refine and found:
+            plans, extras = _refine_detections(pairs, self._dev_fmt, found, plans, *self._line)
+        return [dict(r, **self._balanced) for r in _classify_detections(self._model, pairs, self._dev_fmt, found, plans, extras, self._level,
+                                                                        self._squelch, self._as_numpy)]
+
+    def push(self, chunk):
+        import torch
+        from . import frontend as F
+        if self._core.closed:
+            raise ValueError("push after close: the stream has ended")
+        self._as_numpy = not isinstance(chunk, torch.Tensor)
+        n = int(chunk.numel()) if isinstance(chunk, torch.Tensor) else int(np.asarray(chunk).size)
+        if n % 2:
+            raise ValueError(f"a chunk holds whole (I,Q) pairs: {n} components is an odd number")
+        if n == 0:
+            return self._core.push(None, 0)
+        dev = F._device_samples(chunk, self._fmt, self._device)
+        if self._coeffs is not None:
+            dev = F.balance(dev, self._fmt, self._coeffs).view(-1)
+        return self._core.push(dev, n // 2)
+
+    def close(self):
+        return self._core.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if exc[0] is None:
+            self.close()
+        else:      # the block failed: no more device work, only let go of what is held
+            self._core.abandon()
+        return False
+
+
+def detect_stream(self, sample_format, **kw):
+    """detect_iq for a capture that does not fit on the device, or never ends: a DetectStream (which see) that takes the
+    capture a chunk at a time -- push(chunk) returns the detections that closed with it, close() the rest -- and gives, all
+    calls together, the records of detect_iq(whole capture, sample_format, floor="cfar", batched=True, ...), bit for bit, for
+    any chunking.  Keywords: detect_iq's nfft, avg, threshold_db, cfar, reach_rows, reach_bins, min_rows, min_bins, level,
+    squelch_dbfs, dc_guard, refine, min_line_db, line_nfft, line_avg, and balance (False, or a coefficients tuple; True would
+    estimate from the whole capture: ValueError); max_rows (default 4096) bounds what the stream holds against an emitter that
+    never pauses.  A floor= other than "cfar" is a ValueError: "flat" and "per-bin" are quantiles over the whole capture.
+    "cf32" chunks go through frontend.quantize_cf32(chunk, full_scale=...) first, which is stateless per chunk."""
+    return DetectStream(self, sample_format, **kw)

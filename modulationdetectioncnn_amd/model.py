@@ -993,6 +993,7 @@ class VTCNN2:
     # ------------------------------------------------------------------ wideband captures (capture.py: functions of a model)
     scan_iq = capture.scan_iq
     detect_iq = capture.detect_iq
+    detect_stream = capture.detect_stream
     predict_channels = capture.predict_channels
 
     # ------------------------------------------------------------------ measurement hooks
